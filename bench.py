@@ -15,6 +15,10 @@ reproduces them).  `--workload k10` is rounds 1-2's line (MaxTerm = 2, MaxMsgKey
 
 `python bench.py --gpus N` (N > 1) starts its own N ranks, one per GPU; each builds the RCCL communicator (mc_comm_*) and
 runs the library's sharded level loop (mc_shard_run) on the SAME complete graph ("scaling": "strong").
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what needs runs of its own: the synthetic
+atomic-counter series, BASELINE configs 4 and 5 on one GPU, the compiled-PlusCal models and the multi-threaded CPU oracle baseline.
+`--dump-outputs DIR` writes what the last timed step returned (its counters and per-level distinct counts) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -289,6 +293,21 @@ def dist_roofline(state_bytes, distinct, generated, world, step_s):
             "note": "per GPU, whole step: (2 W D + 8 G) / N bytes over the step's wall time; no kernel-level figure and no counters for the sharded step"}
 
 
+def dump_outputs(out_dir, res):
+    """What the last timed step returned to its caller (mc_engine_run / mc_shard_run's mc_result), one float64 array per field:
+    exact for counts below 2^53.  The wall time of the step is left out; the stored states themselves are not returned by the
+    timed call (and their order in the arena is not fixed from run to run)."""
+    import numpy as np
+    from tla_rust_amd.binding import VERDICTS
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {"distinct": [res.distinct], "generated": [res.generated], "depth": [res.depth], "queue_left": [res.queue_left],
+              "verdict": [VERDICTS.index(res.verdict)], "violated_invariant": [res.violated_invariant],
+              "level_distinct": list(res.get("levels", []))}
+    for name, v in arrays.items():
+        np.save(d / f"{name}.npy", np.asarray(v, dtype=np.float64))
+
+
 def golden():
     g = json.loads((ROOT / "tests" / "golden" / WORKLOAD.get("golden_file", "raft_levels.json")).read_text())
     c = dict(next(c for c in g["cases"] if c["name"] == WORKLOAD["golden"]))
@@ -508,6 +527,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)   # 40 complete BFS runs of 50 ms: two seconds of GPU work in the timed region
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="also the objects that take runs of their own: atomic_add, config4/5_model_one_gpu, "
+                    "pcal and cpu_baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-atomic-add", action="store_true", help="skip the synthetic N-process atomic-counter object of the line")
     ap.add_argument("--no-pcal", action="store_true", help="skip the compiled-PlusCal object of the line (two models as generated code: MC_F_JIT)")
@@ -678,6 +700,8 @@ def main():
         eng.close()
         comm.close()
         return
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, res)
     D, G = res.distinct, res.generated
     if not a.max_distinct:
         # parity gate: the measured run must BE the golden graph (exact counts, per-level where the engine reports them)
@@ -745,18 +769,18 @@ def main():
         stag, ek = expand_kernel_name(WORKLOAD["spec"], WORKLOAD["params"], a.no_family, a.matrix)
         line["roofline"] = kernel_roofline(ks, dt / a.steps, WORKLOAD["spec"], stag, slots, G0["distinct"] + (1 << 20), G, ek,
                                            no_family=a.no_family, matrix=a.matrix, dense_table=a.dense_table)
-        if not a.no_atomic_add and not a.max_distinct and a.workload == "t3":   # (the contract line carries both of north_star's workloads)
+        if a.full and not a.no_atomic_add and not a.max_distinct and a.workload == "t3":   # (with --full the line carries both of north_star's workloads)
             eng.close()
             line["atomic_add"] = atomic_add_series(amd, local)
-        if not a.no_other_configs and not a.max_distinct and a.workload == "t3" and not a.matrix and not a.no_family:
+        if a.full and not a.no_other_configs and not a.max_distinct and a.workload == "t3" and not a.matrix and not a.no_family:
             # ... and BASELINE configs 4 and 5 as far as one GPU holds them (a few seconds: two engines of 200 GB and 30 GB come and go)
             eng.close()
             line["config4_model_one_gpu"] = other_config(amd, local, "raft5")
             line["config5_model_one_gpu"] = other_config(amd, local, "ssi4x3")
-        if not a.no_pcal and not a.max_distinct and a.workload == "t3" and not a.matrix and not a.no_family:
+        if a.full and not a.no_pcal and not a.max_distinct and a.workload == "t3" and not a.matrix and not a.no_family:
             eng.close()
             line["pcal"] = pcal_series(amd, local)
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
     print(json.dumps(line), flush=True)
 

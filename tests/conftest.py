@@ -13,8 +13,9 @@ sys.path.insert(0, str(ROOT / "tests"))
 # box has no /root/reference, so there the built-in lowerings are accepted unverified (the report says so).
 import os  # noqa: E402
 _REF = Path("/root/reference/examples")
-if _REF.exists():
+if os.path.isdir(_REF):   # (False, not an error, where the directory cannot be looked at)
     os.environ.setdefault("TLA_PATH", str(_REF))
+    os.environ.setdefault("TLAMC_REFERENCE", str(_REF.parent))
 else:
     os.environ.setdefault("TLAMC_UNVERIFIED", "1")
 

@@ -332,3 +332,24 @@ def run_with_master_port(make_cmd, tries=4, **kw):
         if p.returncode == 0 or "EADDRINUSE" not in (p.stderr or "") + (p.stdout or ""):
             return p
     return p
+
+
+# How many processes the GPU tests may keep on the device at once.  The shared MI355X hosts that check this suite stop the WHOLE
+# GPU run when more than 6 processes have the GPU open: a clean-checkout run with the 8-rank tests (10 such processes: pytest, the
+# launcher, 8 ranks) was killed there before smoke and the benchmark could start.  No process can read that limit from the host,
+# so 6 is the default; set $TLAMC_TEST_GPU_PROCS (16 on a host of your own) to run the 8-rank cases too.
+GPU_PROCS_DEFAULT = 6
+
+
+def gpu_procs_allowed():
+    return int(os.environ.get("TLAMC_TEST_GPU_PROCS", GPU_PROCS_DEFAULT))
+
+
+def need_gpu_procs(n):
+    """skip the calling test, before it starts anything, when it would keep `n` processes on the GPU at once (count the pytest
+    process itself, its ranks and a launcher that loads the HIP runtime)"""
+    import pytest
+    allowed = gpu_procs_allowed()
+    if n > allowed:
+        pytest.skip(f"needs {n} processes with the GPU open at once; the suite allows {allowed} ($TLAMC_TEST_GPU_PROCS, default 6: "
+                    f"the shared hosts that check it stop the whole GPU run above 6)")

@@ -68,3 +68,71 @@ def test_the_eight_rank_forms_of_configs_4_and_5_go_one_level_deeper():
     b.WORKLOAD = dict(raft, max_levels=13, reduced_levels=13)
     G0 = b.golden()
     assert G0["prefix_levels"] == [1, 6, 40, 205, 775, 2851, 10000, 32015, 97215, 287510, 816406, 2225540, 5913945] and G0["distinct"] == sum(G0["prefix_levels"])
+
+
+
+def test_dump_outputs_option_writes_the_last_timed_steps_result(tmp_path, monkeypatch, capsys):
+    """`bench.py --steps 3 --warmup 2 --dump-outputs DIR` through main(), the engine replaced by a stand-in that returns the golden
+    graph with a different queue_left on each call: the dump holds the FIFTH (last timed) call's result, every field float64, exact"""
+    import sys
+    import numpy as np
+    import torch
+    import tla_rust_amd as amd
+    from tla_rust_amd.binding import Result
+    b = _bench()
+    g = json.loads((ROOT / "tests" / "golden" / "raft_levels.json").read_text())
+    c = next(c for c in g["cases"] if c["name"] == b.WORKLOAD_T3["golden"])
+    calls = []
+
+    class StandIn:
+        def __init__(self, *args, **kw):
+            pass
+
+        def run(self):
+            calls.append(len(calls))
+            return Result(distinct=c["distinct"], generated=c["generated"], queue_left=len(calls) - 1, depth=c["depth"], verdict="ok",
+                          violated_invariant=-1, trace_len=0, levels=list(c["levels"]), seconds=0.125, host_evaluated=False,
+                          unchecked_properties=0)
+
+        def kernel_stats(self):
+            k = {"launches": 1, "ms_total": 1.0, "units": 1}
+            return {"expand": k, "insert": k, "materialise": k, "state_bytes": 136, "cand_cells": 1, "inwave_states": 0}
+
+        def close(self):
+            pass
+
+    monkeypatch.setattr(amd, "Engine", StandIn)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    for v in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(v, raising=False)
+    out = tmp_path / "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(out)])
+    b.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert len(calls) == 5 and line["steps"] == 3 and line["warmup"] == 2 and line["ms_per_step"] > 0
+    assert "cpu_baseline" not in line and "atomic_add" not in line and "pcal" not in line   # (a plain run: those need --full)
+    got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["queue_left"].tolist() == [4.0]                                               # the last timed step's, not a warm-up's
+    assert got["depth"].tolist() == [c["depth"]] and got["violated_invariant"].tolist() == [-1.0]
+    assert got["distinct"].tolist() == [c["distinct"]] and got["generated"].tolist() == [c["generated"]]
+    assert got["level_distinct"].tolist() == c["levels"] and got["verdict"].tolist() == [0.0]
+
+
+def test_dumped_outputs_are_the_last_steps_result_in_float64(tmp_path):
+    """`--dump-outputs DIR`: one float64 array per field of the result the timed call returned, exact for the workload's counts"""
+    import numpy as np
+    from tla_rust_amd.binding import Result
+    b = _bench()
+    g = json.loads((ROOT / "tests" / "golden" / "raft_levels.json").read_text())
+    c = next(c for c in g["cases"] if c["name"] == b.WORKLOAD_T3["golden"])
+    res = Result(distinct=c["distinct"], generated=c["generated"], queue_left=0, depth=c["depth"], verdict="ok", violated_invariant=-1,
+                 trace_len=0, levels=list(c["levels"]), seconds=0.125, host_evaluated=False, unchecked_properties=0)
+    b.dump_outputs(tmp_path / "out", res)
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").glob("*.npy")}
+    assert set(got) == {"distinct", "generated", "depth", "queue_left", "verdict", "violated_invariant", "level_distinct"}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["generated"][0] == c["generated"] and got["distinct"][0] == c["distinct"] == got["level_distinct"].sum()
+    assert got["level_distinct"].tolist() == c["levels"] and got["verdict"][0] == 0
+    assert got["depth"].tolist() == [c["depth"]] and got["queue_left"].tolist() == [0.0] and got["violated_invariant"].tolist() == [-1.0]

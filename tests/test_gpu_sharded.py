@@ -73,6 +73,8 @@ def test_the_three_forms_of_a_stay_level_on_gpu(oracle, tmp_path, form, extra):
 def test_native_rccl_loop_exchange_forms(exchange):
     """`mc X.tla -gpus 4 -samedevice -exchange packed | measured | exact` (exact is the default the other tests run): the native loop over
     the nccl* entry points with each form of the stay levels — the one-GPU run's counter line, and the report's exchange line"""
+    import helpers
+    helpers.need_gpu_procs(2 + 4)   # pytest, `mc`, its ranks
     from pathlib import Path
     S = Path(__file__).resolve().parent.parent / "specs"
     args = [S / "MCraft.tla", "-config", S / "MCraft.cfg", "-maxdistinct", 3000000, "-tablelog2", 24, "-arena", 6000000, "-chunk", 65536]
@@ -158,6 +160,8 @@ def test_invariant_counterexample_across_ranks(oracle, tmp_path, spec, params, l
 def test_eight_engines_on_one_gpu(oracle, tmp_path, world):
     """N = 4 and 8 HIP step engines (the widths of the driver's scaling run) sharing this one GPU, exchange staged
     through gloo: exercises the 8-owner routing / compaction / block plans of the device code"""
+    import helpers
+    helpers.need_gpu_procs(2 + world)   # pytest, the launcher, the ranks
     params = [2, 2, 2, 9, 2, 1]
     o = oracle.oracle_run("raft", params, max_distinct=40000)
     r = run_dist("hip", world, "raft", params, tmp_path, {"max_distinct": 40000, "chunk": 1 << 11, "table": 1 << 18, "arena": 1 << 17,
@@ -170,6 +174,8 @@ def test_eight_engines_on_one_gpu(oracle, tmp_path, world):
 @pytest.mark.parametrize("world,until", [(1, 300), (2, 300), (4, 50)])
 def test_replicated_prefix_on_gpu(oracle, tmp_path, world, until):
     """mc_shard_begin_replicated: the fused single-GPU BFS on every rank for the small levels, then slices"""
+    import helpers
+    helpers.need_gpu_procs(2 + world)   # pytest, the launcher, the ranks
     params = [2, 2, 2, 9, 2, 1]
     o = oracle.oracle_run("raft", params, max_distinct=40000)
     r = run_dist("hip", world, "raft", params, tmp_path, {"max_distinct": 40000, "chunk": 1 << 11, "table": 1 << 18, "arena": 1 << 17,
@@ -278,6 +284,8 @@ def test_native_rccl_loop_with_several_ranks(world):
     """`mc X.tla -gpus P -samedevice`: P forked ranks, mc_comm_create / mc_shard_run over the nccl* entry points (stand-in), the
     C++ level loop with replicated prefix, move and stay levels: the one-GPU `mc`'s counter line — raft (3 servers, 3 M states:
     several rounds per level), the SI model under SYMMETRY, the compiled PlusCal path, Paxos under SYMMETRY with its PROPERTY"""
+    import helpers
+    helpers.need_gpu_procs(2 + world)   # pytest, `mc`, its ranks
     from pathlib import Path
     S = Path(__file__).resolve().parent.parent / "specs"
     env = _fake_env()
@@ -337,6 +345,8 @@ def test_bench_contract_invocation_with_several_ranks(world):
     communicator (id through a file in a directory of the job's own: no port to lose, round 3's GPUTEST failure), run mc_shard_run on
     the COMPLETE bench graph and rank 0 prints the line.  Here the
     ranks share this one GPU (--share-gpu + stand-in): a functional run, the line says so.  P = 8: the frontier stays balanced."""
+    import helpers
+    helpers.need_gpu_procs(1 + world)   # pytest, the ranks (bench.py starts them before it loads the HIP runtime)
     import json
     import subprocess
     import sys
@@ -366,6 +376,8 @@ def test_the_eight_rank_deep_command_lines_of_configs_4_and_5_at_a_reduced_budge
     bench.py itself; seen-set and arenas sized for it) and the eight ranks on this one GPU (--share-gpu + stand-in): the N-rank engine
     walks BASELINE config 4's five-server raft model and config 5's 4 x 3 snapshot-isolation model through replicated, stay and move
     levels and reproduces the oracle's per-level counts."""
+    import helpers
+    helpers.need_gpu_procs(1 + 8)   # pytest, the ranks (bench.py starts them before it loads the HIP runtime)
     import json
     import subprocess
     import sys
@@ -445,6 +457,8 @@ def test_native_checkpoint_per_rank_and_recover(world, tmp_path):
     seen-set slice as it lies in HBM, counters, level table; testout1:10's line is printed once all files are written);
     `mc X.tla -gpus P -recover F` in NEW processes continues with the unexpanded frontier: the counter line of the continued run
     equals the uninterrupted one-GPU run's.  The stop lies in the sharded part (3 M of 6.7 M states: stay levels)"""
+    import helpers
+    helpers.need_gpu_procs(2 + world)   # pytest, `mc`, its ranks
     from pathlib import Path
     S = Path(__file__).resolve().parent.parent / "specs"
     env = _fake_env()

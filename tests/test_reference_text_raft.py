@@ -11,6 +11,7 @@ what it produces; on the GPU box (no /root/reference) the fixture alone is compa
 """
 import hashlib
 import json
+import os
 import sys
 from pathlib import Path
 
@@ -68,7 +69,7 @@ def test_c_oracle_and_lowering_equal_the_deep_reference_text_fixture(tmp_path):
         assert digests(dump) == g["level_digests"]
 
 
-@pytest.mark.skipif(not REF.exists(), reason="/root/reference is only present in the build container")
+@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is not on this host")
 @pytest.mark.parametrize("name", ["raft_2s_mcr1"])   # the others: python tests/golden/make_reference_text_golden.py raft <name> (1 - 15 min each)
 def test_fixture_is_what_the_reference_text_gives(name):
     r = run_raft_text(name)
@@ -105,7 +106,7 @@ def _sweep_config(seed):
     return [n, mcr, mt, mll, mm, inv], mk
 
 
-@pytest.mark.skipif(not REF.exists(), reason="/root/reference is only present in the build container")
+@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is not on this host")
 @pytest.mark.parametrize("seed", range(16))
 def test_c_oracle_equals_the_reference_text_on_random_configurations(seed, tmp_path):
     """the reference's raft.tla, evaluated from its TEXT by the product's C++ evaluator (tlaeval.cpp) under seeded random constants

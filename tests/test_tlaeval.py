@@ -27,7 +27,7 @@ sys.path.insert(0, str(ROOT / "oracle"))
 sys.path.insert(0, str(ROOT / "tests" / "golden"))
 S = Path("/root/reference/examples/SpecifyingSystems")
 SEARCH = [S / d for d in ("Standard", "CachingMemory", "TLC", "FIFO", "AsynchronousInterface", "HourClock", "Liveness", "RealTime", "AdvancedExamples")]
-needs_reference = pytest.mark.skipif(not S.exists(), reason="/root/reference is only present in the build container")
+needs_reference = pytest.mark.skipif(not os.path.isdir(S), reason="the reference tree is not on this host")
 V_OK, V_INVARIANT, V_ASSERT, V_DEADLOCK, V_SPECERR, V_BUDGET = range(6)
 
 
@@ -423,8 +423,8 @@ def test_mc_no_behavior_spec_mode(tmp_path):
     import subprocess
     mc = ROOT / "tla_rust_amd" / "_build" / "mc"
     ref = Path("/root/reference/examples")
-    if not ref.is_dir():
-        pytest.skip("the reference tree is not on this box")
+    if not os.path.isdir(ref):
+        pytest.skip("the reference tree is not on this host")
     env = dict(os.environ, TLA_PATH=str(ref))
     p = subprocess.run([str(mc), str(ref / "SpecifyingSystems" / "SimpleMath" / "SimpleMath.tla")], capture_output=True, text=True, timeout=120, env=env)
     assert p.returncode == 0 and "Model checking completed. No error has been found." in p.stdout and "0 states generated" in p.stdout, (p.stdout, p.stderr)
