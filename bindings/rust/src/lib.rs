@@ -31,6 +31,24 @@ pub struct mc_result {
     pub violated_invariant: i32, pub trace_len: u32, pub levels: u32, pub host_evaluated: u32, pub unchecked_properties: u32, pub seconds: f64,
     pub level_distinct: [u64; MC_MAX_LEVELS],
 }
+// simulation mode (TLC's -simulate num=N -depth D -seed S): mc_engine_simulate, mc_simulate_files
+pub const MC_SIM_END_DEPTH: u32 = 1;
+pub const MC_SIM_END_VIOLATION: u32 = 2;
+pub const MC_SIM_END_DEADLOCK: u32 = 3;
+pub const MC_SIM_END_OUT_OF_MODEL: u32 = 4;
+pub const MC_SIM_END_STUTTER: u32 = 5;
+pub const MC_SIM_END_OVERFLOW: u32 = 6;
+pub const MC_SIM_MAX_DEPTH: u32 = 1000000;
+#[repr(C)]
+pub struct mc_sim_opts {
+    pub num: u64, pub seed: u64, pub depth: u32, pub record: u32,
+    pub record_slots: *mut i32, pub record_len: *mut u32, pub record_end: *mut u32,
+}
+#[repr(C)]
+pub struct mc_sim_result {
+    pub walks: u64, pub steps: u64, pub generated: u64, pub violating_walk: u64, pub max_depth: u32, pub verdict: i32,
+    pub violated_invariant: i32, pub trace_len: u32, pub seconds: f64,
+}
 #[repr(C)]
 pub struct mc_engine { _private: [u8; 0] }
 #[repr(C)]
@@ -41,6 +59,7 @@ extern "C" {
     pub fn mc_engine_run(e: *mut mc_engine, out: *mut mc_result) -> c_int;
     pub fn mc_engine_step(e: *mut mc_engine, levels: u32, out: *mut mc_result) -> c_int;
     pub fn mc_engine_request_stop(e: *mut mc_engine) -> c_int;
+    pub fn mc_engine_simulate(e: *mut mc_engine, opts: *const mc_sim_opts, out: *mut mc_sim_result) -> c_int;
     pub fn mc_engine_trace(e: *mut mc_engine, states: *mut u8, actions: *mut i32, n_inout: *mut usize) -> c_int;
     pub fn mc_engine_read_states(e: *mut mc_engine, first: u64, count: u64, out: *mut u8) -> c_int;
     // TLC's checkpoint / -recover (testout1:10): write / reload the states found so far; the next run continues
@@ -55,6 +74,8 @@ extern "C" {
                             prog_out: *mut *mut mc_program) -> c_int;
     pub fn mc_check_files(tla: *const c_char, cfg_path: *const c_char, cfg: *const mc_config, report: *mut c_char,
                           cap: usize, out: *mut mc_result) -> c_int;
+    pub fn mc_simulate_files(tla: *const c_char, cfg_path: *const c_char, cfg: *const mc_config, opts: *const mc_sim_opts,
+                             report: *mut c_char, cap: usize, out: *mut mc_sim_result, interrupt: *const c_int) -> c_int;
     // PlusCal front-end: `pcal2tla` and the compiler to the GPU interpreter (include/tlamc.h)
     pub fn mc_pcal_translate(tla_text: *const c_char, out: *mut c_char, cap: usize) -> c_int;
     pub fn mc_program_compile(tla_text: *const c_char, cfg_text: *const c_char, out: *mut *mut mc_program) -> c_int;

@@ -193,6 +193,47 @@ int mc_engine_kernel_stats(mc_engine *e, mc_kernel_stats *out);
 /* copy `count` resident states starting at arena index `first` (discovery order: level by level)
  * to the host, mc_state_bytes() bytes each — TLC's "states/" dump, for tests and tooling */
 int mc_engine_read_states(mc_engine *e, uint64_t first, uint64_t count, uint8_t *out);
+
+/* ------------------------------------------------------------------ simulation (TLC's `-simulate [num=N] -depth D -seed S`)
+ * Random walks from the initial states, one GPU lane per walk, no seen-set.  Walk w (0 <= w < num) is a function of
+ * (seed, w, depth) alone: its initial state is init(H(seed, w) mod num_init); at each step every slot of the current state is
+ * evaluated and checked as the BFS checks it, and the walk takes the enabled, in-model, non-stuttering successor whose slot has
+ * the least H(seed, w, step, slot) (the lower slot on a tie).  A walk ends at `depth` states, at its first violation, at a
+ * deadlock, or when only out-of-model or stuttering successors are left (DESIGN.md "Simulation").  Walks run in rounds of a fixed
+ * size, in index order; a run stops after the first round that holds a violation and reports its lowest-indexed violating walk,
+ * whose counterexample mc_engine_trace then returns.  The same (seed, num, depth) on the same model gives the same result on any
+ * device and with any engine capacities.  mc_engine_request_stop (from the progress callback, which is called after every launch with
+ * (rounds done, generated, states reached, walks completed)) ends the run with MC_V_BUDGET; a stop inside a round reports no violation
+ * of that round, whose lowest-indexed violating walk may not have ended yet.  A later mc_engine_run / mc_engine_step starts the BFS over. */
+#define MC_SIM_END_DEPTH 1         /* the walk reached `depth` states                                          */
+#define MC_SIM_END_VIOLATION 2     /* invariant, Assert, evaluation error, or deadlock with MC_F_DEADLOCK        */
+#define MC_SIM_END_DEADLOCK 3      /* no enabled successor, deadlock checking off                               */
+#define MC_SIM_END_OUT_OF_MODEL 4  /* every enabled successor violates a CONSTRAINT (or the initial state does) */
+#define MC_SIM_END_STUTTER 5       /* only stuttering successors are left                                       */
+#define MC_SIM_END_OVERFLOW 6      /* a fixed-capacity slot array overflowed (the call fails with MC_EOVERFLOW) */
+#define MC_SIM_MAX_DEPTH 1000000
+typedef struct {
+    uint64_t num;             /* walks, at most 2^40; 0 = until a violation, mc_engine_request_stop or 2^40 walks */
+    uint64_t seed;
+    uint32_t depth;           /* states per walk at most (TLC's -depth, default 100), 1 .. MC_SIM_MAX_DEPTH  */
+    uint32_t record;          /* K: record walks 0 .. K-1 into the arrays below (0 = none)                 */
+    int32_t *record_slots;    /* K * depth: [k * depth + s] = slot from state s to state s + 1 of walk k, -1 past its end */
+    uint32_t *record_len;     /* K: states walk k reached (0: it did not run)                               */
+    uint32_t *record_end;     /* K: MC_SIM_END_* of walk k (0: it did not run)                              */
+} mc_sim_opts;
+typedef struct {
+    uint64_t walks;           /* walks completed                                                           */
+    uint64_t steps;           /* states reached, initial states included                                   */
+    uint64_t generated;       /* successors evaluated (+ initial states): the BFS's "states generated" unit  */
+    uint64_t violating_walk;  /* index of the walk the counterexample belongs to (verdict != MC_V_OK / BUDGET) */
+    uint32_t max_depth;       /* states of the longest walk                                                */
+    int32_t verdict;          /* MC_V_OK (num walks, no violation), MC_V_BUDGET (stopped), or the violation's */
+    int32_t violated_invariant; /* as in mc_result                                                         */
+    uint32_t trace_len;       /* states of the counterexample (mc_engine_trace), 0 if none                 */
+    double seconds;
+} mc_sim_result;
+int mc_engine_simulate(mc_engine *e, const mc_sim_opts *opts, mc_sim_result *out);
+
 /* Checkpoint / recover — TLC checkpoints a run into its states/ directory ("-- Checkpointing of run states/01-08-03-18-14-01
  * completed.", reference examples/SpecifyingSystems/AdvancedExamples/testout1:10; .gitignore:2) and continues it with -recover.
  * mc_engine_checkpoint: after an mc_engine_run that ended without a violation (normally MC_V_BUDGET), write every distinct
@@ -525,6 +566,12 @@ int mc_check_files_dump(const char *tla_path, const char *cfg_path, const mc_con
  * "-- Checkpointing of run <path> completed." (testout1:10) */
 int mc_check_files_ckpt(const char *tla_path, const char *cfg_path, const mc_config *cfg, char *report, size_t report_cap,
                         mc_result *out, const char *dump_path, const char *recover_path, const char *checkpoint_path);
+/* `mc X.tla -simulate`: the module and its cfg resolved as mc_check_files resolves them, then mc_engine_simulate with `opts`; the report
+ * (seed, the error and its behaviour as in mc_check_files, "The number of states generated: G", the walks and the longest one) goes
+ * to `report`.  A module without a GPU lowering is refused (MC_ENOSPEC).  *interrupt (optional; a SIGINT handler's flag) stops the
+ * simulation between two launches: the report then says so (MC_V_BUDGET). */
+int mc_simulate_files(const char *tla_path, const char *cfg_path, const mc_config *cfg, const mc_sim_opts *opts, char *report, size_t report_cap,
+                      mc_sim_result *out, const volatile int *interrupt);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,20 @@ class Transport(C.Structure):
                 ("all_to_all_others", T_A2A)]   # optional: NULL (a positional constructor leaves it so) = use all_to_all
 
 
+class SimOpts(C.Structure):
+    _fields_ = [("num", C.c_uint64), ("seed", C.c_uint64), ("depth", C.c_uint32), ("record", C.c_uint32),
+                ("record_slots", C.POINTER(C.c_int32)), ("record_len", C.POINTER(C.c_uint32)), ("record_end", C.POINTER(C.c_uint32))]
+
+
+class SimResult(C.Structure):
+    _fields_ = [("walks", C.c_uint64), ("steps", C.c_uint64), ("generated", C.c_uint64), ("violating_walk", C.c_uint64),
+                ("max_depth", C.c_uint32), ("verdict", C.c_int32), ("violated_invariant", C.c_int32), ("trace_len", C.c_uint32),
+                ("seconds", C.c_double)]
+
+
+SIM_ENDS = {1: "depth", 2: "violation", 3: "deadlock", 4: "out-of-model", 5: "stutter", 6: "overflow"}
+
+
 class Result(dict):
     __getattr__ = dict.__getitem__
 
@@ -117,6 +131,7 @@ def lib():
     L.mc_engine_step.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(CResult)]
     L.mc_engine_set_progress.argtypes = [C.c_void_p, PROGRESS_FN, C.c_void_p, C.c_double]
     L.mc_engine_request_stop.argtypes = [C.c_void_p]
+    L.mc_engine_simulate.argtypes = [C.c_void_p, C.POINTER(SimOpts), C.POINTER(SimResult)]
     L.mc_engine_trace.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]
     L.mc_engine_kernel_stats.argtypes = [C.c_void_p, C.POINTER(KernelStats)]
     L.mc_engine_read_states.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
@@ -281,8 +296,27 @@ class Engine:
         _check(lib().mc_engine_step(self._h, levels, C.byref(r)), "mc_engine_step")
         return _result(r)
 
+    def simulate(self, num, depth=100, seed=0, record=0):
+        """mc_engine_simulate (TLC's -simulate num=N -depth D -seed S): `num` random walks of at most `depth` states (num = 0: until a
+        violation or request_stop).  With record = K the first K walks come back as result.recorded: [{len, end, slots}] (end: one of
+        SIM_ENDS' names, or None for a walk that did not run).  trace() then returns the violating walk's counterexample."""
+        o = SimOpts(num, seed, depth, record)
+        if record:
+            slots = (C.c_int32 * (record * depth))()
+            ln, en = (C.c_uint32 * record)(), (C.c_uint32 * record)()
+            o.record_slots, o.record_len, o.record_end = slots, ln, en
+        r = SimResult()
+        _check(lib().mc_engine_simulate(self._h, C.byref(o), C.byref(r)), "mc_engine_simulate")
+        out = Result(walks=r.walks, steps=r.steps, generated=r.generated, max_depth=r.max_depth, verdict=VERDICTS[r.verdict],
+                     violated_invariant=r.violated_invariant, trace_len=r.trace_len, seconds=r.seconds,
+                     violating_walk=r.violating_walk if r.trace_len else None)
+        if record:
+            out["recorded"] = [dict(len=ln[k], end=SIM_ENDS.get(en[k]), slots=[slots[k * depth + s] for s in range(max(ln[k] - 1, 0))])
+                               for k in range(record)]
+        return out
+
     def trace(self):
-        """[(action name, state text)] of the last counterexample."""
+        """[(action name, state text)] of the last counterexample (of the last run or simulation)."""
         W = lib().mc_state_bytes(C.byref(self.desc))
         cap = C.c_size_t(4096)
         states = C.create_string_buffer(W * cap.value)

@@ -60,6 +60,7 @@ static void set_error(const std::string &s) { mc_set_error_internal(s.c_str()); 
 }  // namespace mc
 #include "engine_kernels.h"   // namespace mc { ... every kernel ... }
 #include "engine_pairs.h"     // k_expand_pairs: the by-pairs expand + insert + write kernel (specs with S::PAIR_FAMILIES)
+#include "engine_sim.h"       // k_simulate: simulation mode, one lane per random walk (mc_engine_simulate)
 namespace mc {
 
 // ------------------------------------------------------------------------------------- host side
@@ -116,6 +117,7 @@ struct EngineBase {
     virtual int shard_checkpoint(const char *path) = 0;
     virtual int shard_restore(const char *path) = 0;
     virtual size_t state_bytes() const = 0;
+    virtual int simulate(const mc_sim_opts *opts, mc_sim_result *out) = 0;
 };
 
 static uint64_t round_pow2(uint64_t v) {
@@ -294,6 +296,7 @@ struct Engine : EngineBase {
         if (d_prank) hipFree(d_prank);
         if (d_ctr) hipFree(d_ctr);
         if (h_ctr) hipHostFree(h_ctr);
+        sim_free();
         if (d_lc) hipFree(d_lc);
         if (h_lc) hipHostFree(h_lc);
         for (int i = 0; i < 2; i++) { if (ev_e[i]) hipEventDestroy(ev_e[i]); if (ev_m[i]) hipEventDestroy(ev_m[i]); }
@@ -430,6 +433,7 @@ struct Engine : EngineBase {
         out->violated_invariant = -1;
         memset(kstat, 0, sizeof kstat);
         have_viol = false;
+        sim_trace_n = 0;
         stop_requested = false;
         have_run = false;  // set again on the success path only: a run that fails half-way (MC_EARENA, MC_ETABLEFULL, MC_EOVERFLOW)
                            // leaves fingerprints of an unfinished level in the seen-set — the next step / checkpoint must not continue it
@@ -817,6 +821,7 @@ struct Engine : EngineBase {
         return MC_OK;
     }
     int trace(uint8_t *states_out, int32_t *actions_out, size_t *n_inout) override {
+        if (sim_trace_n) return sim_trace_out(states_out, actions_out, n_inout);
         if (!have_viol) { *n_inout = 0; return MC_OK; }
         HIP_TRY(hipSetDevice(cfg.device));
         const unsigned kind = (unsigned)(last_viol & 7u), slot = (unsigned)(last_viol >> 8 & 0xffffu);
@@ -1602,6 +1607,197 @@ struct Engine : EngineBase {
         }
         return MC_OK;
     }
+    // ------------------------------------------------------------------------------- simulation (mc_engine_simulate; engine_sim.h)
+    // Walks run in rounds of SIM_ROUND (fixed: a run's result must not depend on the device), each round in launches of SIM_ITERS
+    // walk events; the host reads the counters between launches (stop requests, progress, the end of a round).  The walk buffers are
+    // allocated on first use and live until the engine is destroyed; they are not the BFS's arena.
+    static constexpr uint64_t SIM_ROUND = 1ull << 18;
+    static constexpr uint32_t SIM_ITERS = 16;
+    static constexpr uint64_t SIM_MAX_WALKS = 1ull << 40;   // walk indices of a run (the walk field of a violation key, sim_walk.h)
+    uint64_t *d_sim_buf[2] = {nullptr, nullptr};
+    uint32_t *d_sim_wst = nullptr;
+    SimCounters *d_sim_ctr = nullptr;
+    uint64_t sim_cap = 0;
+    std::vector<uint64_t> sim_trace_rows;  // the counterexample of the last simulation (rows in S's layout) and its action ids
+    std::vector<int32_t> sim_trace_acts;
+    size_t sim_trace_n = 0;
+    void sim_free() {
+        for (auto &b : d_sim_buf) { if (b) hipFree(b); b = nullptr; }
+        if (d_sim_wst) hipFree(d_sim_wst);
+        if (d_sim_ctr) hipFree(d_sim_ctr);
+        d_sim_wst = nullptr;
+        d_sim_ctr = nullptr;
+        sim_cap = 0;
+    }
+    int sim_alloc(uint64_t lanes) {
+        lanes = (lanes + 63) & ~63ull;
+        if (sim_cap >= lanes) return MC_OK;
+        sim_free();
+        HIP_TRY(hipMalloc(&d_sim_buf[0], lanes * W * sizeof(uint64_t)));
+        HIP_TRY(hipMalloc(&d_sim_buf[1], lanes * W * sizeof(uint64_t)));
+        HIP_TRY(hipMalloc(&d_sim_wst, lanes * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&d_sim_ctr, sizeof(SimCounters)));
+        sim_cap = lanes;
+        return MC_OK;
+    }
+    // one round: walks w0 .. w0+n-1 from their start to their end (or to a stop request); the counters accumulate in d_sim_ctr.
+    // *complete: every walk of the round ended.  Progress is reported (and a stop request seen) after EVERY launch, the round's last
+    // one included: a model whose walks all end within one launch must not run an unbounded simulation past mc_engine_request_stop.
+    int sim_round(SimArgs a, uint64_t n, SimCounters &c, uint64_t walks_before, bool allow_stop, uint64_t rounds_done, bool *complete) {
+        a.n = n;
+        a.ncols = (n + 63) & ~63ull;
+        *complete = false;
+        HIP_TRY(hipMemsetAsync(d_sim_wst, 0, n * sizeof(uint32_t), stream));
+        const unsigned blocks = (unsigned)((a.ncols + 255) / 256);
+        const uint64_t launches = ((uint64_t)a.depth + 1 + SIM_ITERS - 1) / SIM_ITERS;  // depth + 1 events end every walk
+        for (uint64_t l = 0; l < launches; ++l) {
+            hipLaunchKernelGGL(k_simulate<S>, dim3(blocks), dim3(256), 0, stream, prm, a);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&c, d_sim_ctr, sizeof c, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (c.error) break;
+            if (allow_stop) report_progress((uint32_t)rounds_done, c.generated, c.steps, c.walks);
+            if (c.walks - walks_before >= n) { *complete = true; break; }
+            if (allow_stop && stop_requested) break;
+        }
+        return MC_OK;
+    }
+    int simulate(const mc_sim_opts *o, mc_sim_result *out) override {
+        memset(out, 0, sizeof *out);
+        out->violated_invariant = -1;
+        if (!o || o->depth < 1 || o->depth > MC_SIM_MAX_DEPTH || (o->record && (!o->record_slots || !o->record_len || !o->record_end))) {
+            set_error("simulate: depth must be 1 .. MC_SIM_MAX_DEPTH, and a record request needs its three arrays");
+            return MC_EBADCFG;
+        }
+        if (o->num > SIM_MAX_WALKS) { set_error("simulate: at most 2^40 walks"); return MC_EBADCFG; }
+        if (cfg.shard_count > 1) { set_error("simulate: not available for a sharded engine"); return MC_EBADCFG; }
+        // the BFS's resident search is no longer continued by mc_engine_step, nor checkpointed
+        have_run = have_viol = false;
+        ck_pending = ck_in_place = false;
+        stop_requested = false;
+        sim_trace_n = 0;
+        sim_trace_rows.clear();
+        sim_trace_acts.clear();
+        HIP_TRY(hipSetDevice(cfg.device));
+        const uint64_t lanes = o->num && o->num < SIM_ROUND ? o->num : SIM_ROUND;
+        int rc = sim_alloc(lanes);
+        if (rc) return rc;
+        const uint64_t K = o->record;
+        int32_t *d_rslots = nullptr;
+        uint32_t *d_rlen = nullptr;
+        struct Freer { std::vector<void *> p; ~Freer() { for (void *q : p) hipFree(q); } } freer;
+        if (K) {
+            HIP_TRY(hipMalloc(&d_rslots, K * o->depth * sizeof(int32_t)));
+            freer.p.push_back(d_rslots);
+            HIP_TRY(hipMalloc(&d_rlen, 2 * K * sizeof(uint32_t)));
+            freer.p.push_back(d_rlen);
+            HIP_TRY(hipMemsetAsync(d_rslots, 0xff, K * o->depth * sizeof(int32_t), stream));
+            HIP_TRY(hipMemsetAsync(d_rlen, 0, 2 * K * sizeof(uint32_t), stream));
+        }
+        SimCounters c;
+        memset(&c, 0, sizeof c);
+        c.viol = ~0ull;
+        HIP_TRY(hipMemcpyAsync(d_sim_ctr, &c, sizeof c, hipMemcpyHostToDevice, stream));
+        SimArgs a{};
+        a.seed = o->seed;
+        a.buf0 = d_sim_buf[0];
+        a.buf1 = d_sim_buf[1];
+        a.wst = d_sim_wst;
+        a.depth = o->depth;
+        a.iters = SIM_ITERS;
+        a.deadlock = (cfg.flags & MC_F_DEADLOCK) ? 1u : 0u;
+        a.ctr = d_sim_ctr;
+        a.rec_first = 0;
+        a.rec_count = K;
+        a.rec_slots = d_rslots;
+        a.rec_len = d_rlen;
+        a.rec_end = d_rlen ? d_rlen + K : nullptr;
+        const auto t0 = std::chrono::steady_clock::now();
+        progress_last = t0;
+        bool stopped = false;
+        uint64_t rounds = 0;
+        for (uint64_t first = 0; !o->num || first < o->num; first += SIM_ROUND, ++rounds) {
+            if (first >= SIM_MAX_WALKS) { stopped = true; break; }   // (num = 0: walk indices must stay below 2^40, the width of a key's walk field)
+            const uint64_t n = o->num && o->num - first < SIM_ROUND ? o->num - first : SIM_ROUND;
+            a.w0 = first;
+            const uint64_t before = c.walks;
+            bool complete = false;
+            if ((rc = sim_round(a, n, c, before, true, rounds, &complete))) return rc;
+            if (c.error & DEV_EOVERFLOW) { set_error("packed-state capacity exceeded (raft messages / elections / allLogs slots, or a PlusCal sequence longer than its cells, or a recursive PlusCal procedure deeper than $TLAMC_PCAL_STACK frames)"); return MC_EOVERFLOW; }
+            // stopped inside a round: a violation among the walks that ended need not be the round's lowest-indexed one (a walk of a
+            // lower index may not have ended yet), so none is reported — the run ends like a spent budget, as a stopped BFS does
+            if (!complete) { stopped = true; c.viol = ~0ull; break; }
+            if (c.viol != ~0ull) break;
+            if (stop_requested) { stopped = true; break; }
+        }
+        out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        out->walks = c.walks;
+        out->steps = c.steps;
+        out->generated = c.generated;
+        out->max_depth = c.max_depth;
+        out->verdict = stopped ? MC_V_BUDGET : MC_V_OK;
+        if (K) {
+            HIP_TRY(hipMemcpy(o->record_slots, d_rslots, K * o->depth * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(o->record_len, d_rlen, K * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(o->record_end, d_rlen + K, K * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        }
+        if (c.viol == ~0ull) return MC_OK;
+        const unsigned long long key = c.viol;
+        const unsigned kind = sim_key_kind(key), vslot = sim_key_slot(key);
+        out->verdict = kind == SIM_VK_INVARIANT ? MC_V_INVARIANT : kind == SIM_VK_ASSERT ? MC_V_ASSERT : kind == SIM_VK_DEADLOCK ? MC_V_DEADLOCK : MC_V_SPECERR;
+        if (kind == SIM_VK_INVARIANT) out->violated_invariant = (int)sim_key_inv(key);
+        out->violating_walk = sim_key_walk(key);
+        // the counterexample: walk w once more, alone, in record mode (nothing was kept per walk in the run itself)
+        int32_t *d_tslots = nullptr;
+        uint32_t *d_tlen = nullptr;
+        uint64_t *d_rows = nullptr;
+        HIP_TRY(hipMalloc(&d_tslots, (size_t)o->depth * sizeof(int32_t)));
+        freer.p.push_back(d_tslots);
+        HIP_TRY(hipMalloc(&d_tlen, 2 * sizeof(uint32_t)));
+        freer.p.push_back(d_tlen);
+        HIP_TRY(hipMalloc(&d_rows, ((size_t)o->depth + 1) * W * sizeof(uint64_t)));
+        freer.p.push_back(d_rows);
+        HIP_TRY(hipMemsetAsync(d_tslots, 0xff, (size_t)o->depth * sizeof(int32_t), stream));
+        SimCounters c2;
+        memset(&c2, 0, sizeof c2);
+        c2.viol = ~0ull;
+        HIP_TRY(hipMemcpyAsync(d_sim_ctr, &c2, sizeof c2, hipMemcpyHostToDevice, stream));
+        a.w0 = out->violating_walk;
+        a.rec_first = out->violating_walk;
+        a.rec_count = 1;
+        a.rec_slots = d_tslots;
+        a.rec_len = d_tlen;
+        a.rec_end = d_tlen + 1;
+        a.rec_rows = d_rows;
+        bool complete = false;
+        if ((rc = sim_round(a, 1, c2, 0, false, 0, &complete))) return rc;
+        uint32_t len = 0;
+        HIP_TRY(hipMemcpy(&len, d_tlen, sizeof len, hipMemcpyDeviceToHost));
+        if (c2.viol != key || len < 1 || len > o->depth) { set_error("simulate: the violating walk did not repeat in record mode"); return MC_ESTATE; }
+        const bool extra = kind == SIM_VK_INVARIANT && vslot < SIM_SLOT_PARENT;
+        const size_t n = len + (extra ? 1u : 0u);
+        std::vector<int32_t> slots(len > 1 ? len - 1 : 1);
+        sim_trace_rows.resize(n * W);
+        HIP_TRY(hipMemcpy(sim_trace_rows.data(), d_rows, n * W * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (len > 1) HIP_TRY(hipMemcpy(slots.data(), d_tslots, (len - 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
+        sim_trace_acts.assign(1, -1);
+        for (size_t k = 1; k < len; ++k) sim_trace_acts.push_back(S::action_of(prm, &sim_trace_rows[(k - 1) * W], slots[k - 1]));
+        if (extra) sim_trace_acts.push_back(S::action_of(prm, &sim_trace_rows[(size_t)(len - 1) * W], (int)vslot));
+        sim_trace_n = n;
+        out->trace_len = (uint32_t)n;
+        return MC_OK;
+    }
+    int sim_trace_out(uint8_t *states_out, int32_t *actions_out, size_t *n_inout) {
+        const size_t n = sim_trace_n;
+        if (n > *n_inout) { *n_inout = n; set_error("trace buffer too small"); return MC_EBADCFG; }
+        if constexpr (HasExport<S>::value) {  // rows leave the engine in the spec's PUBLIC layout, as the BFS's traces do
+            for (size_t k = 0; k < n; ++k) S::export_row(prm, &sim_trace_rows[k * W], (uint64_t *)states_out + k * (size_t)S::EXPORT_WORDS);
+        } else
+        memcpy(states_out, sim_trace_rows.data(), n * W * sizeof(uint64_t));
+        memcpy(actions_out, sim_trace_acts.data(), n * sizeof(int32_t));
+        *n_inout = n;
+        return MC_OK;
+    }
     int kernel_stats(mc_kernel_stats *o) override {
         o->expand = kstat[0];
         o->insert = kstat[1];
@@ -1815,6 +2011,9 @@ int mc_engine_request_stop(mc_engine *e) {
 }
 int mc_engine_trace(mc_engine *e, uint8_t *states_out, int32_t *actions_out, size_t *n_inout) {
     return e && n_inout ? e->impl->trace(states_out, actions_out, n_inout) : MC_EBADCFG;
+}
+int mc_engine_simulate(mc_engine *e, const mc_sim_opts *opts, mc_sim_result *out) {
+    return e && opts && out ? e->impl->simulate(opts, out) : MC_EBADCFG;
 }
 int mc_engine_kernel_stats(mc_engine *e, mc_kernel_stats *out) { return e && out ? e->impl->kernel_stats(out) : MC_EBADCFG; }
 int mc_engine_read_states(mc_engine *e, uint64_t first, uint64_t count, uint8_t *out) {

@@ -1209,6 +1209,101 @@ static int host_evaluate(const char *tla_path, const char *cfg_path, const mc_co
     return MC_OK;
 }
 
+// The error part of a report: TLC's message for the violation, the behaviour that leads to it (mc_engine_trace) and, for an Assert,
+// the positions of the failing conjunct.  Both the BFS (mc_check_files_ckpt) and simulation (mc_simulate_files) print it.
+static void put_error_report(Out &o, mc_engine *e, const Resolved &R, int32_t verdict, int32_t violated_invariant, uint32_t trace_len) {
+    const mc_spec_desc &d = R.d;
+    const std::string &tla = R.tla, &module = R.module, &def_text = R.def_text, &def_module_name = R.def_module_name;
+    mc_program *const prog = R.prog;
+    const bool generic = prog != nullptr;
+    if (verdict == MC_V_ASSERT && !generic) {
+        // the message pcal2tla puts into the translation names the position of the `assert` statement in THIS module's
+        // text (pcal_intro.tla:16 col 4 in the reference's layout; the hash that selected the lowering ignores layout)
+        int al = 16, ac = 4;
+        const size_t a0 = tla.find("--algorithm");
+        size_t at = a0 == std::string::npos ? a0 : tla.find("assert", a0);
+        if (at != std::string::npos) {
+            al = 1; ac = 1;
+            for (size_t k = 0; k < at; k++) { if (tla[k] == '\n') { al++; ac = 1; } else ac++; }
+        }
+        o.put("The first argument of Assert evaluated to FALSE; the second argument was:\n\"Failure of assertion at line %d, column %d.\"\n", al, ac);
+    }
+    else if (verdict == MC_V_ASSERT) { /* compiled program: the message names the failing assert, found below */ }
+    else if (verdict == MC_V_INVARIANT && d.spec_id == MC_SPEC_PAXOS && violated_invariant == (d.params[0] == 1 ? 1 : 4))
+        o.put("Error: Action property %s is violated.\n", invariant_name(&d, violated_invariant));  // the step breaks [Next]_v of the PROPERTY
+    else if (verdict == MC_V_INVARIANT) o.put("Error: Invariant %s is violated.\n", invariant_name(&d, violated_invariant));
+    else if (verdict == MC_V_DEADLOCK) o.put("Error: Deadlock reached.\n");
+    else o.put("Error: evaluation error (a function was applied outside its domain).\n");
+    const size_t W = mc_state_bytes(&d);
+    std::string assert_def = "C";  // the action whose Assert failed
+    size_t n = trace_len ? trace_len : 1;
+    std::vector<uint8_t> states(n * W);
+    std::vector<int32_t> acts(n);
+    // action definitions live in the checked module, or in the module an MC wrapper EXTENDS
+    const std::vector<std::string> srcL = split_lines(def_text.empty() ? tla : def_text);
+    const std::string &def_module = def_text.empty() ? module : def_module_name;
+    const bool have_trace = mc_engine_trace(e, states.data(), acts.data(), &n) == MC_OK && n;
+    if (generic && verdict == MC_V_ASSERT) {  // which assert: re-evaluate the last state of the trace on the host
+        std::string msg = "Failure of assertion.";
+        if (have_trace) {
+            const pcal::Program &P = prog->prog;
+            std::vector<int32_t> vals((size_t)P.nv + 1);
+            const uint64_t *w = (const uint64_t *)&states[(n - 1) * W];
+            for (int i = 0; i < P.nv; i++) vals[(size_t)i] = (int32_t)(uint32_t)(w[i / 2] >> (32 * (i & 1)));
+            int label = -1;
+            const int id = mc::vm_failed_assert(&P, vals.data(), &label);
+            if (id >= 0) {
+                msg = "Failure of assertion at line " + std::to_string(P.asserts[(size_t)id].line) + ", column " + std::to_string(P.asserts[(size_t)id].col) + ".";
+                assert_def = P.strings[(size_t)label];
+            }
+        }
+        o.put("The first argument of Assert evaluated to FALSE; the second argument was:\n\"%s\"\n", msg.c_str());
+    }
+    if (have_trace) {
+        o.put("Error: The behavior up to this point is:\n");
+        std::vector<char> txt(1 << 16);
+        for (size_t k = 0; k < n; k++) {
+            mc_state_format(&d, &states[k * W], txt.data(), txt.size());
+            if (acts[k] < 0) { o.put("State %zu: <Initial predicate>\n%s\n\n", k + 1, txt.data()); continue; }
+            const char *an = mc_action_name(&d, acts[k]);
+            const Span sp = definition_span(srcL, an);
+            if (sp.ok)  // README.md:278
+                o.put("State %zu: <Action line %d, col %d to line %d, col %d of module %s>\n%s\n\n", k + 1, sp.l1, sp.c1, sp.l2, sp.c2,
+                      def_module.c_str(), txt.data());
+            else
+                o.put("State %zu: <Action %s of module %s>\n%s\n\n", k + 1, an, def_module.c_str(), txt.data());
+        }
+    }
+    if (verdict == MC_V_ASSERT) {  // README.md:313-316: the conjunct being evaluated and the Assert call itself
+        int first = 0;
+        const Span c = definition_span(srcL, assert_def.c_str(), &first);
+        if (c.ok) {
+            Span a0, a1;
+            const std::string &l0 = srcL[first];
+            size_t b = (size_t)c.c1 - 1;
+            if (l0.compare(b, 2, "/\\") == 0) { b += 2; while (b < l0.size() && l0[b] == ' ') b++; }
+            a0.l1 = a0.l2 = c.l1; a0.c1 = (int)b + 1; a0.c2 = last_nonspace(l0);
+            for (int i = first; i < c.l2; i++) {
+                const size_t at = srcL[i].find("Assert(");
+                if (at == std::string::npos) continue;
+                a1.l1 = i + 1; a1.c1 = (int)at + 1;
+                int depth = 0;
+                for (int j = i; j < c.l2 && !a1.ok; j++)
+                    for (size_t q = (j == i ? at : 0); q < srcL[j].size(); q++) {
+                        if (srcL[j][q] == '(') depth++;
+                        else if (srcL[j][q] == ')' && --depth == 0) { a1.l2 = j + 1; a1.c2 = (int)q + 1; a1.ok = true; break; }
+                    }
+                break;
+            }
+            if (a1.ok) {
+                o.put("Error: The error occurred when TLC was evaluating the nested\nexpressions at the following positions:\n");
+                o.put("0. Line %d, column %d to line %d, column %d in %s\n", a0.l1, a0.c1, a0.l2, a0.c2, def_module.c_str());
+                o.put("1. Line %d, column %d to line %d, column %d in %s\n\n\n", a1.l1, a1.c1, a1.l2, a1.c2, def_module.c_str());
+            }
+        }
+    }
+}
+
 extern "C" void *mc_jit_factory(const void *program);   // pcal_codegen.cpp
 static bool jit_compiler_present() {
     const char *hc = getenv("HIPCC");
@@ -1365,92 +1460,7 @@ int mc_check_files_ckpt(const char *tla_path, const char *cfg_path, const mc_con
         o.put("  Estimates of the probability that TLC did not check all reachable states\n"
               "  because two distinct states had the same fingerprint:\n  calculated (optimistic):  val = %.2g\n", opt);
     } else {
-        if (res->verdict == MC_V_ASSERT && !generic) {
-            // the message pcal2tla puts into the translation names the position of the `assert` statement in THIS module's
-            // text (pcal_intro.tla:16 col 4 in the reference's layout; the hash that selected the lowering ignores layout)
-            int al = 16, ac = 4;
-            const size_t a0 = tla.find("--algorithm");
-            size_t at = a0 == std::string::npos ? a0 : tla.find("assert", a0);
-            if (at != std::string::npos) {
-                al = 1; ac = 1;
-                for (size_t k = 0; k < at; k++) { if (tla[k] == '\n') { al++; ac = 1; } else ac++; }
-            }
-            o.put("The first argument of Assert evaluated to FALSE; the second argument was:\n\"Failure of assertion at line %d, column %d.\"\n", al, ac);
-        }
-        else if (res->verdict == MC_V_ASSERT) { /* compiled program: the message names the failing assert, found below */ }
-        else if (res->verdict == MC_V_INVARIANT && d.spec_id == MC_SPEC_PAXOS && res->violated_invariant == (d.params[0] == 1 ? 1 : 4))
-            o.put("Error: Action property %s is violated.\n", invariant_name(&d, res->violated_invariant));  // the step breaks [Next]_v of the PROPERTY
-        else if (res->verdict == MC_V_INVARIANT) o.put("Error: Invariant %s is violated.\n", invariant_name(&d, res->violated_invariant));
-        else if (res->verdict == MC_V_DEADLOCK) o.put("Error: Deadlock reached.\n");
-        else o.put("Error: evaluation error (a function was applied outside its domain).\n");
-        const size_t W = mc_state_bytes(&d);
-        std::string assert_def = "C";  // the action whose Assert failed
-        size_t n = res->trace_len ? res->trace_len : 1;
-        std::vector<uint8_t> states(n * W);
-        std::vector<int32_t> acts(n);
-        // action definitions live in the checked module, or in the module an MC wrapper EXTENDS
-        const std::vector<std::string> srcL = split_lines(def_text.empty() ? tla : def_text);
-        const std::string &def_module = def_text.empty() ? module : def_module_name;
-        const bool have_trace = mc_engine_trace(e, states.data(), acts.data(), &n) == MC_OK && n;
-        if (generic && res->verdict == MC_V_ASSERT) {  // which assert: re-evaluate the last state of the trace on the host
-            std::string msg = "Failure of assertion.";
-            if (have_trace) {
-                const pcal::Program &P = prog->prog;
-                std::vector<int32_t> vals((size_t)P.nv + 1);
-                const uint64_t *w = (const uint64_t *)&states[(n - 1) * W];
-                for (int i = 0; i < P.nv; i++) vals[(size_t)i] = (int32_t)(uint32_t)(w[i / 2] >> (32 * (i & 1)));
-                int label = -1;
-                const int id = mc::vm_failed_assert(&P, vals.data(), &label);
-                if (id >= 0) {
-                    msg = "Failure of assertion at line " + std::to_string(P.asserts[(size_t)id].line) + ", column " + std::to_string(P.asserts[(size_t)id].col) + ".";
-                    assert_def = P.strings[(size_t)label];
-                }
-            }
-            o.put("The first argument of Assert evaluated to FALSE; the second argument was:\n\"%s\"\n", msg.c_str());
-        }
-        if (have_trace) {
-            o.put("Error: The behavior up to this point is:\n");
-            std::vector<char> txt(1 << 16);
-            for (size_t k = 0; k < n; k++) {
-                mc_state_format(&d, &states[k * W], txt.data(), txt.size());
-                if (acts[k] < 0) { o.put("State %zu: <Initial predicate>\n%s\n\n", k + 1, txt.data()); continue; }
-                const char *an = mc_action_name(&d, acts[k]);
-                const Span sp = definition_span(srcL, an);
-                if (sp.ok)  // README.md:278
-                    o.put("State %zu: <Action line %d, col %d to line %d, col %d of module %s>\n%s\n\n", k + 1, sp.l1, sp.c1, sp.l2, sp.c2,
-                          def_module.c_str(), txt.data());
-                else
-                    o.put("State %zu: <Action %s of module %s>\n%s\n\n", k + 1, an, def_module.c_str(), txt.data());
-            }
-        }
-        if (res->verdict == MC_V_ASSERT) {  // README.md:313-316: the conjunct being evaluated and the Assert call itself
-            int first = 0;
-            const Span c = definition_span(srcL, assert_def.c_str(), &first);
-            if (c.ok) {
-                Span a0, a1;
-                const std::string &l0 = srcL[first];
-                size_t b = (size_t)c.c1 - 1;
-                if (l0.compare(b, 2, "/\\") == 0) { b += 2; while (b < l0.size() && l0[b] == ' ') b++; }
-                a0.l1 = a0.l2 = c.l1; a0.c1 = (int)b + 1; a0.c2 = last_nonspace(l0);
-                for (int i = first; i < c.l2; i++) {
-                    const size_t at = srcL[i].find("Assert(");
-                    if (at == std::string::npos) continue;
-                    a1.l1 = i + 1; a1.c1 = (int)at + 1;
-                    int depth = 0;
-                    for (int j = i; j < c.l2 && !a1.ok; j++)
-                        for (size_t q = (j == i ? at : 0); q < srcL[j].size(); q++) {
-                            if (srcL[j][q] == '(') depth++;
-                            else if (srcL[j][q] == ')' && --depth == 0) { a1.l2 = j + 1; a1.c2 = (int)q + 1; a1.ok = true; break; }
-                        }
-                    break;
-                }
-                if (a1.ok) {
-                    o.put("Error: The error occurred when TLC was evaluating the nested\nexpressions at the following positions:\n");
-                    o.put("0. Line %d, column %d to line %d, column %d in %s\n", a0.l1, a0.c1, a0.l2, a0.c2, def_module.c_str());
-                    o.put("1. Line %d, column %d to line %d, column %d in %s\n\n\n", a1.l1, a1.c1, a1.l2, a1.c2, def_module.c_str());
-                }
-            }
-        }
+        put_error_report(o, e, R, res->verdict, res->violated_invariant, res->trace_len);
     }
     o.put("%llu states generated, %llu distinct states found, %llu states left on queue.\n", (unsigned long long)res->generated,
           (unsigned long long)res->distinct, (unsigned long long)res->queue_left);
@@ -1472,6 +1482,86 @@ int mc_check_files_ckpt(const char *tla_path, const char *cfg_path, const mc_con
         }
         fclose(f);
     }
+    mc_engine_destroy(e);
+    return MC_OK;
+}
+
+// `mc X.tla -simulate` (TLC's -simulate): resolve the module as mc_check_files does, then mc_engine_simulate instead of the BFS.
+// A compiled PlusCal program starts on the device interpreter and moves to its generated code once that is built, as the BFS does
+// (walks are the same on both: the simulation starts over with them).  *interrupt != 0 (the caller's SIGINT handler): stop after the
+// current launch and report what was walked (verdict MC_V_BUDGET).
+int mc_simulate_files(const char *tla_path, const char *cfg_path, const mc_config *cfg, const mc_sim_opts *opts, char *report, size_t report_cap,
+                      mc_sim_result *res, const volatile int *interrupt) {
+    if (!tla_path || !cfg || !opts || !report || !report_cap || !res) return MC_EBADCFG;
+    report[0] = 0;
+    if (no_behavior_cfg(tla_path, cfg_path)) return fe_fail(MC_ENOSPEC, "%s: -simulate needs a behaviour spec", tla_path);
+    Resolved R;
+    int rc = resolve_files(tla_path, cfg_path, cfg->flags, R);
+    if (rc == MC_ENOSPEC && !R.module.empty() && !lowered_family(R.module, R.tla))
+        return fe_fail(MC_ENOSPEC, "%s: -simulate needs a GPU lowering (the module is evaluated on the host)", R.module.c_str());
+    if (rc) return rc;
+    const mc_spec_desc &d = R.d;
+    mc_config c = *cfg;
+    if (R.check_deadlock >= 0) c.flags = R.check_deadlock ? (c.flags | MC_F_DEADLOCK) : (c.flags & ~MC_F_DEADLOCK);
+    struct Watch {
+        mc_engine *e = nullptr;
+        const volatile int *interrupt = nullptr;
+        bool print = false, auto_jit = false, started = false, stopped = false, interrupted = false;
+        double after = 0.3;
+        std::chrono::steady_clock::time_point t0, last_print;
+        const void *program = nullptr;
+        std::shared_ptr<std::atomic<int>> built = std::make_shared<std::atomic<int>>(0);
+    } w;
+    const char *const aje = getenv("TLAMC_AUTOJIT"), *const tje = getenv("TLAMC_JIT"), *const aa = getenv("TLAMC_AUTOJIT_AFTER");
+    w.auto_jit = R.prog && d.spec_id == MC_SPEC_PCAL && d.nparams >= 1 && d.params[0] && !(c.flags & MC_F_JIT) && !(tje && *tje && *tje != '0') &&
+                 !(aje && *aje == '0') && jit_compiler_present();
+    w.after = aa ? atof(aa) : 0.3;
+    w.interrupt = interrupt;
+    w.print = (c.flags & MC_F_PROGRESS) != 0;
+    w.program = (const void *)(intptr_t)(d.nparams ? d.params[0] : 0);
+    w.t0 = w.last_print = std::chrono::steady_clock::now();
+    const auto watch = [](void *u, uint32_t, uint64_t g, uint64_t steps, uint64_t walks) {
+        Watch &a = *(Watch *)u;
+        const auto now = std::chrono::steady_clock::now();
+        if (a.print && std::chrono::duration<double>(now - a.last_print).count() >= 1.0) {   // TLC: "Progress: N states checked, M traces generated"
+            a.last_print = now;
+            printf("Progress: %llu states checked, %llu states generated, %llu walks completed.\n", (unsigned long long)steps, (unsigned long long)g,
+                   (unsigned long long)walks);
+            fflush(stdout);
+        }
+        if (a.interrupt && *a.interrupt) { a.interrupted = true; mc_engine_request_stop(a.e); return; }
+        if (!a.auto_jit) return;
+        if (!a.started && std::chrono::duration<double>(now - a.t0).count() >= a.after) {
+            a.started = true;
+            std::thread([built = a.built, program = a.program] { built->store(mc_jit_factory(program) ? 1 : -1); }).detach();
+        }
+        if (a.started && !a.stopped && a.built->load() == 1) { a.stopped = true; mc_engine_request_stop(a.e); }
+    };
+    mc_engine *e = nullptr;
+    if ((rc = mc_engine_create(&d, &c, &e))) return rc;
+    w.e = e;
+    mc_engine_set_progress(e, watch, &w, 0.02);
+    rc = mc_engine_simulate(e, opts, res);
+    if (!rc && w.stopped && !w.interrupted && res->verdict == MC_V_BUDGET) {   // generated code is there: the same walks, faster
+        mc_engine_destroy(e);
+        e = nullptr;
+        c.flags |= MC_F_JIT;
+        if ((rc = mc_engine_create(&d, &c, &e))) return rc;
+        w.e = e;
+        w.auto_jit = false;
+        mc_engine_set_progress(e, watch, &w, 0.02);
+        rc = mc_engine_simulate(e, opts, res);
+    }
+    if (rc) { mc_engine_destroy(e); return rc; }
+    Out o{report, report_cap, 0};
+    if (!R.warning.empty()) o.put("%s", R.warning.c_str());
+    o.put("Running Random Simulation with seed %llu.\n", (unsigned long long)opts->seed);
+    if (res->verdict == MC_V_OK) o.put("Simulation completed. No error has been found.\n");
+    else if (res->verdict == MC_V_BUDGET) o.put("Simulation stopped; no error has been found so far.\n");
+    else put_error_report(o, e, R, res->verdict, res->violated_invariant, res->trace_len);
+    o.put("The number of states generated: %llu\n", (unsigned long long)res->generated);
+    o.put("Simulation using seed %llu: %llu walks completed, %llu states checked, the longest walk has %u states.\n",
+          (unsigned long long)opts->seed, (unsigned long long)res->walks, (unsigned long long)res->steps, res->max_depth);
     mc_engine_destroy(e);
     return MC_OK;
 }

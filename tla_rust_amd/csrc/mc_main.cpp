@@ -5,6 +5,7 @@
 //   mc X.tla [-config X.cfg] [-deadlock] [-workers N] [-device D] [-generic] [-dump FILE]
 //            [-maxdistinct N] [-maxlevels N] [-tablelog2 T] [-arena N] [-chunk N]
 //            [-checkpoint FILE] [-recover FILE] [-gpus P [-samedevice | -torch] [-exchange exact|measured|packed] [-fanout N]] [-noprogress] [-I DIR]
+//   mc X.tla -simulate [num=N] [-depth D] [-seed S] [-config X.cfg] [-deadlock] [-jit] [-device D] [-noprogress] [-I DIR]
 //   mc --transpile X.tla [Y.tla ...]      the `pcal2tla *tla` of the reference's Makefile:3-4: inserts (or
 //                                         replaces) the TLA+ translation of the PlusCal algorithm in place,
 //                                         the previous text is kept as X.old
@@ -37,9 +38,17 @@
 //             `python3 -m torch.distributed.run --nproc-per-node P -m tla_rust_amd.mc_multi X.tla <the other options>`; that front
 //             door also rebalances drifting ranks by moving states and prints a counterexample walked back across the ranks
 //             ($PYTHON names another interpreter, $MASTER_PORT the rendezvous port).
+// -simulate [num=N] [-depth D] [-seed S]: TLC's random simulation instead of the exhaustive search — N random walks of at most D
+//             states (default 100) from the initial states, every state and successor checked as the search checks them, one GPU
+//             lane per walk (mc_engine_simulate).  Without num= it walks until it finds an error or is interrupted (SIGINT: the report
+//             of what was walked, exit status 0).  Without -seed a seed is drawn; the report prints it, and the same seed, num and
+//             depth give the same walks and the same report.  The report has the error and its behaviour as the search's has, "The
+//             number of states generated: G" and the walks, but no distinct-state count or search depth: nothing was searched
+//             exhaustively.  -gpus, -dump, -checkpoint and -recover do not apply; a module without a GPU lowering is refused.
 // -deadlock : as with TLC, do NOT check for deadlock.  -workers is accepted and ignored (the
 // GPU is the worker pool).  Exit status: 0 no error, 12 safety violation (invariant / assert),
 // 11 deadlock, 1 any other failure — TLC's convention.
+#include <errno.h>
 #include <limits.h>
 #include <signal.h>
 #include <stdio.h>
@@ -274,6 +283,41 @@ static int run_rank(const char *tla, const char *cfgp, mc_config cfg, int rank, 
     return res.verdict == MC_V_DEADLOCK ? 11 : 12;
 }
 
+// a whole decimal number, nothing before or after it (strtoull alone takes "abc" for 0 and "-1" for 2^64 - 1)
+static bool parse_u64(const char *s, uint64_t *out) {
+    if (!s || *s < '0' || *s > '9') return false;
+    errno = 0;
+    char *end = nullptr;
+    const unsigned long long v = strtoull(s, &end, 10);
+    if (errno || *end) return false;
+    *out = v;
+    return true;
+}
+
+// ---- mc X.tla -simulate: the walks of mc_simulate_files; SIGINT stops them between two launches and the report is printed
+static volatile sig_atomic_t g_interrupt = 0;
+static int run_simulation(const char *tla, const char *cfgp, const mc_config &cfg, mc_sim_opts sim, bool have_seed, const char *refused) {
+    if (refused) { fprintf(stderr, "mc: %s is not available with -simulate\n", refused); return 1; }
+    if (!have_seed) {   // TLC draws a seed and prints it, so that the run can be repeated
+        uint64_t s = (uint64_t)time(nullptr) * 0x9e3779b97f4a7c15ull ^ ((uint64_t)getpid() << 32) ^ (uint64_t)clock();
+        FILE *r = fopen("/dev/urandom", "rb");
+        if (r) { if (fread(&s, sizeof s, 1, r) != 1) s ^= 0x5851f42d4c957f2dull; fclose(r); }
+        sim.seed = s >> 1;   // (non-negative, like TLC's long seeds)
+    }
+    signal(SIGINT, [](int) { g_interrupt = 1; });
+    std::vector<char> report(1 << 22);
+    static mc_sim_result res;
+    const int rc = mc_simulate_files(tla, cfgp, &cfg, &sim, report.data(), report.size(), &res, (const volatile int *)&g_interrupt);
+    signal(SIGINT, SIG_DFL);
+    if (rc) {
+        fprintf(stderr, "mc: %s: %s\n", mc_strerror(rc), mc_last_error());
+        return 1;
+    }
+    fputs(report.data(), stdout);
+    if (res.verdict == MC_V_OK || res.verdict == MC_V_BUDGET) return 0;
+    return res.verdict == MC_V_DEADLOCK ? 11 : 12;
+}
+
 int main(int argc, char **argv) {
     setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", 0);   // (RCCL between processes needs dmabuf IPC on this driver; read when the HSA runtime starts)
     int gpus = 0;
@@ -286,6 +330,8 @@ int main(int argc, char **argv) {
         if (!strcmp(argv[i], "-torch")) torch_door = true;
         if (!strcmp(argv[i], "-samedevice")) setenv("MC_SAMEDEVICE", "1", 1);
     }
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "-simulate") && gpus) { fprintf(stderr, "mc: -gpus is not available with -simulate\n"); return 1; }
     if (gpus && torch_door) return exec_multi(gpus, argc, argv);
     const char *env_rank = getenv("MC_RANK");
     if (gpus && !env_rank) {
@@ -298,6 +344,10 @@ int main(int argc, char **argv) {
         return rc;
     }
     const char *tla = nullptr, *cfgp = nullptr, *dump = nullptr, *recover = nullptr, *ckpt = nullptr;
+    bool simulate = false, have_seed = false, have_depth = false;
+    mc_sim_opts sim;
+    memset(&sim, 0, sizeof sim);
+    sim.depth = 100;   // TLC's default -depth
     mc_config cfg;
     memset(&cfg, 0, sizeof cfg);
     cfg.flags = MC_F_DEADLOCK | MC_F_TRACE | MC_F_PROGRESS;  // TLC reports its progress while it runs (testout2:4-259); -noprogress
@@ -306,6 +356,25 @@ int main(int argc, char **argv) {
     for (int i = 1; i < argc; i++) {
         auto arg = [&](const char *name) { return !strcmp(argv[i], name) && i + 1 < argc; };
         if (arg("-config")) cfgp = argv[++i];
+        else if (!strcmp(argv[i], "-simulate")) {
+            simulate = true;
+            if (i + 1 < argc && !strncmp(argv[i + 1], "num=", 4)) {
+                if (!parse_u64(argv[++i] + 4, &sim.num) || !sim.num || sim.num > (1ull << 40)) {
+                    fprintf(stderr, "mc: -simulate num=N needs a number of walks (1..2^40)\n");
+                    return 1;
+                }
+            }
+        }
+        else if (arg("-depth")) {
+            uint64_t v = 0;
+            if (!parse_u64(argv[++i], &v) || v < 1 || v > MC_SIM_MAX_DEPTH) { fprintf(stderr, "mc: -depth needs a number of states (1..%d)\n", MC_SIM_MAX_DEPTH); return 1; }
+            sim.depth = (uint32_t)v;
+            have_depth = true;
+        }
+        else if (arg("-seed")) {
+            if (!parse_u64(argv[++i], &sim.seed)) { fprintf(stderr, "mc: -seed needs a non-negative integer\n"); return 1; }
+            have_seed = true;
+        }
         else if (!strcmp(argv[i], "-deadlock")) cfg.flags &= ~MC_F_DEADLOCK;
         else if (arg("-dump")) dump = argv[++i];
         else if (arg("-checkpoint")) ckpt = argv[++i];
@@ -350,10 +419,13 @@ int main(int argc, char **argv) {
                 "usage: mc X.tla [-config X.cfg] [-deadlock] [-dump FILE] [-generic] [-jit] [-unverified] [-device D] [-I DIR]\n"
                 "                [-maxdistinct N] [-maxlevels N] [-tablelog2 T] [-arena N] [-chunk N]\n"
                 "                [-checkpoint FILE] [-recover FILE] [-gpus P [-torch]]                    check X.tla like `tlc X.tla`\n"
+                "       mc X.tla -simulate [num=N] [-depth D] [-seed S] [...]                             random walks like `tlc -simulate`\n"
                 "       mc --transpile X.tla [Y.tla ...]                                                  translate like `pcal2tla`\n"
                 "exit status: 0 no error, 12 invariant / assertion violated, 11 deadlock, 1 anything else\n");
         return 1;
     }
+    if (!simulate && (have_depth || have_seed)) { fprintf(stderr, "mc: %s needs -simulate\n", have_depth ? "-depth" : "-seed"); return 1; }
+    if (simulate) return run_simulation(tla, cfgp, cfg, sim, have_seed, dump ? "-dump" : ckpt ? "-checkpoint" : recover ? "-recover" : nullptr);
     if (gpus) {  // one rank of `mc X.tla -gpus P`
         if (dump) { fprintf(stderr, "mc: -dump is not available with -gpus\n"); return 1; }
         return run_rank(tla, cfgp, cfg, atoi(env_rank), gpus, getenv("MC_IDFILE"), ckpt, recover);
