@@ -198,7 +198,8 @@ int mc_engine_read_states(mc_engine *e, uint64_t first, uint64_t count, uint8_t 
  * Random walks from the initial states, one GPU lane per walk, no seen-set.  Walk w (0 <= w < num) is a function of
  * (seed, w, depth) alone: its initial state is init(H(seed, w) mod num_init); at each step every slot of the current state is
  * evaluated and checked as the BFS checks it, and the walk takes the enabled, in-model, non-stuttering successor whose slot has
- * the least H(seed, w, step, slot) (the lower slot on a tie).  A walk ends at `depth` states, at its first violation, at a
+ * the least H(seed, w, step, slot) (the lower slot on a tie); a successor equal to its parent counts as stuttering whether or not
+ * the lowering marks it (the terminating disjunct of a PlusCal translation), and is passed over.  A walk ends at `depth` states, at its first violation, at a
  * deadlock, or when only out-of-model or stuttering successors are left (DESIGN.md "Simulation").  Walks run in rounds of a fixed
  * size, in index order; a run stops after the first round that holds a violation and reports its lowest-indexed violating walk,
  * whose counterexample mc_engine_trace then returns.  The same (seed, num, depth) on the same model gives the same result on any

@@ -47,6 +47,7 @@ typedef struct {
     uint32_t cur_level;  /* level (1-based) of the states being created                */
     uint64_t nsucc;
     FILE *dump;
+    FILE *edges;         /* oracle_run_edges: one line per successor on_emit sees (and per initial state) */
     char *pbuf;
     size_t pcap;
     /* first violation */
@@ -175,6 +176,19 @@ static void on_emit(or_emit *em, const uint8_t *s, size_t len, int action, unsig
     b->nsucc++;
     r->generated++;
     if (b->cur_level - 1 < OR_MAX_LEVELS && b->cur != UINT64_MAX) r->level_generated[b->cur_level - 2]++;
+    if (b->edges) {
+        /* "<parent index in dump order, -1 = initial> <action> <flags> <inside the CONSTRAINT> <invariant broken or -1> <text>";
+         * a successor whose evaluation failed (Assert, evaluation error) has no state: -1 -1 and "-" */
+        long long par = b->cur == UINT64_MAX ? -1 : (long long)b->cur;
+        if (flags & (OR_FLAG_ASSERT | OR_FLAG_SPECERR)) fprintf(b->edges, "%lld %d %u -1 -1 -\n", par, action, flags);
+        else {
+            size_t k = sp->print(sp->ctx, s, len, b->pbuf, b->pcap);
+            for (size_t i = 0; i < k; i++)
+                if (b->pbuf[i] == '\n') b->pbuf[i] = ' ';
+            fprintf(b->edges, "%lld %d %u %d %d %.*s\n", par, action, flags, sp->constraint ? sp->constraint(sp->ctx, s, len) : 1,
+                    sp->invariant ? sp->invariant(sp->ctx, s, len) : -1, (int)k, b->pbuf);
+        }
+    }
     if (flags & OR_FLAG_SPECERR) {
         note_violation(b, OR_SPEC_ERROR, -1, b->cur, s, len, action, 0);
         return;
@@ -256,7 +270,7 @@ static double now_s(void) {
     return ts.tv_sec + 1e-9 * ts.tv_nsec;
 }
 
-static int run_bfs(const or_spec *sp, const or_options *opt, or_result *r) {
+static int run_bfs(const or_spec *sp, const or_options *opt, const char *edges_path, or_result *r) {
     bfs_t b;
     memset(&b, 0, sizeof b);
     memset(r, 0, sizeof *r);
@@ -270,6 +284,11 @@ static int run_bfs(const or_spec *sp, const or_options *opt, or_result *r) {
     if (opt->dump_path) {
         b.dump = fopen(opt->dump_path, "w");
         if (!b.dump) { or_set_error("cannot open dump file %s", opt->dump_path); return -1; }
+    }
+    if (edges_path) {
+        if (sp->canon || opt->stop_on_violation == 2) { or_set_error("the edge dump needs a model without SYMMETRY and stop_on_violation != 2"); return -1; }
+        b.edges = fopen(edges_path, "w");
+        if (!b.edges) { or_set_error("cannot open edge file %s", edges_path); return -1; }
     }
     uint8_t *tmp = malloc(sp->max_state_bytes);
     or_emit em = {&b, on_emit};
@@ -320,6 +339,7 @@ done:
     if (b.have_violation) build_trace(&b);
     r->arena_bytes = b.arena_len;
     if (b.dump) fclose(b.dump);
+    if (b.edges) fclose(b.edges);
     free(tmp);
     free(b.pbuf);
     free(b.arena);
@@ -334,7 +354,7 @@ done:
     return 0;
 }
 
-static int run_any(const char *spec, const int64_t *params, int nparams, const or_options *opt, int threads, double max_seconds, or_result *res) {
+static int run_any(const char *spec, const int64_t *params, int nparams, const or_options *opt, const char *edges_path, int threads, double max_seconds, or_result *res) {
     or_spec sp;
     memset(&sp, 0, sizeof sp);
     int rc;
@@ -348,15 +368,19 @@ static int run_any(const char *spec, const int64_t *params, int nparams, const o
     if (rc) return rc;
     or_options o = {0, 0, 1, 1, NULL};
     if (opt) o = *opt;
-    rc = threads > 0 ? or_run_bfs_mt(&sp, &o, threads, max_seconds, res) : run_bfs(&sp, &o, res);
+    if (threads > 0 && edges_path) { or_set_error("the multi-threaded oracle has no edge dump"); rc = -1; }
+    else rc = threads > 0 ? or_run_bfs_mt(&sp, &o, threads, max_seconds, res) : run_bfs(&sp, &o, edges_path, res);
     free(sp.ctx);
     return rc;
 }
 int oracle_run(const char *spec, const int64_t *params, int nparams, const or_options *opt, or_result *res) {
-    return run_any(spec, params, nparams, opt, 0, 0.0, res);
+    return run_any(spec, params, nparams, opt, NULL, 0, 0.0, res);
+}
+int oracle_run_edges(const char *spec, const int64_t *params, int nparams, const or_options *opt, const char *edges_path, or_result *res) {
+    return run_any(spec, params, nparams, opt, edges_path, 0, 0.0, res);
 }
 int oracle_run_mt(const char *spec, const int64_t *params, int nparams, const or_options *opt, int threads, double max_seconds, or_result *res) {
-    return run_any(spec, params, nparams, opt, threads < 1 ? 1 : threads, max_seconds, res);
+    return run_any(spec, params, nparams, opt, NULL, threads < 1 ? 1 : threads, max_seconds, res);
 }
 
 const char *oracle_action_name(const char *spec, int action) {

@@ -86,6 +86,17 @@ typedef struct {
 int oracle_run(const char *spec, const int64_t *params, int nparams,
                const or_options *opt, or_result *res);
 
+/* oracle_run, and the state GRAPH beside the states: edges_path gets one line per successor the search generates and per initial
+ * state, in generation order, duplicates, self loops and successors outside the CONSTRAINT included (multiplicities are kept):
+ *   "<parent> <action> <flags> <inmodel> <invariant> <text>"
+ * parent = index of the expanded state in dump order (line number of opt->dump_path, from 0; -1 for an initial state), flags =
+ * bit 0 Assert failed, bit 1 evaluation error, bit 2 the transition breaks a PROPERTY (bits 8.. its index), inmodel = 1 inside
+ * the CONSTRAINT, invariant = index of the INVARIANT the successor breaks or -1, text = the successor on one line.  A successor
+ * whose evaluation failed has no state: "-1 -1 -".  Use stop_on_violation = 0 for the whole graph.  Single-threaded search only,
+ * models without SYMMETRY only (the states stored there are orbit representatives). */
+int oracle_run_edges(const char *spec, const int64_t *params, int nparams,
+                     const or_options *opt, const char *edges_path, or_result *res);
+
 /* Multi-threaded variant (oracle/bfs_mt.c): same specs, same counting conventions, exact dedup over a
  * hash-sharded seen-set, `threads` worker threads per BFS level.  Counts, depth, per-level counts and the
  * verdict only (no counterexample trace).  max_seconds > 0: stop (verdict budget) after the first level

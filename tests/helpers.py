@@ -47,6 +47,8 @@ def oracle_lib():
         lib = C.CDLL(str(so))
         lib.oracle_run.argtypes = [C.c_char_p, C.POINTER(C.c_int64), C.c_int, C.POINTER(OrOptions), C.POINTER(OrResult)]
         lib.oracle_run.restype = C.c_int
+        lib.oracle_run_edges.argtypes = [C.c_char_p, C.POINTER(C.c_int64), C.c_int, C.POINTER(OrOptions), C.c_char_p, C.POINTER(OrResult)]
+        lib.oracle_run_edges.restype = C.c_int
         lib.oracle_run_mt.argtypes = [C.c_char_p, C.POINTER(C.c_int64), C.c_int, C.POINTER(OrOptions), C.c_int, C.c_double, C.POINTER(OrResult)]
         lib.oracle_run_mt.restype = C.c_int
         lib.oracle_trace_state.argtypes = [C.c_uint32]
@@ -72,6 +74,19 @@ def oracle_run(spec, params, max_levels=0, max_distinct=0, check_deadlock=True, 
                 verdict=VERDICTS[res.verdict], violated_invariant=res.violated_invariant,
                 levels=[res.level_distinct[i] for i in range(res.depth)], trace=trace, seconds=res.seconds,
                 max_stat=list(res.max_stat))
+
+
+def oracle_graph_files(spec, params, dump, edges, check_deadlock=True):
+    """The oracle's complete state graph (no stop at a violation): its stored states into `dump` ("L<level> <text>", line k = state
+    k) and every successor it generates into `edges` (oracle/oracle.h oracle_run_edges); tests/simgraph.py reads the two.  Returns
+    the run's counters."""
+    lib = oracle_lib()
+    p = (C.c_int64 * len(params))(*params)
+    opt = OrOptions(0, 0, int(check_deadlock), 0, str(dump).encode())
+    res = OrResult()
+    if lib.oracle_run_edges(spec.encode(), p, len(params), C.byref(opt), str(edges).encode(), C.byref(res)):
+        raise RuntimeError(lib.oracle_last_error().decode())
+    return dict(distinct=res.distinct, generated=res.generated, depth=res.depth, verdict=VERDICTS[res.verdict])
 
 
 def oracle_run_mt(spec, params, threads, max_levels=0, max_distinct=0, check_deadlock=True, max_seconds=0.0):

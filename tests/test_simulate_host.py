@@ -1,6 +1,9 @@
 """Simulation mode's walk on the host (tla_rust_amd/csrc/sim_walk.h through tests/_simshim, no GPU): every state a walk reaches is a
 state the BFS stores, at a BFS level no deeper than its place in the walk; the walks cover a small model; they find the README model's
-assertion failure along a behaviour of the model."""
+assertion failure along a behaviour of the model.
+
+These are checks of the state SET.  That consecutive states are transitions of the oracle's graph, that a walk ends for the reason the
+graph gives, its counters and the uniformity of its choices are tests/test_simulate_graph.py's (reference: tests/simgraph.py)."""
 import pytest
 
 import helpers

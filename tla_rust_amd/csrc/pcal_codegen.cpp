@@ -773,8 +773,8 @@ bool exists(const std::string &p) { struct stat st; return stat(p.c_str(), &st) 
 
 // Build (or find in the cache) the engine library of program `p` and return its factory: int (*)(const mc_spec_desc *, const mc_config *, mc::EngineBase **).
 // The library is engine.hip compiled as translation unit 9 around the generated header (hipcc --offload-arch=gfx950: seconds to a minute,
-// once per program text: the object is cached under $TLAMC_JIT_CACHE, default /tmp/tlamc_jit_<uid>, by the hash of the generated text and
-// of the engine sources).  nullptr + mc_last_error when the program cannot be translated or the compiler fails: the caller interprets.
+// once per program text: the object is cached under $TLAMC_JIT_CACHE, default /tmp/tlamc_jit_<uid>, by the hash of the generated text,
+// of the engine sources and of this library's directory).  nullptr + mc_last_error when the program cannot be translated or the compiler fails: the caller interprets.
 // pack: rows packed to the cells' inferred ranges (one-GPU engines; a sharded engine's rows travel between ranks and leave through
 // mc_shard_* in the interpreter's layout, so it keeps that layout).
 extern "C" void *mc_jit_factory_opts(const void *program /* pcal::Program * */, int pack) {
@@ -799,6 +799,9 @@ extern "C" void *mc_jit_factory_opts(const void *program /* pcal::Program * */, 
     const char *jd = getenv("TLAMC_JIT_DEFS");
     const std::string shape = jd && *jd ? jd : "-DMC_PAIR_MINW=2 -DMC_PAIR_WAVES=1";
     h = (h ^ fnv(shape)) * 0x100000001b3ull;
+    // (the object is linked against THIS libtlamc.so by path (-L / -rpath below): an entry another copy of the tree built — same sources, same
+    //  times, e.g. unpacked from one archive — would bring that copy's library in beside this one, with an error buffer of its own)
+    h = (h ^ fnv(lib)) * 0x100000001b3ull;
     const char *cd = getenv("TLAMC_JIT_CACHE");
     const std::string cache = cd && *cd ? cd : "/tmp/tlamc_jit_" + std::to_string((unsigned)getuid());
     mkdir(cache.c_str(), 0700);

@@ -6,7 +6,8 @@
 //   * at every step each slot 0 .. nslots-1 of the current state is evaluated with S::eval, as the BFS evaluates it, and every
 //     enabled successor is checked as the BFS checks it (Assert, invariants, evaluation errors, slot-array overflow);
 //   * the next state is the enabled, in-model, non-stuttering successor whose slot has the least H(seed, w, step, slot) (the lower
-//     slot on a tie): one pass, no per-slot masks, uniform over the candidates;
+//     slot on a tie): no per-slot masks, uniform over the candidates; one pass, and one more for every stuttering successor that only
+//     shows when it is built (a row equal to its parent's) and is then passed over;
 //   * every state reached is checked with init_status (the initial state) and the stored-state invariants (all of them);
 //   * the walk ends at `depth` states, at its first violation, at a deadlock, or when no in-model, non-stuttering successor is left.
 // So every state a walk reaches is one the BFS stores (tests/test_simulate_host.py).  Compiles without HIP (spec_*.h do too).
@@ -78,9 +79,9 @@ MC_HD void sim_begin(SimWalk &wk, uint64_t seed, uint64_t walk, uint32_t t, uint
 }
 
 // One event of a walk: a walk with t = 0 builds its initial state into `nxt`; otherwise the current state `cur` is checked, expanded,
-// and its chosen successor written to `nxt` (t + 1), or the walk ends.  `bound(ns)` gives the trip count of the slot loop: ns on the
-// host, the wavefront's maximum on the device (every lane of a wavefront calls it, at the same point: its lanes that take no step
-// pass 0).  flags: MC_F_DEADLOCK.
+// and its chosen successor written to `nxt` (t + 1), or the walk ends.  `bound(ns)` gives the trip count of the slot loop and says
+// whether another pass is due: ns on the host, the wavefront's maximum on the device (every lane of a wavefront calls it, at the same
+// points: its lanes that take no step pass 0).  flags: MC_F_DEADLOCK.
 template <class S, class Bound>
 MC_HD void sim_step(const typename S::Params &prm, SimWalk &wk, uint32_t depth, unsigned deadlock, CWordRef cur, WordRef nxt, Bound &&bound) {
     wk.slot = -1;
@@ -114,48 +115,67 @@ MC_HD void sim_step(const typename S::Params &prm, SimWalk &wk, uint32_t depth, 
             ns = S::nslots(prm, loc);
         }
     }
-    const int wns = bound(ns);
     const uint64_t sh = sim_step_hash(wk.hash, wk.t);
-    uint64_t best = ~0ull;
-    int pick = -1;
+    const int W = S::words(prm);
     unsigned gen = 0, stutter = 0, overflow = 0;
     unsigned long long viol = ~0ull;
-    for (int slot = 0; slot < wns; ++slot) {
-        if (slot < ns) {
-            uint64_t f = 0;
-            const unsigned st = S::eval(prm, loc, cur, slot, f);
-            if (st & ST_ENABLED) {
-                ++gen;
-                if (st & ST_OVERFLOW) overflow = 1;
-                else if (st & ST_ASSERT) viol = viol < sim_key(wk.walk, slot, SIM_VK_ASSERT, 0) ? viol : sim_key(wk.walk, slot, SIM_VK_ASSERT, 0);
-                else if (st & ST_SPECERR) viol = viol < sim_key(wk.walk, slot, SIM_VK_SPECERR, 0) ? viol : sim_key(wk.walk, slot, SIM_VK_SPECERR, 0);
-                else {
-                    if (st & ST_INVARIANT) {
-                        const unsigned long long k = sim_key(wk.walk, slot, SIM_VK_INVARIANT, st >> 8);
-                        viol = viol < k ? viol : k;
-                    }
-                    if (st & ST_SELFLOOP) stutter = 1;
-                    else if (!(st & ST_OUT_OF_MODEL)) {
-                        const uint64_t h = sim_slot_hash(sh, slot);
-                        if (h < best || pick < 0) { best = h; pick = slot; }
+    // A pass evaluates every slot and picks the candidate with the least (hash, slot) above `floor`.  A lowering marks the stuttering
+    // successors it knows of (ST_SELFLOOP); one it does not mark (the terminating disjunct of a PlusCal translation, a label whose body
+    // changes nothing) shows when it is built: the row equals its parent.  It is then passed over and the next candidate in hash order
+    // taken by one more pass, so the choice stays uniform over the non-stuttering candidates.  Every lane of a wavefront makes the
+    // same number of passes (bound() is a wavefront operation on the device).
+    uint64_t floor_h = 0;
+    int floor_slot = -1;
+    bool first = true, again = expand;
+    while (bound(again ? 1 : 0)) {
+        const int wns = bound(again ? ns : 0);
+        uint64_t best = ~0ull;
+        int pick = -1;
+        for (int slot = 0; slot < wns; ++slot) {
+            if (again && slot < ns) {
+                uint64_t f = 0;
+                const unsigned st = S::eval(prm, loc, cur, slot, f);
+                if (st & ST_ENABLED) {
+                    if (first) ++gen;
+                    if (st & ST_OVERFLOW) overflow = 1;
+                    else if (st & ST_ASSERT) viol = viol < sim_key(wk.walk, slot, SIM_VK_ASSERT, 0) ? viol : sim_key(wk.walk, slot, SIM_VK_ASSERT, 0);
+                    else if (st & ST_SPECERR) viol = viol < sim_key(wk.walk, slot, SIM_VK_SPECERR, 0) ? viol : sim_key(wk.walk, slot, SIM_VK_SPECERR, 0);
+                    else {
+                        if (st & ST_INVARIANT) {
+                            const unsigned long long k = sim_key(wk.walk, slot, SIM_VK_INVARIANT, st >> 8);
+                            viol = viol < k ? viol : k;
+                        }
+                        if (st & ST_SELFLOOP) stutter = 1;
+                        else if (!(st & ST_OUT_OF_MODEL)) {
+                            const uint64_t h = sim_slot_hash(sh, slot);
+                            const bool above = floor_slot < 0 || h > floor_h || (h == floor_h && slot > floor_slot);
+                            if (above && (h < best || pick < 0)) { best = h; pick = slot; }
+                        }
                     }
                 }
             }
         }
+        if (!again) continue;
+        again = false;
+        if (first) {
+            first = false;
+            wk.gen += gen;
+            if (overflow) { wk.end = SIM_END_OVERFLOW; continue; }
+            if (viol != ~0ull) { wk.viol = viol; wk.end = SIM_END_VIOLATION; continue; }
+            if (gen == 0) {
+                if (deadlock) { wk.viol = sim_key(wk.walk, SIM_SLOT_NONE, SIM_VK_DEADLOCK, 0); wk.end = SIM_END_VIOLATION; }
+                else wk.end = SIM_END_DEADLOCK;
+                continue;
+            }
+        }
+        if (pick < 0) { wk.end = stutter ? SIM_END_STUTTER : SIM_END_OUT_OF_MODEL; continue; }
+        S::apply(prm, cur, pick, nxt);
+        bool same = true;
+        for (int w = 0; w < W; ++w) same = same && nxt.get(w) == cur.get(w);
+        if (same) { stutter = 1; floor_h = best; floor_slot = pick; again = true; continue; }
+        wk.slot = pick;
+        wk.t++;
     }
-    if (!expand) return;
-    wk.gen += gen;
-    if (overflow) { wk.end = SIM_END_OVERFLOW; return; }
-    if (viol != ~0ull) { wk.viol = viol; wk.end = SIM_END_VIOLATION; return; }
-    if (gen == 0) {
-        if (deadlock) { wk.viol = sim_key(wk.walk, SIM_SLOT_NONE, SIM_VK_DEADLOCK, 0); wk.end = SIM_END_VIOLATION; }
-        else wk.end = SIM_END_DEADLOCK;
-        return;
-    }
-    if (pick < 0) { wk.end = stutter ? SIM_END_STUTTER : SIM_END_OUT_OF_MODEL; return; }
-    S::apply(prm, cur, pick, nxt);
-    wk.slot = pick;
-    wk.t++;
 }
 
 }  // namespace mc
