@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "spec_registry.h"
+#include "hip_owned.h"        // DevBuf, PinnedBuf, Event, Stream: every HIP resource of the host half is held by one of these
 
 namespace mc {
 
@@ -65,7 +66,7 @@ namespace mc {
 
 // ------------------------------------------------------------------------------------- host side
 struct EngineBase {
-    void *owned_device_blob = nullptr;  // program image of a compiled PlusCal spec (spec_vm.h)
+    DevBuf<int32_t> owned_device_blob;  // program image of a compiled PlusCal spec (spec_vm.h)
     uint64_t program_hash = 0;          // ... and a hash of that image + its entry points: what a checkpoint of it is matched by
     mc_progress_fn progress_fn = nullptr;  // mc_engine_set_progress
     void *progress_user = nullptr;
@@ -79,7 +80,7 @@ struct EngineBase {
         progress_last = now;
         progress_fn(progress_user, levels, generated, distinct, queue);
     }
-    virtual ~EngineBase() { if (owned_device_blob) hipFree(owned_device_blob); }
+    virtual ~EngineBase() = default;
     virtual int run(mc_result *out) = 0;
     virtual int step(uint32_t levels, mc_result *out) = 0;
     virtual int trace(uint8_t *states_out, int32_t *actions_out, size_t *n_inout) = 0;
@@ -127,19 +128,19 @@ static uint64_t round_pow2(uint64_t v) {
 }
 
 struct KTimer {
-    std::vector<hipEvent_t> pool;
+    std::vector<Event> pool;
     struct Pending { int which; size_t e0, e1; uint64_t units; };
     std::vector<Pending> pending;
     size_t used = 0;
     bool enabled = false;
     hipEvent_t get() {
-        if (used == pool.size()) { hipEvent_t e; hipEventCreate(&e); pool.push_back(e); }
-        return pool[used++];
+        if (used == pool.size()) pool.emplace_back(hipEventDefault);
+        return pool[used++].get();
     }
     void resolve(mc_kernel_stat *stats /*[3]*/) {
         for (auto &p : pending) {
             float ms = 0;
-            hipEventElapsedTime(&ms, pool[p.e0], pool[p.e1]);
+            hipEventElapsedTime(&ms, pool[p.e0].get(), pool[p.e1].get());
             stats[p.which].launches++;
             stats[p.which].ms_total += ms;
             stats[p.which].units += p.units;
@@ -147,7 +148,6 @@ struct KTimer {
         pending.clear();
         used = 0;
     }
-    ~KTimer() { for (auto e : pool) hipEventDestroy(e); }
 };
 
 // specs whose stored row is not the row the C ABI hands out (spec_gen.h: generated code packs its cells): S::EXPORT_WORDS, S::export_row
@@ -160,6 +160,61 @@ struct PackedRows : std::false_type {};
 template <class S>
 struct PackedRows<S, decltype((void)S::PACKED_ROWS)> : std::integral_constant<bool, S::PACKED_ROWS> {};
 
+// what a violation key (engine_kernels.h viol_key; the same kinds in a simulation's: sim_walk.h) says
+static_assert((unsigned)SIM_VK_INVARIANT == VK_INVARIANT && (unsigned)SIM_VK_ASSERT == VK_ASSERT && (unsigned)SIM_VK_DEADLOCK == VK_DEADLOCK, "one verdict_of_kind");
+static int32_t verdict_of_kind(unsigned kind) {
+    return kind == VK_INVARIANT ? MC_V_INVARIANT : kind == VK_ASSERT ? MC_V_ASSERT : kind == VK_DEADLOCK ? MC_V_DEADLOCK : MC_V_SPECERR;
+}
+struct Viol {
+    unsigned kind, slot;
+    int32_t verdict, invariant;  // invariant: its index, or -1
+    explicit Viol(unsigned long long key)
+        : kind((unsigned)(key & 7u)), slot((unsigned)(key >> 8 & 0xffffu)), verdict(verdict_of_kind(kind)), invariant(kind == VK_INVARIANT ? (int32_t)(key >> 3 & 31u) : -1) {}
+    bool extra_state() const { return kind == VK_INVARIANT && slot < SLOT_PARENT; }  // the violating successor itself ends the trace
+};
+
+// ------------------------------------------------------------------------------- checkpoint files
+// Two formats, one identity prefix: a fused engine's file (mc_engine_checkpoint) and a rank's file of a sharded run (mc_shard_checkpoint).
+// Both are: header, level table (nlevels words), [the rank's counters], then device sections as they lie in HBM (Engine::ck_sections).
+struct CkIdent {
+    char magic[8];
+    uint32_t spec_id, nparams;
+    int64_t params[16];  // of a compiled program: params[0] = the hash of its image (its parameter is a host pointer)
+    uint32_t words, has_trace;
+};
+struct CkHeader {
+    CkIdent id;
+    uint64_t distinct, generated, cells, lo, hi, nlevels;
+};
+struct ShCkHeader {
+    CkIdent id;
+    uint32_t rank, world;
+    uint64_t table_cap, lo, hi, next, dup, nlevels;
+};
+// the counters a per-rank checkpoint carries, field by field (the file held a raw DevCounters, whose layout —
+// padding, alignment, members — changes with the kernels; "TLAMCSK1" files are refused as "not a per-rank checkpoint file")
+struct ShCkCounters {
+    uint64_t arena_next, viol_key, via_list;
+    uint64_t generated[NSHARD], cells[NSHARD];
+    uint32_t error, pad;
+};
+// the files' layout is fixed (files written by earlier builds restore; tests edit bytes at these offsets)
+static_assert(sizeof(CkIdent) == 152 && offsetof(CkIdent, spec_id) == 8 && offsetof(CkIdent, params) == 16 && offsetof(CkIdent, words) == 144 && offsetof(CkIdent, has_trace) == 148, "checkpoint identity");
+static_assert(sizeof(CkHeader) == 200 && offsetof(CkHeader, distinct) == 152 && offsetof(CkHeader, generated) == 160 && offsetof(CkHeader, cells) == 168 &&
+              offsetof(CkHeader, lo) == 176 && offsetof(CkHeader, hi) == 184 && offsetof(CkHeader, nlevels) == 192, "TLAMCCK1 header");
+static_assert(sizeof(ShCkHeader) == 208 && offsetof(ShCkHeader, rank) == 152 && offsetof(ShCkHeader, world) == 156 && offsetof(ShCkHeader, table_cap) == 160 &&
+              offsetof(ShCkHeader, lo) == 168 && offsetof(ShCkHeader, hi) == 176 && offsetof(ShCkHeader, next) == 184 && offsetof(ShCkHeader, dup) == 192 &&
+              offsetof(ShCkHeader, nlevels) == 200, "TLAMCSK2 header");
+static_assert(NSHARD == 8 && sizeof(ShCkCounters) == 160 && offsetof(ShCkCounters, generated) == 24 && offsetof(ShCkCounters, cells) == 88 && offsetof(ShCkCounters, error) == 152, "TLAMCSK2 counters");
+// what tells the two formats apart: the magic, and the words of the messages (`who` + ": " + ...)
+struct CkFormat { const char *magic, *writer, *reader, *not_ours, *other_program; };
+static constexpr CkFormat CK_FUSED{"TLAMCCK1", "checkpoint", "restore", "not a checkpoint file",
+                                   "the checkpoint was written by another compiled program (algorithm, constants, invariants or constraints differ)"};
+static constexpr CkFormat CK_RANK{"TLAMCSK2", "mc_shard_checkpoint", "mc_shard_restore", "not a per-rank checkpoint file (of this library version)",
+                                  "the checkpoint was written by another compiled program"};
+struct CkPart { void *p; size_t bytes; };  // a run of bytes of a checkpoint file, in host or in device memory
+struct FileCloser { FILE *f; ~FileCloser() { if (f) fclose(f); } };
+
 template <class S>
 struct Engine : EngineBase {
     using Params = typename S::Params;
@@ -168,25 +223,102 @@ struct Engine : EngineBase {
     Params prm;
     mc_spec_desc desc;
     mc_config cfg;
-    hipStream_t stream = nullptr, stream2 = nullptr;  // expand+insert on `stream`, materialise on `stream2`
+    // ---- HIP resources: streams first (members go in reverse order: the streams outlive every event and buffer)
+    Stream stream, stream2;  // expand+insert on `stream`, materialise on `stream2`
     // The chunks of ONE level are independent of each other (they read the frontier, probe / insert with atomics, take arena indices
     // with atomics): the odd ones go to a stream of their own, so that the first workgroups of chunk c+1 fill the CUs the last
     // workgroups of chunk c leave idle (a launch of 2^23 parents is 32 rounds of the 2048 resident workgroups: the last one is half
     // empty) instead of waiting for the stream order.  $TLAMC_EXPAND_STREAMS = 2 switches it on (A/B; off by default until measured).
-    hipStream_t stream_b = nullptr;
-    hipEvent_t ev_level = nullptr;
-    hipEvent_t ev_e[2] = {nullptr, nullptr}, ev_m[2] = {nullptr, nullptr};
-    uint64_t *d_arena = nullptr, *d_table = nullptr, *d_cand = nullptr;
-    uint32_t *d_newlist = nullptr;
-    uint64_t *d_newfp = nullptr;  // fingerprints of the new-list entries (specs with apply_known_fp)
-    uint16_t *d_nsl = nullptr, *d_pslot = nullptr;
-    uint64_t *d_inittmp = nullptr;
-    uint32_t *d_parent = nullptr;
-    uint8_t *d_prank = nullptr;  // sharded runs with MC_F_TRACE: rank a state's parent lives on (0xff = this rank)
-    DevCounters *d_ctr = nullptr, *h_ctr = nullptr;
-    LevelCtl *d_lc = nullptr, *h_lc = nullptr;
+    Stream stream_b;
+    Event ev_level, ev_e[2], ev_m[2];
+    DevBuf<uint64_t> d_arena, d_table, d_cand, d_inittmp;
+    DevBuf<uint32_t> d_newlist, d_parent;
+    DevBuf<uint64_t> d_newfp;  // fingerprints of the new-list entries (specs with apply_known_fp)
+    DevBuf<uint16_t> d_nsl, d_pslot;
+    DevBuf<uint8_t> d_prank;  // sharded runs with MC_F_TRACE: rank a state's parent lives on (0xff = this rank)
+    DevBuf<DevCounters> d_ctr;
+    PinnedBuf<DevCounters> h_ctr;
+    DevBuf<LevelCtl> d_lc;
+    PinnedBuf<LevelCtl> h_lc;
     uint64_t table_cap = 0, arena_cap = 0, chunk = 0, row_stride = 0, seg_cap = 0;
-    bool seen_sparse = false;
+    bool seen_sparse = false, use_matrix = false;
+    bool no_slices = getenv("TLAMC_NOSLICE") != nullptr;
+    // fused runs of a by-family spec: the expand wavefronts write their own survivors (MC_F_NOINWAVE = A/B: everything through the
+    // new-list and k_materialise, as in rounds 1-3)
+    double inwave_growth_limit = getenv("TLAMC_INWAVE_GROWTH") ? atof(getenv("TLAMC_INWAVE_GROWTH")) : 10.0;  // (A/B knob.  Round 4, profiles/r04l:
+    // t3 — levels grow by at most 2.2 x — was best with every level in-wave, the 5-server model — 2.4 x and more on all 18 levels — with
+    // none, 230.6 against 239.0 ms: the limit was 2.3.  Round 5: with the writer's scratch traffic gone the in-wave tail wins there too,
+    // 191.9 / 192.1 against 205.0 / 203.0 ms at 2.3 (profiles/r05i_raft5_inwave_growth.jsonl); 10 = in effect every level)
+    KTimer timer;
+    mc_kernel_stat kstat[3];
+    // ---- the fused run (run / step) and what it left behind: counters, level table, counterexample
+    struct Fused {
+        bool have_run = false, have_viol = false;
+        unsigned long long last_viol = ~0ull;
+        std::vector<uint64_t> level_start;
+        uint64_t last_distinct = 0, last_generated = 0, cells = 0, inwave = 0;  // cells, inwave: for mc_kernel_stats
+        uint64_t stop_frontier = 0, lo = 0, hi = 0;  // run() stops before a level of >= stop_frontier states (0 = never); the frontier it stopped with
+        bool mat_inwave_level = false;     // the level being enqueued writes in-wave: k_materialise sees the overflow only
+        uint64_t mat_list_hint = 0;        // states per chunk the level before sent through the new-list
+    } fr;
+    // ---- hand-over to the next run(): from restore() (a checkpoint file) or step() (in place: the stopped run's seen-set is still valid)
+    struct HandOver {
+        bool pending = false, in_place = false;
+        uint64_t distinct = 0, generated = 0, cells = 0, lo = 0;
+        std::vector<uint64_t> level_start;
+    } ck;
+    // ---- the sharded step API (mc_shard_*)
+    // Two expand slots: the route-mode expand of chunk r+1 (on `stream`) overlaps the exchange, probe and keep /
+    // materialise of chunk r (kernels on `stream2`, collectives on the caller's stream).
+    struct ShSlot {
+        DevBuf<uint64_t> rt_fp;
+        DevBuf<uint32_t> rt_src, pend_src;  // pend_src.n = the slot's pending-list capacity (shard_alloc)
+        DevBuf<PaddedCounter> rt_cur;  // [nranks*NSHARD] route cursors
+        uint64_t rt_subcap = 0, pend_total = 0, chunk_base = 0, count = 0, ncols = 0;
+        BlockPlan plan;          // of the slot's last shard_materialise (for shard_materialise_parents)
+        uint64_t moved = 0;
+        OwnerOffsets pend_off;
+        bool launched = false, keep_pending = false;
+    };
+    struct Shard {
+        uint64_t lo = 0, hi = 0, next = 0;  // local frontier [lo, hi), arena fill level
+        uint64_t dup = 0;                   // states of the replicated prefix that other ranks count (shard_begin_replicated)
+        ShSlot sl[2];
+        DevBuf<uint32_t> d_new_src, d_incl;
+        DevBuf<unsigned long long> d_ends;
+        PinnedBuf<unsigned long long> h_ends;
+        PinnedBuf<PaddedCounter> h_cur;  // pinned copy of one slot's route cursors
+        DevBuf<char> d_scan_tmp;
+        // Side stream of the sharded path.  By default the engine's own second stream, and every step call returns
+        // with its work finished.  A caller that runs its collectives on a HIP stream hands that stream over with
+        // shard_set_stream: compaction / probe / keep / materialise / ingest are then enqueued on it WITHOUT host
+        // synchronisation (stream order ties them to the caller's all-to-alls), and only the calls that must return
+        // counts to the host wait.
+        hipStream_t ext_stream = nullptr;
+        bool ext_side = false;
+        Event ev_slot[2], ev_keep[2], ev_ans;
+        // Three kinds of kernels append states at arena_next (the chunk's locally owned new states, keep, ingest) and they run on
+        // different streams: one event chains them, each appender waits for the previous one and records when it is enqueued.
+        Event ev_append;
+        // fixed-capacity rounds (nothing of a round waits for the host; sizes travel in band; errors surface at shard_end_level)
+        Event ev_exp[2];
+        // the slot's new-list segment and its counters (parity = slot) are read by the local materialise + commit on the second
+        // stream: the NEXT expand into the same slot waits for them (a host that never blocks enqueues expands back to back)
+        Event ev_mat[2];
+        std::vector<uint64_t> levels;  // the whole job's level table (shard_note_levels): what a per-rank checkpoint carries
+        bool ck_ok = false, resume = false;
+        std::unique_ptr<mc_result> prefix_res{new mc_result()};  // of the replicated prefix: large (level table), so not on the stack
+    } sh;
+    // ---- simulation (mc_engine_simulate): the walk buffers, allocated on first use, and the counterexample of the last simulation
+    struct Sim {
+        DevBuf<uint64_t> buf[2];
+        DevBuf<uint32_t> wst;
+        DevBuf<SimCounters> ctr;
+        std::vector<uint64_t> trace_rows;  // rows in S's layout
+        std::vector<int32_t> trace_acts;   // ... and their action ids
+        size_t trace_n = 0;
+    } sim;
+
     // slot slices of a generic-kernel launch (k_expand_insert): as many as it takes to give the device a few thousand wavefronts,
     // for specs whose slots all go through the loop (no unrolled prefix) and that have enough of them; TLAMC_NOSLICE=1 = A/B
     unsigned slices_for(uint64_t ncols, bool blind) const {
@@ -199,35 +331,29 @@ struct Engine : EngineBase {
         if (sg > max_slots / 4) sg = max_slots / 4;
         return sg < 1 ? 1u : (unsigned)sg;
     }
-    bool no_slices = getenv("TLAMC_NOSLICE") != nullptr;
     uint64_t seen_arg() const { return seen_sparse ? ((table_cap / MC_SPARSE_SLOTS) | SEEN_SPARSE) : table_cap / 8; }
-    KTimer timer;
-    mc_kernel_stat kstat[3];
-    // counterexample of the last run
-    bool have_viol = false;
-    unsigned long long last_viol = ~0ull;
-    std::vector<uint64_t> level_start;
+    unsigned nranks() const { return cfg.shard_count > 1 ? cfg.shard_count : 1; }
 
     int alloc() {
         W = S::words(prm);
         max_slots = (unsigned)S::max_slots(prm);
         use_matrix = (cfg.flags & MC_F_MATRIX) != 0;
         HIP_TRY(hipSetDevice(cfg.device));
-        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        HIP_TRY(stream.create());
         {   // A/B knob (measured in DESIGN.md section 4): TLAMC_PRIO=1 gives the materialise stream the highest priority, =2 the lowest
             const char *pe = getenv("TLAMC_PRIO");
             int lo_p = 0, hi_p = 0;
             hipDeviceGetStreamPriorityRange(&lo_p, &hi_p);  // lo_p = least, hi_p = greatest priority (numerically smaller)
-            if (pe && *pe == '1') HIP_TRY(hipStreamCreateWithPriority(&stream2, hipStreamNonBlocking, hi_p));
-            else if (pe && *pe == '2') HIP_TRY(hipStreamCreateWithPriority(&stream2, hipStreamNonBlocking, lo_p));
-            else HIP_TRY(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
+            if (pe && *pe == '1') HIP_TRY(stream2.create(hi_p));
+            else if (pe && *pe == '2') HIP_TRY(stream2.create(lo_p));
+            else HIP_TRY(stream2.create());
         }
-        for (int i = 0; i < 2; i++) { HIP_TRY(hipEventCreateWithFlags(&ev_e[i], hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&ev_m[i], hipEventDisableTiming)); }
+        for (int i = 0; i < 2; i++) { HIP_TRY(ev_e[i].create()); HIP_TRY(ev_m[i].create()); }
         {
             const char *es = getenv("TLAMC_EXPAND_STREAMS");
             if (es && *es == '2') {
-                HIP_TRY(hipStreamCreateWithFlags(&stream_b, hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&ev_level, hipEventDisableTiming));
+                HIP_TRY(stream_b.create());
+                HIP_TRY(ev_level.create());
             }
         }
         table_cap = cfg.table_capacity ? cfg.table_capacity : (1ull << 24);
@@ -245,65 +371,32 @@ struct Engine : EngineBase {
         if (chunk > (1ull << 24) - 256) chunk = (1ull << 24) - 256;  // a column index must fit 24 bits (new-list entries: (slot << 24) | column)
         if (max_slots > 255) { set_error("spec has more than 255 action slots per state"); return MC_EBADCFG; }
         row_stride = chunk + 256;
-        HIP_TRY(hipMalloc(&d_arena, arena_cap * W * sizeof(uint64_t)));
-        HIP_TRY(hipMalloc(&d_table, table_cap * sizeof(uint64_t)));
-        HIP_TRY(hipMalloc(&d_cand, (size_t)(use_matrix ? max_slots : 1) * row_stride * sizeof(uint64_t)));
+        HIP_TRY(d_arena.alloc(arena_cap * W));
+        HIP_TRY(d_table.alloc(table_cap));
+        HIP_TRY(d_cand.alloc((size_t)(use_matrix ? max_slots : 1) * row_stride));
         seg_cap = (row_stride / NSHARD + 256) * max_slots;
         seg_cap += seg_cap / 64 + 65;   // (round 6: an in-wave writer parks its overflow here as chunks of 64 entries + a link: 65 / 64 of the worst case)
-        HIP_TRY(hipMalloc(&d_newlist, (size_t)2 * NSHARD * seg_cap * sizeof(uint32_t)));
-        if (HasKnownFp<S>::value && !use_matrix) HIP_TRY(hipMalloc(&d_newfp, (size_t)2 * NSHARD * seg_cap * sizeof(uint64_t)));
+        HIP_TRY(d_newlist.alloc((size_t)2 * NSHARD * seg_cap));
+        if (HasKnownFp<S>::value && !use_matrix) HIP_TRY(d_newfp.alloc((size_t)2 * NSHARD * seg_cap));
         {
             const uint64_t ni = S::num_init(prm);
-            HIP_TRY(hipMalloc(&d_inittmp, (size_t)(ni < chunk ? ni : chunk) * W * sizeof(uint64_t)));
+            HIP_TRY(d_inittmp.alloc((size_t)(ni < chunk ? ni : chunk) * W));
         }
-        HIP_TRY(hipMalloc(&d_nsl, row_stride * sizeof(uint16_t)));
+        HIP_TRY(d_nsl.alloc(row_stride));
         if (cfg.flags & MC_F_TRACE) {
-            HIP_TRY(hipMalloc(&d_parent, arena_cap * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc(&d_pslot, arena_cap * sizeof(uint16_t)));
+            HIP_TRY(d_parent.alloc(arena_cap));
+            HIP_TRY(d_pslot.alloc(arena_cap));
             if (cfg.shard_count > 1) {
-                HIP_TRY(hipMalloc(&d_prank, arena_cap));
+                HIP_TRY(d_prank.alloc(arena_cap));
                 HIP_TRY(hipMemset(d_prank, 0xff, arena_cap));
             }
         }
-        HIP_TRY(hipMalloc(&d_ctr, sizeof(DevCounters)));
-        HIP_TRY(hipHostMalloc(&h_ctr, sizeof(DevCounters)));
-        HIP_TRY(hipMalloc(&d_lc, sizeof(LevelCtl)));
-        HIP_TRY(hipHostMalloc(&h_lc, sizeof(LevelCtl)));
+        HIP_TRY(d_ctr.alloc(1));
+        HIP_TRY(h_ctr.alloc(1));
+        HIP_TRY(d_lc.alloc(1));
+        HIP_TRY(h_lc.alloc(1));
         timer.enabled = (cfg.flags & MC_F_TIMING) != 0;
         return MC_OK;
-    }
-    ~Engine() override {
-        if (d_arena) hipFree(d_arena);
-        if (d_table) hipFree(d_table);
-        if (d_cand) hipFree(d_cand);
-        if (d_newlist) hipFree(d_newlist);
-        if (d_newfp) hipFree(d_newfp);
-        if (d_nsl) hipFree(d_nsl);
-        if (d_inittmp) hipFree(d_inittmp);
-        for (auto &q : sl) {
-            if (q.rt_fp) { hipFree(q.rt_fp); hipFree(q.rt_src); hipFree(q.pend_src); }
-            if (q.rt_cur) hipFree(q.rt_cur);
-        }
-        if (d_new_src) { hipFree(d_new_src); hipFree(d_incl); }
-        if (d_ends) { hipFree(d_ends); hipHostFree(h_ends); hipHostFree(h_cur); }
-        for (auto &ev : ev_slot) if (ev) hipEventDestroy(ev);
-        for (auto &ev : ev_keep) if (ev) hipEventDestroy(ev);
-        if (ev_ans) hipEventDestroy(ev_ans);
-        if (ev_append) hipEventDestroy(ev_append);
-        if (d_scan_tmp) hipFree(d_scan_tmp);
-        if (d_parent) hipFree(d_parent);
-        if (d_pslot) hipFree(d_pslot);
-        if (d_prank) hipFree(d_prank);
-        if (d_ctr) hipFree(d_ctr);
-        if (h_ctr) hipHostFree(h_ctr);
-        sim_free();
-        if (d_lc) hipFree(d_lc);
-        if (h_lc) hipHostFree(h_lc);
-        for (int i = 0; i < 2; i++) { if (ev_e[i]) hipEventDestroy(ev_e[i]); if (ev_m[i]) hipEventDestroy(ev_m[i]); }
-        if (stream2) hipStreamDestroy(stream2);
-        if (stream_b) hipStreamDestroy(stream_b);
-        if (ev_level) hipEventDestroy(ev_level);
-        if (stream) hipStreamDestroy(stream);
     }
 
     template <class F>
@@ -334,19 +427,10 @@ struct Engine : EngineBase {
         return MC_OK;
     }
 
-    bool use_matrix = false;
-    // fused runs of a by-family spec: the expand wavefronts write their own survivors (MC_F_NOINWAVE = A/B: everything through the
-    // new-list and k_materialise, as in rounds 1-3)
-    double inwave_growth_limit = getenv("TLAMC_INWAVE_GROWTH") ? atof(getenv("TLAMC_INWAVE_GROWTH")) : 10.0;  // (A/B knob.  Round 4, profiles/r04l:
-    // t3 — levels grow by at most 2.2 x — was best with every level in-wave, the 5-server model — 2.4 x and more on all 18 levels — with
-    // none, 230.6 against 239.0 ms: the limit was 2.3.  Round 5: with the writer's scratch traffic gone the in-wave tail wins there too,
-    // 191.9 / 192.1 against 205.0 / 203.0 ms at 2.3 (profiles/r05i_raft5_inwave_growth.jsonl); 10 = in effect every level)
     bool inwave_ok() const { return (UsesFamilies<S>::value || UsesPairs<S>::value) && !use_matrix && !(cfg.flags & (MC_F_NOFAMILY | MC_F_NOINWAVE)); }
     // by-pairs specs (engine_pairs.h) write EVERY new state in the expand kernel: nothing ever reaches the new-list, so a fused run launches
     // neither k_materialise nor k_commit for them
     bool pairs_only() const { return UsesPairs<S>::value && inwave_ok(); }
-    bool mat_inwave_level = false;     // the level being enqueued writes in-wave: k_materialise sees the overflow only
-    uint64_t mat_list_hint = 0;        // states per chunk the level before sent through the new-list
     void set_inwave(RouteArgs &rt) const {
         if (!inwave_ok()) return;
         rt.arena_w = d_arena;
@@ -354,30 +438,35 @@ struct Engine : EngineBase {
         rt.parent = d_parent;
         rt.pslot = d_pslot;
     }
+    // k_materialise's grid (x NSHARD segments) for the new-list of a chunk of ncols parents (a grid-stride kernel: any grid is correct)
+    static unsigned mat_grid(uint64_t ncols) {
+        const unsigned bx = (unsigned)((ncols + 255) / 256);
+        const unsigned gm = bx < 8 * 256 ? (bx + 7) / 8 : 256;
+        return gm ? gm : 1u;
+    }
     // materialise + commit of the chunk whose survivors are in new-list `parity`, on the second stream: it overlaps
     // the expansion of the next chunk (memory-bound next to latency-bound)
     void finish_materialise(uint64_t chunk_base, uint64_t ncols, unsigned parity, hipStream_t expanded_on = nullptr) {
         if (pairs_only()) return;
-        const unsigned bx = (unsigned)((ncols + 255) / 256);
-        unsigned gm = bx < 8 * 256 ? (bx + 7) / 8 : 256;
+        unsigned gm = mat_grid(ncols);
         // In-wave levels hand k_materialise only the OVERFLOW of the expand wavefronts' survivor lists (0.15 % of the contract workload's
         // states, 11 % of the five-server model's): the grid follows what the level before sent through the list (x 4, per chunk) instead
         // of the chunk's size — a grid-stride kernel: any grid is correct — so that a launch with next to nothing to do is 8 workgroups
         // that start and end at once, not 2048 that queue behind the next chunk's expand (round 5: 70 launches per step showed 62 ms of
         // HIP-event time for 0.8 M states: VERDICT weak 9)
-        if (mat_inwave_level) {
-            const uint64_t want = (mat_list_hint * 4 + 255) / 256;   // workgroups of 256 states, all eight segments together
+        if (fr.mat_inwave_level) {
+            const uint64_t want = (fr.mat_list_hint * 4 + 255) / 256;   // workgroups of 256 states, all eight segments together
             const unsigned per_seg = (unsigned)((want + NSHARD - 1) / NSHARD);
             if (per_seg < gm) gm = per_seg ? per_seg : 1u;
         }
-        hipEventRecord(ev_e[parity], expanded_on ? expanded_on : stream);
-        hipStreamWaitEvent(stream2, ev_e[parity], 0);
+        hipEventRecord(ev_e[parity].get(), expanded_on ? expanded_on : stream.s);
+        hipStreamWaitEvent(stream2, ev_e[parity].get(), 0);
         timed(2, 0, [&] {
             hipLaunchKernelGGL(k_materialise<S>, dim3(gm, NSHARD), dim3(256), 0, stream2, prm, d_arena, chunk_base, d_newlist,
                                seg_cap, arena_cap, d_parent, d_pslot, d_ctr, parity, (const LevelCtl *)nullptr, (const uint64_t *)d_newfp);
         }, stream2);
         hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, stream2, d_ctr, parity);
-        hipEventRecord(ev_m[parity], stream2);
+        hipEventRecord(ev_m[parity].get(), stream2);
         // measurement knob: TLAMC_SERIAL=1 lets no expand kernel run beside a materialise kernel (each kernel's stand-alone time)
         static const bool serial = getenv("TLAMC_SERIAL") != nullptr;
         if (serial) hipStreamSynchronize(stream2);
@@ -397,7 +486,7 @@ struct Engine : EngineBase {
         const unsigned lflags = cfg.flags | ((cfg.flags & MC_F_PARK) ? MC_FI_PARK : 0u);   // (the PARK instantiation, see run())
         timed(0, 0, [&] {
             launch_expand<S, false>(!(cfg.flags & MC_F_NOFAMILY), lflags, ncols, stream, sg, prm, (const uint64_t *)d_arena,
-                                    (uint64_t)0, (uint64_t)0, ncols, d_table, seen_arg(), d_newlist, seg_cap, d_ctr, cfg.flags, rt, 0u);
+                                    (uint64_t)0, (uint64_t)0, ncols, d_table.p, seen_arg(), d_newlist.p, seg_cap, d_ctr.p, cfg.flags, rt, 0u);
             if (dl) hipLaunchKernelGGL(k_deadlock_slices, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, stream, (const uint16_t *)d_nsl,
                                        (uint64_t)0, (uint64_t)0, ncols, (const LevelCtl *)d_lc, d_ctr);
         });
@@ -428,34 +517,69 @@ struct Engine : EngineBase {
         hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, stream, d_ctr, 0u);
     }
 
-    int run(mc_result *out) override {
-        memset(out, 0, sizeof *out);
-        out->violated_invariant = -1;
-        memset(kstat, 0, sizeof kstat);
-        have_viol = false;
-        sim_trace_n = 0;
-        stop_requested = false;
-        have_run = false;  // set again on the success path only: a run that fails half-way (MC_EARENA, MC_ETABLEFULL, MC_EOVERFLOW)
-                           // leaves fingerprints of an unfinished level in the seen-set — the next step / checkpoint must not continue it
-        level_start.clear();
-        HIP_TRY(hipSetDevice(cfg.device));
-        const bool in_place = ck_pending && ck_in_place;  // mc_engine_step: the seen-set of the stopped run is still valid
-        ck_in_place = false;
+    // The start of every search, on `stream`: an empty seen-set, fresh counters, then level 1 = the initial states that `rank` of `count`
+    // owns.  resuming (run() after restore() / inside step()): the counters are the handed-over run's and its states are in the arena
+    // already; the seen-set is rebuilt from them unless it is still valid (in_place).  t0 (fused runs): the run's clock starts when the
+    // clearing is done, before the first kernel is enqueued.
+    int seed_init(unsigned rank, unsigned count, bool resuming, bool in_place, std::chrono::steady_clock::time_point *t0) {
         if (!in_place) HIP_TRY(hipMemsetAsync(d_table, 0, table_cap * sizeof(uint64_t), stream));
         HIP_TRY(hipMemsetAsync(d_ctr, 0, sizeof(DevCounters), stream));
         DevCounters init_c;
         memset(&init_c, 0, sizeof init_c);
         init_c.viol_key = ~0ull;
-        const bool resuming = ck_pending;
-        ck_pending = false;
-        if (resuming) {  // counters of the checkpointed run; its states are already in the arena (restore())
-            init_c.arena_next = ck_distinct;
-            init_c.generated[0].v = ck_generated;
-            init_c.cells[0].v = ck_cells;
+        if (resuming) {
+            init_c.arena_next = ck.distinct;
+            init_c.generated[0].v = ck.generated;
+            init_c.cells[0].v = ck.cells;
         }
         HIP_TRY(hipMemcpyAsync(d_ctr, &init_c, sizeof init_c, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        const auto t0 = std::chrono::steady_clock::now();
+        if (t0) {
+            HIP_TRY(hipStreamSynchronize(stream));
+            *t0 = std::chrono::steady_clock::now();
+        }
+        if (resuming && ck.distinct && !in_place)
+            hipLaunchKernelGGL(k_reseed_table<S>, dim3((unsigned)((ck.distinct + 255) / 256)), dim3(256), 0, stream, prm,
+                               (const uint64_t *)d_arena, ck.distinct, d_table, seen_arg(), d_ctr);
+        const uint64_t ninit = resuming ? 0 : S::num_init(prm);
+        for (uint64_t first = 0; first < ninit; first += chunk) {
+            const uint64_t n = ninit - first < chunk ? ninit - first : chunk;
+            const uint64_t ncols = (n + 63) & ~63ull;
+            hipLaunchKernelGGL(k_init_cand<S>, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, stream, prm, first, n,
+                               d_inittmp, d_cand, ncols, d_nsl, d_ctr, rank, count);
+            finish_chunk<true>(first, ncols, 1);
+        }
+        return MC_OK;
+    }
+    // The level [lo, hi) has been expanded and the arena now ends at new_hi: the next frontier is [hi, new_hi), a level of its own
+    // unless it is empty.
+    int close_level(uint64_t &lo, uint64_t &hi, uint64_t new_hi, uint32_t &level, mc_result *out) {
+        lo = hi;
+        hi = new_hi;
+        if (hi > lo) {
+            fr.level_start.push_back(lo);
+            if (level < MC_MAX_LEVELS) out->level_distinct[level] = hi - lo;
+            level++;
+        }
+        if (level >= MC_MAX_LEVELS) { set_error("too many BFS levels"); return MC_EBADCFG; }
+        return MC_OK;
+    }
+
+    int run(mc_result *out) override {
+        memset(out, 0, sizeof *out);
+        out->violated_invariant = -1;
+        memset(kstat, 0, sizeof kstat);
+        fr.have_viol = false;
+        sim.trace_n = 0;
+        stop_requested = false;
+        fr.have_run = false;  // set again on the success path only: a run that fails half-way (MC_EARENA, MC_ETABLEFULL, MC_EOVERFLOW)
+                           // leaves fingerprints of an unfinished level in the seen-set — the next step / checkpoint must not continue it
+        fr.level_start.clear();
+        HIP_TRY(hipSetDevice(cfg.device));
+        const bool resuming = ck.pending, in_place = ck.pending && ck.in_place;  // in place (mc_engine_step): the seen-set of the stopped run is still valid
+        ck.pending = ck.in_place = false;
+        std::chrono::steady_clock::time_point t0;
+        int rc = seed_init(0u, 1u, resuming, in_place, &t0);  // level 1: Init; run() is never owner-filtered
+        if (rc) return rc;
         progress_last = t0;
         auto progress = [&](uint32_t lv, uint64_t lo_, uint64_t hi_) {
             if (!progress_fn) return;
@@ -463,19 +587,6 @@ struct Engine : EngineBase {
             for (int t = 0; t < NSHARD; t++) g += h_ctr->generated[t].v;
             report_progress(lv, g, hi_, hi_ - lo_);
         };
-
-        // level 1: Init
-        const uint64_t ninit = resuming ? 0 : S::num_init(prm);
-        if (resuming && ck_distinct && !in_place)
-            hipLaunchKernelGGL(k_reseed_table<S>, dim3((unsigned)((ck_distinct + 255) / 256)), dim3(256), 0, stream, prm,
-                               (const uint64_t *)d_arena, ck_distinct, d_table, seen_arg(), d_ctr);
-        for (uint64_t first = 0; first < ninit; first += chunk) {
-            const uint64_t count = ninit - first < chunk ? ninit - first : chunk;
-            const uint64_t ncols = (count + 63) & ~63ull;
-            hipLaunchKernelGGL(k_init_cand<S>, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, stream, prm, first, count,
-                               d_inittmp, d_cand, ncols, d_nsl, d_ctr, 0u, 1u);  // run() is never owner-filtered
-            finish_chunk<true>(first, ncols, 1);
-        }
         // with in-wave writes every writer takes its arena indices from arena_next itself from here on (DevCounters::atomic_alloc).
         // Init above, the candidate-matrix form and every spec whose states all go through k_materialise keep appending in stream
         // order: one returning atomicAdd per wavefront of k_materialise on ONE word is pure cost there (atomic_add N = 28: 145
@@ -483,19 +594,18 @@ struct Engine : EngineBase {
         if (inwave_ok()) hipLaunchKernelGGL(k_set_alloc_mode, dim3(1), dim3(1), 0, stream, d_ctr, 1u);
         bool alloc_atomic = inwave_ok();
         uint64_t prev_frontier = ~0ull >> 12;  // (the first level is never "fast growing")
-        int rc = read_counters();
-        if (rc) return rc;
+        if ((rc = read_counters())) return rc;
         if ((rc = check_dev_error())) return rc;
         uint64_t lo = 0, hi = h_ctr->arena_next;
         uint32_t level = 1;
         out->level_distinct[0] = hi;
-        level_start.push_back(0);
+        fr.level_start.push_back(0);
         if (resuming) {  // continue with the frontier [lo, hi) = the last, unexpanded level of the checkpointed run
-            level_start = ck_level_start;
-            level = (uint32_t)level_start.size();
-            lo = ck_lo;
+            fr.level_start = ck.level_start;
+            level = (uint32_t)fr.level_start.size();
+            lo = ck.lo;
             for (uint32_t k = 0; k < level && k < MC_MAX_LEVELS; k++)
-                out->level_distinct[k] = (k + 1 < level ? level_start[k + 1] : hi) - level_start[k];
+                out->level_distinct[k] = (k + 1 < level ? fr.level_start[k + 1] : hi) - fr.level_start[k];
         }
         int budget = 0;
         uint64_t via_seen = 0;
@@ -503,8 +613,8 @@ struct Engine : EngineBase {
         // write it themselves (k_expand_family<.., PARK>).  Measured (profiles/r06zb, zf, zg, zh): every state of the five-server model
         // is written in-wave then (924 M instead of 821 M; k_materialise idle) and its step takes as long as before, or longer — not the default
         const bool park_levels = (cfg.flags & MC_F_PARK) != 0;
-        mat_list_hint = ~0ull >> 8;   // (unknown before the first large level: the full grid)
-        mat_inwave_level = false;
+        fr.mat_list_hint = ~0ull >> 8;   // (unknown before the first large level: the full grid)
+        fr.mat_inwave_level = false;
         // (the largest frontier a batched level takes: 2^20 states since round 6 — 2^16 before; profiles/r06zm_blind_ab.jsonl: the contract
         //  workload 128.7 / 127.5 -> 126.1 / 126.0 ms, the generated pagecache model 7.65 / 7.63 -> 7.42 / 7.44 — $TLAMC_BLIND_LOG2 = A/B knob.
         //  Specs whose blind launches are sliced — the interpreter, the Paxos family: 32 slices of the level's CAPACITY — keep 2^16)
@@ -513,7 +623,7 @@ struct Engine : EngineBase {
         if (chunk < blind_max) blind_max = chunk;
         while (hi > lo) {
             if (h_ctr->viol_key != ~0ull) break;
-            if (stop_frontier && hi - lo >= stop_frontier) break;  // the caller continues this level sharded
+            if (fr.stop_frontier && hi - lo >= fr.stop_frontier) break;  // the caller continues this level sharded
             if (cfg.max_levels && level >= cfg.max_levels) { budget = 1; break; }
             if (cfg.max_distinct && hi >= cfg.max_distinct) { budget = 1; break; }
             if (stop_requested) { budget = 1; break; }
@@ -521,32 +631,25 @@ struct Engine : EngineBase {
                 // Small frontier: BLIND_BATCH levels are enqueued back to back; the kernels take each level's range from
                 // LevelCtl and k_end_level applies the same stopping rules as this loop, so one host round trip covers
                 // up to BLIND_BATCH levels instead of one (a level of a few thousand states is pure launch latency).
-                memset(h_lc, 0, sizeof *h_lc);
+                memset(h_lc, 0, sizeof(LevelCtl));
                 h_lc->lo = lo;
                 h_lc->hi = hi;
                 h_lc->max_states = blind_max;
                 h_lc->max_distinct = cfg.max_distinct;
                 h_lc->levels_left = cfg.max_levels ? (unsigned)(cfg.max_levels - level) : 0u;
-                HIP_TRY(hipMemcpyAsync(d_lc, h_lc, sizeof *h_lc, hipMemcpyHostToDevice, stream));
+                HIP_TRY(hipMemcpyAsync(d_lc, h_lc, sizeof(LevelCtl), hipMemcpyHostToDevice, stream));
                 HIP_TRY(hipStreamSynchronize(stream2));  // (nothing of an earlier level is still being materialised)
                 if (inwave_ok() && !alloc_atomic) {  // the batched small levels always write in-wave
                     hipLaunchKernelGGL(k_set_alloc_mode, dim3(1), dim3(1), 0, stream, d_ctr, 1u);
                     alloc_atomic = true;
                 }
                 for (int k = 0; k < BLIND_BATCH; k++) enqueue_blind_level(blind_max);
-                HIP_TRY(hipMemcpyAsync(h_lc, d_lc, sizeof *h_lc, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipMemcpyAsync(h_lc, d_lc, sizeof(LevelCtl), hipMemcpyDeviceToHost, stream));
                 if ((rc = read_counters())) return rc;
                 if ((rc = check_dev_error())) return rc;
                 for (unsigned k = 0; k < h_lc->nlev; k++) {
                     kstat[0].units += hi - lo;  // states expanded by this level (the launches were timed with 0 units)
-                    lo = hi;
-                    hi = h_lc->level_hi[k];
-                    if (hi > lo) {
-                        level_start.push_back(lo);
-                        if (level < MC_MAX_LEVELS) out->level_distinct[level] = hi - lo;
-                        level++;
-                    }
-                    if (level >= MC_MAX_LEVELS) { set_error("too many BFS levels"); return MC_EBADCFG; }
+                    if ((rc = close_level(lo, hi, h_lc->level_hi[k], level, out))) return rc;
                 }
                 progress(level, lo, hi);
                 prev_frontier = hi > lo ? hi - lo : 1;
@@ -561,13 +664,13 @@ struct Engine : EngineBase {
                 alloc_atomic = lvl_inwave;
             }
             prev_frontier = hi - lo;
-            mat_inwave_level = lvl_inwave;
+            fr.mat_inwave_level = lvl_inwave;
             unsigned chunk_no = 0;
             // (odd chunks on their own stream — see stream_b; not with the slot-sliced launches' shared flag array, not for the matrix form)
             const bool two_streams = stream_b && !use_matrix && hi - lo > chunk && !(slices_for(chunk, false) > 1 && (cfg.flags & MC_F_DEADLOCK));
             if (two_streams) {  // what the level's first kernels on `stream` were ordered behind, stream_b's are too
-                hipEventRecord(ev_level, stream);
-                hipStreamWaitEvent(stream_b, ev_level, 0);
+                hipEventRecord(ev_level.get(), stream);
+                hipStreamWaitEvent(stream_b, ev_level.get(), 0);
             }
             for (uint64_t c0 = lo; c0 < hi; ++chunk_no) {
                 const unsigned parity = chunk_no & 1u;
@@ -582,8 +685,8 @@ struct Engine : EngineBase {
                     });
                     finish_chunk<false>(base, ncols, max_slots);
                 } else {
-                    hipStream_t es = two_streams && parity ? stream_b : stream;
-                    if (chunk_no >= 2) hipStreamWaitEvent(es, ev_m[parity], 0);  // new-list `parity` is free again
+                    hipStream_t es = two_streams && parity ? stream_b.s : stream.s;
+                    if (chunk_no >= 2) hipStreamWaitEvent(es, ev_m[parity].get(), 0);  // new-list `parity` is free again
                     RouteArgs rt_new{};
                     rt_new.new_fp = d_newfp;
                     if (lvl_inwave) set_inwave(rt_new);
@@ -593,7 +696,7 @@ struct Engine : EngineBase {
                     const unsigned lflags = cfg.flags | (lvl_inwave && park_levels ? MC_FI_PARK : 0u);
                     timed(0, c1 - c0, [&] {
                         launch_expand<S, false>(!(cfg.flags & MC_F_NOFAMILY), lflags, ncols, es, sg, prm,
-                                                (const uint64_t *)d_arena, c0, c1, ncols, d_table, seen_arg(), d_newlist, seg_cap, d_ctr,
+                                                (const uint64_t *)d_arena, c0, c1, ncols, d_table.p, seen_arg(), d_newlist.p, seg_cap, d_ctr.p,
                                                 cfg.flags, rt_new, parity);
                         if (dl) hipLaunchKernelGGL(k_deadlock_slices, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, es,
                                                    (const uint16_t *)d_nsl, c0, c1, ncols, (const LevelCtl *)nullptr, d_ctr);
@@ -608,76 +711,50 @@ struct Engine : EngineBase {
                 const uint64_t via = h_ctr->via_list - via_seen;
                 via_seen = h_ctr->via_list;
                 const double growth = hi > lo ? (double)(h_ctr->arena_next - hi) / (double)(hi - lo) : 1.0;
-                mat_list_hint = (uint64_t)((double)(via / (chunk_no ? chunk_no : 1u)) * (growth > 1.0 ? growth : 1.0)) + 1;
+                fr.mat_list_hint = (uint64_t)((double)(via / (chunk_no ? chunk_no : 1u)) * (growth > 1.0 ? growth : 1.0)) + 1;
             }
-            lo = hi;
-            hi = h_ctr->arena_next;
-            if (hi > lo) {
-                level_start.push_back(lo);
-                if (level < MC_MAX_LEVELS) out->level_distinct[level] = hi - lo;
-                level++;
-            }
-            if (level >= MC_MAX_LEVELS) { set_error("too many BFS levels"); return MC_EBADCFG; }
+            if ((rc = close_level(lo, hi, h_ctr->arena_next, level, out))) return rc;
             progress(level, lo, hi);
         }
         // a run that stops with an unexpanded frontier (budget) has not evaluated that level's check-on-expand invariants yet
-        if (hi > lo && h_ctr->viol_key == ~0ull && !stop_frontier && (rc = check_frontier(lo, hi))) return rc;
+        if (hi > lo && h_ctr->viol_key == ~0ull && !fr.stop_frontier && (rc = check_frontier(lo, hi))) return rc;
         const auto t1 = std::chrono::steady_clock::now();
         out->seconds = std::chrono::duration<double>(t1 - t0).count();
         out->distinct = h_ctr->arena_next;
-        last_distinct = h_ctr->arena_next;
+        fr.last_distinct = h_ctr->arena_next;
         kstat[2].units = h_ctr->arena_next;
         out->generated = 0;
-        kstat_cells = 0;
-        for (int t = 0; t < NSHARD; t++) { out->generated += h_ctr->generated[t].v; kstat_cells += h_ctr->cells[t].v; }
-        last_generated = out->generated;
+        fr.cells = 0;
+        for (int t = 0; t < NSHARD; t++) { out->generated += h_ctr->generated[t].v; fr.cells += h_ctr->cells[t].v; }
+        fr.last_generated = out->generated;
         // (a resumed run counts from the checkpoint on: via_list starts at 0 there)
-        kstat_inwave = inwave_ok() && h_ctr->arena_next >= h_ctr->via_list + (resuming ? ck_distinct : 0)
-                           ? h_ctr->arena_next - h_ctr->via_list - (resuming ? ck_distinct : 0) : 0;  // (Init's states went through the list too)
-        have_run = true;
+        fr.inwave = inwave_ok() && h_ctr->arena_next >= h_ctr->via_list + (resuming ? ck.distinct : 0)
+                           ? h_ctr->arena_next - h_ctr->via_list - (resuming ? ck.distinct : 0) : 0;  // (Init's states went through the list too)
+        fr.have_run = true;
         out->queue_left = hi - lo;
         out->depth = level;
         out->levels = level;
-        run_lo = lo;
-        run_hi = hi;
+        fr.lo = lo;
+        fr.hi = hi;
         if (h_ctr->viol_key != ~0ull) {
-            have_viol = true;
-            last_viol = h_ctr->viol_key;
-            const unsigned kind = (unsigned)(last_viol & 7u);
-            out->verdict = kind == VK_INVARIANT ? MC_V_INVARIANT : kind == VK_ASSERT ? MC_V_ASSERT
-                         : kind == VK_DEADLOCK ? MC_V_DEADLOCK : MC_V_SPECERR;
-            if (kind == VK_INVARIANT) out->violated_invariant = (int)(last_viol >> 3 & 31u);
+            fr.have_viol = true;
+            fr.last_viol = h_ctr->viol_key;
+            const Viol v(fr.last_viol);
+            out->verdict = v.verdict;
+            out->violated_invariant = v.invariant;
             std::vector<uint64_t> chain;
-            if (build_chain(chain) == MC_OK) {
-                const unsigned slot = (unsigned)(last_viol >> 8 & 0xffffu);
-                const bool extra = kind == VK_INVARIANT && slot < SLOT_PARENT;  // violating successor itself
-                out->trace_len = (uint32_t)chain.size() + (extra ? 1u : 0u);
-            }
+            if (build_chain(chain) == MC_OK) out->trace_len = (uint32_t)chain.size() + (v.extra_state() ? 1u : 0u);
         } else {
             out->verdict = budget ? MC_V_BUDGET : MC_V_OK;
         }
         return MC_OK;
     }
-    uint64_t kstat_cells = 0, kstat_inwave = 0;
-    uint64_t stop_frontier = 0, run_lo = 0, run_hi = 0;  // run() stops before a level of >= stop_frontier states (0 = never)
 
     // ------------------------------------------------------------------------------- checkpoint / recover
     // TLC checkpoints a run into its states/ directory and continues it with -recover (testout1:10: "-- Checkpointing of
     // run states/01-08-03-18-14-01 completed."; .gitignore:2).  Here the resident arena already IS the state store: a
     // checkpoint is the arena's used blocks as they lie in HBM, the level boundaries, the counters and (with MC_F_TRACE)
     // the parent pointers.  The seen-set is not written: recovery re-inserts word 0 of every state (k_reseed_table).
-    struct CkHeader {
-        char magic[8];
-        uint32_t spec_id, nparams;
-        int64_t params[16];
-        uint32_t words, has_trace;
-        uint64_t distinct, generated, cells, lo, hi, nlevels;
-    };
-    struct FileCloser {
-        FILE *f;
-        ~FileCloser() { if (f) fclose(f); }
-    };
-    bool have_run = false, ck_pending = false, ck_in_place = false;
     // mc_engine_step: `levels` more BFS levels.  The first call (or a call after a run that ended: complete, or with an error)
     // starts from Init; a call after a budget stop continues IN PLACE — arena, seen-set and parent pointers stay where they
     // are in HBM, only the counters and the level table are handed over (the same hand-over as restore(), without the file
@@ -685,114 +762,194 @@ struct Engine : EngineBase {
     int step(uint32_t levels, mc_result *out) override {
         if (!levels) return MC_EBADCFG;
         const uint64_t saved = cfg.max_levels;
-        const bool cont = have_run && !have_viol && run_hi > run_lo && !ck_pending;
+        const bool cont = fr.have_run && !fr.have_viol && fr.hi > fr.lo && !ck.pending;
         if (cont) {
-            ck_distinct = last_distinct; ck_generated = last_generated; ck_cells = kstat_cells; ck_lo = run_lo;
-            ck_level_start = level_start;
-            ck_pending = ck_in_place = true;
-            cfg.max_levels = (uint64_t)level_start.size() + levels;
-        } else if (ck_pending) {  // restore() handed a checkpoint over: `levels` more levels beyond the checkpointed ones
-            cfg.max_levels = (uint64_t)ck_level_start.size() + levels;
+            ck.distinct = fr.last_distinct; ck.generated = fr.last_generated; ck.cells = fr.cells; ck.lo = fr.lo;
+            ck.level_start = fr.level_start;
+            ck.pending = ck.in_place = true;
+            cfg.max_levels = (uint64_t)fr.level_start.size() + levels;
+        } else if (ck.pending) {  // restore() handed a checkpoint over: `levels` more levels beyond the checkpointed ones
+            cfg.max_levels = (uint64_t)ck.level_start.size() + levels;
         } else {
             cfg.max_levels = levels;
         }
         const int rc = run(out);
         cfg.max_levels = saved;
-        if (rc) ck_pending = ck_in_place = false;  // after a failure the next step starts over
+        if (rc) ck.pending = ck.in_place = false;  // after a failure the next step starts over
         return rc;
     }
-    uint64_t last_generated = 0, ck_distinct = 0, ck_generated = 0, ck_cells = 0, ck_lo = 0;
-    std::vector<uint64_t> ck_level_start;
+    // ---- the codec both formats share (CkIdent .. CkPart above)
     bool ck_params_comparable() const { return desc.spec_id != MC_SPEC_PCAL; }  // a compiled program's parameter is a host pointer
-    int dev_to_file(const void *dev, size_t bytes, FILE *f) {
-        std::vector<char> buf(bytes < (64u << 20) ? bytes : (64u << 20));
-        for (size_t off = 0; off < bytes; off += buf.size()) {
-            const size_t n = bytes - off < buf.size() ? bytes - off : buf.size();
-            HIP_TRY(hipMemcpy(buf.data(), (const char *)dev + off, n, hipMemcpyDeviceToHost));
-            if (fwrite(buf.data(), 1, n, f) != n) { set_error("checkpoint: short write"); return MC_EBADCFG; }
-        }
+    void ck_fill_ident(CkIdent &id, const CkFormat &fmt) const {
+        memcpy(id.magic, fmt.magic, 8);
+        id.spec_id = desc.spec_id;
+        id.nparams = ck_params_comparable() ? desc.nparams : 1;
+        for (uint32_t i = 0; i < id.nparams && i < 16; i++) id.params[i] = desc.params[i];
+        if (!ck_params_comparable()) id.params[0] = (int64_t)program_hash;  // a compiled program is identified by its image
+        id.words = (uint32_t)W;
+        id.has_trace = d_parent ? 1u : 0u;
+    }
+    static int ck_fail(int code, const char *who, const std::string &msg) { set_error(std::string(who) + ": " + msg); return code; }
+    int ck_check_ident(const CkIdent &id, const CkFormat &fmt) const {
+        if (memcmp(id.magic, fmt.magic, 8) != 0) return ck_fail(MC_EPARSE, fmt.reader, fmt.not_ours);
+        if (id.spec_id != desc.spec_id || id.words != (uint32_t)W) return ck_fail(MC_EBADCFG, fmt.reader, "the checkpoint belongs to another spec");
+        if (ck_params_comparable() && (id.nparams != desc.nparams || memcmp(id.params, desc.params, sizeof(int64_t) * (id.nparams < 16 ? id.nparams : 16)) != 0))
+            return ck_fail(MC_EBADCFG, fmt.reader, "the checkpoint was written with other constants / invariants");
+        if (!ck_params_comparable() && (id.nparams != 1 || (uint64_t)id.params[0] != program_hash)) return ck_fail(MC_EBADCFG, fmt.reader, fmt.other_program);
         return MC_OK;
     }
-    int file_to_dev(void *dev, size_t bytes, FILE *f) {
-        std::vector<char> buf(bytes < (64u << 20) ? bytes : (64u << 20));
-        for (size_t off = 0; off < bytes; off += buf.size()) {
-            const size_t n = bytes - off < buf.size() ? bytes - off : buf.size();
-            if (fread(buf.data(), 1, n, f) != n) { set_error("restore: the checkpoint file is truncated"); return MC_EPARSE; }
-            HIP_TRY(hipMemcpy((char *)dev + off, buf.data(), n, hipMemcpyHostToDevice));
+    // the device sections of a checkpoint of the first n states of the arena, in file order; per_rank: + parent ranks and the seen-set slice
+    std::vector<CkPart> ck_sections(uint64_t n, bool per_rank) const {
+        std::vector<CkPart> v{{d_arena.p, (size_t)((n + 63) >> 6) * (size_t)W * 64 * sizeof(uint64_t)}};
+        if (d_parent) {
+            v.push_back({d_parent.p, (size_t)n * sizeof(uint32_t)});
+            v.push_back({d_pslot.p, (size_t)n * sizeof(uint16_t)});
+        }
+        if (per_rank && d_prank) v.push_back({d_prank.p, (size_t)n});
+        if (per_rank) v.push_back({d_table.p, (size_t)table_cap * sizeof(uint64_t)});
+        return v;
+    }
+    // the whole file: the host parts (header, level table, ...), then the device sections
+    int ck_write(const CkFormat &fmt, const char *path, std::initializer_list<CkPart> host, const std::vector<CkPart> &dev) {
+        FILE *f = fopen(path, "wb");
+        if (!f) return ck_fail(MC_EBADCFG, fmt.writer, std::string("cannot write ") + path);
+        FileCloser closer{f};  // early returns (HIP errors) must not leak the handle
+        int rc = MC_OK;
+        for (const CkPart &h : host)
+            if (!rc && fwrite(h.p, 1, h.bytes, f) != h.bytes) rc = ck_fail(MC_EBADCFG, fmt.writer, "short write");
+        for (const CkPart &d : dev) {
+            if (rc) break;
+            std::vector<char> buf(d.bytes < (64u << 20) ? d.bytes : (64u << 20));
+            for (size_t off = 0; off < d.bytes && !rc; off += buf.size()) {
+                const size_t n = d.bytes - off < buf.size() ? d.bytes - off : buf.size();
+                HIP_TRY(hipMemcpy(buf.data(), (const char *)d.p + off, n, hipMemcpyDeviceToHost));
+                if (fwrite(buf.data(), 1, n, f) != n) rc = ck_fail(MC_EBADCFG, "checkpoint", "short write");
+            }
+        }
+        closer.f = nullptr;
+        if (fclose(f) != 0 && !rc) rc = ck_fail(MC_EBADCFG, fmt.writer, "close failed");
+        return rc;
+    }
+    // reading goes in three steps, the caller's own checks between them: header (read, identity checked), host parts, sections
+    template <class H>
+    int ck_read_header(const CkFormat &fmt, FILE *f, H &h) const {
+        if (fread(&h, sizeof h, 1, f) != 1) return ck_fail(MC_EPARSE, fmt.reader, fmt.not_ours);
+        return ck_check_ident(h.id, fmt);
+    }
+    static int ck_read_host(const CkFormat &fmt, FILE *f, std::initializer_list<CkPart> host) {
+        for (const CkPart &h : host)
+            if (fread(h.p, 1, h.bytes, f) != h.bytes) return ck_fail(MC_EPARSE, fmt.reader, "the checkpoint file is truncated");
+        return MC_OK;
+    }
+    static int ck_read_sections(FILE *f, const std::vector<CkPart> &dev) {
+        for (const CkPart &d : dev) {
+            std::vector<char> buf(d.bytes < (64u << 20) ? d.bytes : (64u << 20));
+            for (size_t off = 0; off < d.bytes; off += buf.size()) {
+                const size_t n = d.bytes - off < buf.size() ? d.bytes - off : buf.size();
+                if (fread(buf.data(), 1, n, f) != n) return ck_fail(MC_EPARSE, "restore", "the checkpoint file is truncated");
+                HIP_TRY(hipMemcpy((char *)d.p + off, buf.data(), n, hipMemcpyHostToDevice));
+            }
         }
         return MC_OK;
     }
     int checkpoint(const char *path) override {
         if (cfg.shard_count > 1) { set_error("checkpoint: not available for a sharded engine"); return MC_EBADCFG; }
-        if (!have_run || have_viol) { set_error("checkpoint: needs a completed mc_engine_run that stopped on a budget (or finished) without a violation"); return MC_EBADCFG; }
+        if (!fr.have_run || fr.have_viol) { set_error("checkpoint: needs a completed mc_engine_run that stopped on a budget (or finished) without a violation"); return MC_EBADCFG; }
         HIP_TRY(hipSetDevice(cfg.device));
         HIP_TRY(hipDeviceSynchronize());
-        FILE *f = fopen(path, "wb");
-        if (!f) { set_error(std::string("checkpoint: cannot write ") + path); return MC_EBADCFG; }
-        FileCloser closer{f};  // early returns (HIP errors) must not leak the handle
         CkHeader h;
         memset(&h, 0, sizeof h);
-        memcpy(h.magic, "TLAMCCK1", 8);
-        h.spec_id = desc.spec_id;
-        h.nparams = ck_params_comparable() ? desc.nparams : 1;
-        for (uint32_t i = 0; i < h.nparams && i < 16; i++) h.params[i] = desc.params[i];
-        if (!ck_params_comparable()) h.params[0] = (int64_t)program_hash;  // a compiled program is identified by its image
-        h.words = (uint32_t)W;
-        h.has_trace = d_parent ? 1u : 0u;
-        h.distinct = last_distinct; h.generated = last_generated; h.cells = kstat_cells;
-        h.lo = run_lo; h.hi = run_hi; h.nlevels = level_start.size();
-        int rc = MC_OK;
-        if (fwrite(&h, sizeof h, 1, f) != 1 || fwrite(level_start.data(), sizeof(uint64_t), level_start.size(), f) != level_start.size()) {
-            set_error("checkpoint: short write");
-            rc = MC_EBADCFG;
-        }
-        const size_t blocks = (size_t)((last_distinct + 63) >> 6);
-        if (!rc) rc = dev_to_file(d_arena, blocks * (size_t)W * 64 * sizeof(uint64_t), f);
-        if (!rc && d_parent) rc = dev_to_file(d_parent, (size_t)last_distinct * sizeof(uint32_t), f);
-        if (!rc && d_parent) rc = dev_to_file(d_pslot, (size_t)last_distinct * sizeof(uint16_t), f);
-        closer.f = nullptr;
-        if (fclose(f) != 0 && !rc) { set_error("checkpoint: close failed"); rc = MC_EBADCFG; }
-        return rc;
+        ck_fill_ident(h.id, CK_FUSED);
+        h.distinct = fr.last_distinct; h.generated = fr.last_generated; h.cells = fr.cells;
+        h.lo = fr.lo; h.hi = fr.hi; h.nlevels = fr.level_start.size();
+        return ck_write(CK_FUSED, path, {{&h, sizeof h}, {fr.level_start.data(), fr.level_start.size() * sizeof(uint64_t)}}, ck_sections(fr.last_distinct, false));
     }
     int restore(const char *path) override {
         if (cfg.shard_count > 1) { set_error("restore: not available for a sharded engine"); return MC_EBADCFG; }
-        FILE *f = fopen(path, "rb");
-        if (!f) { set_error(std::string("restore: cannot read ") + path); return MC_EPARSE; }
-        FileCloser closer{f};
+        FileCloser f{fopen(path, "rb")};
+        if (!f.f) return ck_fail(MC_EPARSE, "restore", std::string("cannot read ") + path);
         CkHeader h;
-        int rc = MC_OK;
-        auto fail = [&](int code, const char *msg) { set_error(msg); rc = code; };
-        if (fread(&h, sizeof h, 1, f) != 1 || memcmp(h.magic, "TLAMCCK1", 8) != 0) fail(MC_EPARSE, "restore: not a checkpoint file");
-        else if (h.spec_id != desc.spec_id || h.words != (uint32_t)W) fail(MC_EBADCFG, "restore: the checkpoint belongs to another spec");
-        else if (ck_params_comparable() && (h.nparams != desc.nparams || memcmp(h.params, desc.params, sizeof(int64_t) * (h.nparams < 16 ? h.nparams : 16)) != 0))
-            fail(MC_EBADCFG, "restore: the checkpoint was written with other constants / invariants");
-        else if (!ck_params_comparable() && (h.nparams != 1 || (uint64_t)h.params[0] != program_hash))
-            fail(MC_EBADCFG, "restore: the checkpoint was written by another compiled program (algorithm, constants, invariants or constraints differ)");
+        int rc = ck_read_header(CK_FUSED, f.f, h);
+        if (rc) return rc;
         // a run may legitimately stop on a budget at a seen-set load of 0.5 - 0.8 (the bench model at 2^27 slots ends at 0.76): its
         // checkpoint must restore into the same configuration; beyond 0.9 the reseeding itself could not finish (DEV_ETABLE)
-        else if (h.distinct * 10 > table_cap * 9) fail(MC_ETABLEFULL, "restore: table_capacity cannot hold the checkpoint's states (load > 0.9)");
-        else if (h.distinct > arena_cap) fail(MC_EARENA, "restore: arena_capacity is smaller than the checkpoint");
-        else if (h.hi != h.distinct || h.lo > h.hi || h.nlevels == 0 || h.nlevels >= MC_MAX_LEVELS) fail(MC_EPARSE, "restore: inconsistent header");
-        else if (d_parent && !h.has_trace) fail(MC_EBADCFG, "restore: the checkpoint holds no parent pointers (written without MC_F_TRACE); run without MC_F_TRACE");
-        if (!rc) {
-            ck_level_start.assign((size_t)h.nlevels, 0);
-            if (fread(ck_level_start.data(), sizeof(uint64_t), ck_level_start.size(), f) != ck_level_start.size()) fail(MC_EPARSE, "restore: the checkpoint file is truncated");
-            else {  // level table: starts at 0, strictly increasing, below the fill level; an unexpanded frontier IS the last level
-                bool ok = ck_level_start[0] == 0 && ck_level_start.back() < h.hi && (h.lo == h.hi || ck_level_start.back() == h.lo);
-                for (size_t k = 1; k < ck_level_start.size() && ok; k++) ok = ck_level_start[k] > ck_level_start[k - 1];
-                if (!ok) fail(MC_EPARSE, "restore: inconsistent level table");
-            }
-        }
-        if (!rc) {
-            HIP_TRY(hipSetDevice(cfg.device));
-            const size_t blocks = (size_t)((h.distinct + 63) >> 6);
-            rc = file_to_dev(d_arena, blocks * (size_t)W * 64 * sizeof(uint64_t), f);
-            if (!rc && d_parent && h.has_trace) rc = file_to_dev(d_parent, (size_t)h.distinct * sizeof(uint32_t), f);
-            if (!rc && d_parent && h.has_trace) rc = file_to_dev(d_pslot, (size_t)h.distinct * sizeof(uint16_t), f);
-        }
+        if (h.distinct * 10 > table_cap * 9) return ck_fail(MC_ETABLEFULL, "restore", "table_capacity cannot hold the checkpoint's states (load > 0.9)");
+        if (h.distinct > arena_cap) return ck_fail(MC_EARENA, "restore", "arena_capacity is smaller than the checkpoint");
+        if (h.hi != h.distinct || h.lo > h.hi || h.nlevels == 0 || h.nlevels >= MC_MAX_LEVELS) return ck_fail(MC_EPARSE, "restore", "inconsistent header");
+        if (d_parent && !h.id.has_trace) return ck_fail(MC_EBADCFG, "restore", "the checkpoint holds no parent pointers (written without MC_F_TRACE); run without MC_F_TRACE");
+        ck.level_start.assign((size_t)h.nlevels, 0);
+        if ((rc = ck_read_host(CK_FUSED, f.f, {{ck.level_start.data(), ck.level_start.size() * sizeof(uint64_t)}}))) return rc;
+        // level table: starts at 0, strictly increasing, below the fill level; an unexpanded frontier IS the last level
+        bool ok = ck.level_start[0] == 0 && ck.level_start.back() < h.hi && (h.lo == h.hi || ck.level_start.back() == h.lo);
+        for (size_t k = 1; k < ck.level_start.size() && ok; k++) ok = ck.level_start[k] > ck.level_start[k - 1];
+        if (!ok) return ck_fail(MC_EPARSE, "restore", "inconsistent level table");
+        HIP_TRY(hipSetDevice(cfg.device));
+        if ((rc = ck_read_sections(f.f, ck_sections(h.distinct, false)))) return rc;
+        ck.distinct = h.distinct; ck.generated = h.generated; ck.cells = h.cells; ck.lo = h.lo;
+        ck.pending = true;  // the next run() continues from here
+        return MC_OK;
+    }
+    // One checkpoint file per rank (testout1:10).
+    // A rank's share of a sharded run cannot be rebuilt from its arena alone: the states a rank HOLDS are the ones it generated
+    // (stay levels) or was sent (move levels), the fingerprints its seen-set slice holds are the ones it OWNS.  So a rank's file is
+    // its arena, its parent pointers (index, slot, rank), its seen-set slice as it lies in HBM, its counters, and the level table of
+    // the whole job (the same on every rank; the level loop hands it over when a run ends: shard_note_levels).  Restoring needs
+    // the same world size, rank, table_capacity and spec; the next mc_shard_run* then continues with the unexpanded frontier.
+    int shard_checkpoint(const char *path) override {
+        if (!sh.ck_ok || sh.levels.empty()) { set_error("mc_shard_checkpoint: needs a sharded run that ended (finished, or stopped on a budget) without an error"); return MC_EBADCFG; }
+        HIP_TRY(hipSetDevice(cfg.device));
+        HIP_TRY(hipDeviceSynchronize());
+        ShCkHeader h;
+        memset(&h, 0, sizeof h);
+        ck_fill_ident(h.id, CK_RANK);
+        h.rank = cfg.shard_rank; h.world = nranks();
+        h.table_cap = table_cap | (seen_sparse ? SEEN_SPARSE : 0); h.lo = sh.lo; h.hi = sh.hi; h.next = sh.next; h.dup = sh.dup; h.nlevels = sh.levels.size();
+        DevCounters dc;
+        HIP_TRY(hipMemcpy(&dc, d_ctr, sizeof dc, hipMemcpyDeviceToHost));
+        ShCkCounters c;
+        memset(&c, 0, sizeof c);
+        c.arena_next = dc.arena_next; c.viol_key = dc.viol_key; c.via_list = dc.via_list; c.error = dc.error;
+        for (int t = 0; t < NSHARD; t++) { c.generated[t] = dc.generated[t].v; c.cells[t] = dc.cells[t].v; }
+        return ck_write(CK_RANK, path, {{&h, sizeof h}, {sh.levels.data(), sh.levels.size() * sizeof(uint64_t)}, {&c, sizeof c}}, ck_sections(sh.next, true));
+    }
+    int shard_restore_read(FILE *f, ShCkHeader &h, ShCkCounters &fc) {
+        int rc = ck_read_header(CK_RANK, f, h);
         if (rc) return rc;
-        ck_distinct = h.distinct; ck_generated = h.generated; ck_cells = h.cells; ck_lo = h.lo;
-        ck_pending = true;  // the next run() continues from here
+        const char *who = CK_RANK.reader;
+        if (h.rank != cfg.shard_rank || h.world != nranks()) return ck_fail(MC_EBADCFG, who, "the file is another rank's, or of a run with another number of ranks");
+        if (h.table_cap != (table_cap | (seen_sparse ? SEEN_SPARSE : 0)))
+            return ck_fail(MC_EBADCFG, who, "table_capacity differs from the checkpointed run's, or the bucket form it implies (4 slots when the table is >= 3 x the arena): the seen-set slice is stored as it lay in HBM");
+        if (h.next > arena_cap) return ck_fail(MC_EARENA, who, "arena_capacity is smaller than the checkpoint");
+        if (h.lo > h.hi || h.hi != h.next || h.dup > h.next || h.nlevels == 0 || h.nlevels >= MC_MAX_LEVELS) return ck_fail(MC_EPARSE, who, "inconsistent header");
+        if ((d_parent.p != nullptr) != (h.id.has_trace != 0)) return ck_fail(MC_EBADCFG, who, "MC_F_TRACE differs from the checkpointed run's");
+        sh.levels.assign((size_t)h.nlevels, 0);
+        if ((rc = ck_read_host(CK_RANK, f, {{sh.levels.data(), sh.levels.size() * sizeof(uint64_t)}, {&fc, sizeof fc}}))) return rc;
+        if (fc.arena_next != h.next || fc.viol_key != ~0ull || fc.error) return ck_fail(MC_EPARSE, who, "inconsistent counters");
+        HIP_TRY(hipSetDevice(cfg.device));
+        HIP_TRY(hipDeviceSynchronize());
+        if ((rc = ck_read_sections(f, ck_sections(h.next, true)))) return rc;
+        if (fgetc(f) != EOF) return ck_fail(MC_EPARSE, who, "trailing bytes (not the file this engine's configuration wrote)");
+        return MC_OK;
+    }
+    int shard_restore(const char *path) override {
+        if (int rc = refuse_packed()) return rc;
+        FileCloser f{fopen(path, "rb")};
+        if (!f.f) return ck_fail(MC_EPARSE, "mc_shard_restore", std::string("cannot read ") + path);
+        ShCkHeader h;
+        ShCkCounters fc;
+        if (int rc = shard_restore_read(f.f, h, fc)) { sh.levels.clear(); return rc; }
+        DevCounters c;
+        memset(&c, 0, sizeof c);
+        c.arena_next = fc.arena_next; c.viol_key = fc.viol_key; c.via_list = fc.via_list;
+        for (int t = 0; t < NSHARD; t++) { c.generated[t].v = fc.generated[t]; c.cells[t].v = fc.cells[t]; }
+        HIP_TRY(hipMemcpy(d_ctr, &c, sizeof c, hipMemcpyHostToDevice));
+        memset(kstat, 0, sizeof kstat);
+        sh.lo = h.lo; sh.hi = h.hi; sh.next = h.next; sh.dup = h.dup;
+        fr.last_distinct = sh.next;
+        fr.have_viol = false;
+        sh.sl[0].launched = sh.sl[1].launched = false;
+        sh.resume = true;
+        sh.ck_ok = false;
         return MC_OK;
     }
 
@@ -804,11 +961,10 @@ struct Engine : EngineBase {
     // arena indices from an initial state to the state the violation was found in / from
     int build_chain(std::vector<uint64_t> &chain) {
         chain.clear();
-        if (!have_viol) return MC_ESTATE;
-        const unsigned slot = (unsigned)(last_viol >> 8 & 0xffffu);
-        if (slot == SLOT_INIT) return MC_OK;  // violated by an initial state: handled by the caller
+        if (!fr.have_viol) return MC_ESTATE;
+        if (Viol(fr.last_viol).slot == SLOT_INIT) return MC_OK;  // violated by an initial state: handled by the caller
         if (!d_parent) { set_error("engine created without MC_F_TRACE"); return MC_ESTATE; }
-        uint64_t idx = viol_idx(last_viol);
+        uint64_t idx = viol_idx(fr.last_viol);
         for (int guard = 0; guard < MC_MAX_LEVELS; ++guard) {
             chain.push_back(idx);
             uint32_t p;
@@ -821,15 +977,16 @@ struct Engine : EngineBase {
         return MC_OK;
     }
     int trace(uint8_t *states_out, int32_t *actions_out, size_t *n_inout) override {
-        if (sim_trace_n) return sim_trace_out(states_out, actions_out, n_inout);
-        if (!have_viol) { *n_inout = 0; return MC_OK; }
+        if (sim.trace_n) return sim_trace_out(states_out, actions_out, n_inout);
+        if (!fr.have_viol) { *n_inout = 0; return MC_OK; }
         HIP_TRY(hipSetDevice(cfg.device));
-        const unsigned kind = (unsigned)(last_viol & 7u), slot = (unsigned)(last_viol >> 8 & 0xffffu);
+        const Viol v(fr.last_viol);
+        const unsigned slot = v.slot;
         std::vector<uint64_t> words;
         std::vector<int32_t> acts;
         if (slot == SLOT_INIT) {  // an initial state violates an invariant
             words.resize(W);
-            S::init(prm, viol_idx(last_viol), WordRef{words.data(), 1});
+            S::init(prm, viol_idx(fr.last_viol), WordRef{words.data(), 1});
             acts.push_back(-1);
         } else {
             std::vector<uint64_t> chain;
@@ -845,7 +1002,7 @@ struct Engine : EngineBase {
                     acts.push_back(S::action_of(prm, &words[(k - 1) * W], (int)ps));
                 }
             }
-            if (kind == VK_INVARIANT && slot < SLOT_PARENT) {  // append the violating successor
+            if (v.extra_state()) {  // append the violating successor
                 std::vector<uint64_t> last(words.end() - W, words.end());
                 words.resize(words.size() + W);
                 S::apply(prm, CWordRef{last.data(), 1}, (int)slot, WordRef{&words[words.size() - W], 1});
@@ -864,11 +1021,11 @@ struct Engine : EngineBase {
     }
     int read_states(uint64_t first, uint64_t count, uint8_t *out) override {
         if (!count) return MC_OK;
-        if (first + count > last_distinct) { set_error("read_states: range beyond the states found by the last run"); return MC_EBADCFG; }
+        if (first + count > fr.last_distinct) { set_error("read_states: range beyond the states found by the last run"); return MC_EBADCFG; }
         HIP_TRY(hipSetDevice(cfg.device));
-        uint64_t *tmp = nullptr;
+        DevBuf<uint64_t> tmp;
         const uint64_t piece = 1ull << 20;
-        HIP_TRY(hipMalloc(&tmp, (count < piece ? count : piece) * W * sizeof(uint64_t)));
+        HIP_TRY(tmp.alloc((count < piece ? count : piece) * W));
         for (uint64_t off = 0; off < count; off += piece) {
             const uint64_t n = count - off < piece ? count - off : piece;
             hipLaunchKernelGGL(k_gather_states, dim3((unsigned)((n * W + 255) / 256)), dim3(256), 0, stream, d_arena, W, first + off, n, tmp);
@@ -883,12 +1040,10 @@ struct Engine : EngineBase {
                 e1 = hipMemcpyAsync(out + off * W * sizeof(uint64_t), tmp, n * W * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
                 e2 = hipStreamSynchronize(stream);
             }
-            if (e1 != hipSuccess || e2 != hipSuccess) { hipFree(tmp); set_error("read_states: copy failed"); return MC_EHIP; }
+            if (e1 != hipSuccess || e2 != hipSuccess) { set_error("read_states: copy failed"); return MC_EHIP; }
         }
-        hipFree(tmp);
         return MC_OK;
     }
-    uint64_t last_distinct = 0;
     // Profiling aid: expand every resident state again (seen-set already full, so every probe hits)
     // with optional ablation flags; returns the kernel time.  State counts are not changed.
     int debug_flags(uint32_t set, uint32_t clear) override { cfg.flags = (cfg.flags & ~clear) | set; return MC_OK; }
@@ -907,84 +1062,57 @@ struct Engine : EngineBase {
     }
     int debug_reexpand(unsigned extra_flags, double *ms) override {
         HIP_TRY(hipSetDevice(cfg.device));
-        hipEvent_t a, b;
-        HIP_TRY(hipEventCreate(&a));
-        HIP_TRY(hipEventCreate(&b));
-        HIP_TRY(hipEventRecord(a, stream));
-        for (uint64_t c0 = 0; c0 < last_distinct; c0 += chunk) {
-            const uint64_t c1 = c0 + chunk < last_distinct ? c0 + chunk : last_distinct;
+        Event a(hipEventDefault), b(hipEventDefault);  // (timing events)
+        HIP_TRY(hipEventRecord(a.get(), stream));
+        for (uint64_t c0 = 0; c0 < fr.last_distinct; c0 += chunk) {
+            const uint64_t c1 = c0 + chunk < fr.last_distinct ? c0 + chunk : fr.last_distinct;
             const uint64_t ncols = ((c1 - c0) + 63) & ~63ull;
             launch_expand<S, false>(!((cfg.flags | extra_flags) & MC_F_NOFAMILY), cfg.flags | extra_flags, ncols, stream, 0u, prm,
-                                    (const uint64_t *)d_arena, c0, c1, ncols, d_table, seen_arg(), d_newlist, seg_cap, d_ctr,
+                                    (const uint64_t *)d_arena, c0, c1, ncols, d_table.p, seen_arg(), d_newlist.p, seg_cap, d_ctr.p,
                                     cfg.flags | extra_flags, RouteArgs{}, 0u);
             hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, stream, d_ctr, 0u);
         }
-        HIP_TRY(hipEventRecord(b, stream));
+        HIP_TRY(hipEventRecord(b.get(), stream));
         HIP_TRY(hipStreamSynchronize(stream));
         float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, a, b));
+        HIP_TRY(hipEventElapsedTime(&t, a.get(), b.get()));
         *ms = t;
-        hipEventDestroy(a);
-        hipEventDestroy(b);
         // restore arena_next (k_commit added nothing: no probe can be new) and leave counters as they were
         return MC_OK;
     }
     // ------------------------------------------------------------------ sharded step API
-    uint64_t sh_lo = 0, sh_hi = 0, sh_next = 0;  // local frontier [sh_lo, sh_hi), arena fill level
-    // Two expand slots: the route-mode expand of chunk r+1 (on `stream`) overlaps the exchange, probe and keep /
-    // materialise of chunk r (kernels on `stream2`, collectives on the caller's stream).
-    struct ShSlot {
-        uint64_t *rt_fp = nullptr;
-        uint32_t *rt_src = nullptr, *pend_src = nullptr;
-        PaddedCounter *rt_cur = nullptr;  // [nranks*NSHARD] route cursors
-        uint64_t rt_subcap = 0, pend_cap = 0, pend_total = 0, chunk_base = 0, count = 0, ncols = 0;
-        BlockPlan plan;          // of the slot's last shard_materialise (for shard_materialise_parents)
-        uint64_t moved = 0;
-        OwnerOffsets pend_off;
-        bool launched = false, keep_pending = false;
-    } sl[2];
-    uint32_t *d_new_src = nullptr, *d_incl = nullptr;
-    uint64_t new_cap = 0;
-    unsigned long long *d_ends = nullptr, *h_ends = nullptr;
-    PaddedCounter *h_cur = nullptr;  // pinned copy of one slot's route cursors
-    void *d_scan_tmp = nullptr;
-    size_t scan_tmp_bytes = 0;
-    unsigned nranks() const { return cfg.shard_count > 1 ? cfg.shard_count : 1; }
-
+    // the slot's exchange buffers for rounds of up to send_cap candidates (grow-only; every caller of a slot passes through here)
     int shard_alloc(ShSlot &q, uint64_t send_cap) {
         const unsigned P = nranks();
-        if (send_cap > q.pend_cap) {
-            if (q.rt_fp) { hipFree(q.rt_fp); hipFree(q.rt_src); hipFree(q.pend_src); q.rt_fp = nullptr; }
+        if (send_cap > q.pend_src.n) {  // all three go before any comes back, pend_src last: its size is the capacity the slot answers for
+            q.rt_fp.reset(); q.rt_src.reset(); q.pend_src.reset();
             q.rt_subcap = (send_cap / (P * NSHARD)) * 2 + 4096;
-            HIP_TRY(hipMalloc(&q.rt_fp, (size_t)P * NSHARD * q.rt_subcap * sizeof(uint64_t)));
-            HIP_TRY(hipMalloc(&q.rt_src, (size_t)P * NSHARD * q.rt_subcap * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc(&q.pend_src, send_cap * sizeof(uint32_t)));
-            q.pend_cap = send_cap;
+            HIP_TRY(q.rt_fp.alloc((size_t)P * NSHARD * q.rt_subcap));
+            HIP_TRY(q.rt_src.alloc((size_t)P * NSHARD * q.rt_subcap));
+            HIP_TRY(q.pend_src.alloc(send_cap));
         }
-        if (!q.rt_cur) HIP_TRY(hipMalloc(&q.rt_cur, (size_t)(P * NSHARD) * sizeof(PaddedCounter)));
-        if (send_cap > new_cap) {
-            if (d_new_src) { hipFree(d_new_src); hipFree(d_incl); d_new_src = nullptr; }
-            HIP_TRY(hipMalloc(&d_new_src, send_cap * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc(&d_incl, send_cap * sizeof(uint32_t)));
-            new_cap = send_cap;
+        HIP_TRY(q.rt_cur.reserve((size_t)(P * NSHARD)));
+        if (send_cap > sh.d_incl.n) {
+            sh.d_new_src.reset(); sh.d_incl.reset();
+            HIP_TRY(sh.d_new_src.alloc(send_cap));
+            HIP_TRY(sh.d_incl.alloc(send_cap));
         }
-        if (!d_ends) {
-            HIP_TRY(hipMalloc(&d_ends, 8 * sizeof(unsigned long long)));
-            HIP_TRY(hipHostMalloc(&h_ends, 8 * sizeof(unsigned long long)));
-            HIP_TRY(hipHostMalloc(&h_cur, (size_t)8 * NSHARD * sizeof(PaddedCounter)));
-        }
+        HIP_TRY(sh.d_ends.reserve(8));
+        HIP_TRY(sh.h_ends.reserve(8));
+        HIP_TRY(sh.h_cur.reserve((size_t)8 * NSHARD));
         return MC_OK;
     }
     int scan_answers(const uint8_t *answers_back, uint64_t n, hipStream_t on) {
         hipcub::TransformInputIterator<uint32_t, AnswerCast, const uint8_t *> in(answers_back, AnswerCast());
         size_t need = 0;
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, in, d_incl, (int)n, on));
-        if (need > scan_tmp_bytes) {
-            if (d_scan_tmp) hipFree(d_scan_tmp);
-            HIP_TRY(hipMalloc(&d_scan_tmp, need));
-            scan_tmp_bytes = need;
-        }
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(d_scan_tmp, need, in, d_incl, (int)n, on));
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, in, sh.d_incl.p, (int)n, on));
+        HIP_TRY(sh.d_scan_tmp.reserve(need));
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(sh.d_scan_tmp.p, need, in, sh.d_incl.p, (int)n, on));
+        return MC_OK;
+    }
+    // generated code with packed rows serves one GPU: its rows cannot travel between ranks
+    static int refuse_packed() {
+        if constexpr (PackedRows<S>::value) { set_error("this engine of generated code stores rows packed to its program's cell ranges and serves ONE GPU: create a sharded engine with shard_count > 1 (or $TLAMC_JIT_PACK=0)"); return MC_EBADCFG; }
         return MC_OK;
     }
     // a sharded run that failed mid-level (a full route bucket, MC_ETABLEFULL ...) leaves its slots as they were: the remedy the
@@ -992,35 +1120,23 @@ struct Engine : EngineBase {
     void shard_reset_slots() {
         hipSetDevice(cfg.device);
         hipDeviceSynchronize();  // (whatever the failed run left on the streams has drained; its events are complete)
-        for (auto &q : sl) { q.launched = false; q.keep_pending = false; q.pend_total = 0; q.moved = 0; q.count = 0; }
+        for (auto &q : sh.sl) { q.launched = false; q.keep_pending = false; q.pend_total = 0; q.moved = 0; q.count = 0; }
     }
     int shard_begin() override {
-        if constexpr (PackedRows<S>::value) { set_error("this engine of generated code stores rows packed to its program's cell ranges and serves ONE GPU: create a sharded engine with shard_count > 1 (or $TLAMC_JIT_PACK=0)"); return MC_EBADCFG; }
+        int rc = refuse_packed();
+        if (rc) return rc;
         if (nranks() > 8) { set_error("at most 8 shards"); return MC_EBADCFG; }
-        sh_dup = 0;
-        sh_resume = sh_ck_ok = false;
+        sh.dup = 0;
+        sh.resume = sh.ck_ok = false;
         shard_reset_slots();
         HIP_TRY(hipSetDevice(cfg.device));
         memset(kstat, 0, sizeof kstat);
-        HIP_TRY(hipMemsetAsync(d_table, 0, table_cap * sizeof(uint64_t), stream));
-        DevCounters init_c;
-        memset(&init_c, 0, sizeof init_c);
-        init_c.viol_key = ~0ull;
-        HIP_TRY(hipMemcpyAsync(d_ctr, &init_c, sizeof init_c, hipMemcpyHostToDevice, stream));
-        const uint64_t ninit = S::num_init(prm);
-        for (uint64_t first = 0; first < ninit; first += chunk) {
-            const uint64_t count = ninit - first < chunk ? ninit - first : chunk;
-            const uint64_t ncols = (count + 63) & ~63ull;
-            hipLaunchKernelGGL(k_init_cand<S>, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, stream, prm, first, count,
-                               d_inittmp, d_cand, ncols, d_nsl, d_ctr, cfg.shard_rank, cfg.shard_count);
-            finish_chunk<true>(first, ncols, 1);
-        }
-        int rc = read_counters();
-        if (rc) return rc;
+        if ((rc = seed_init(cfg.shard_rank, cfg.shard_count, false, false, nullptr))) return rc;
+        if ((rc = read_counters())) return rc;
         if ((rc = check_dev_error())) return rc;
-        sh_lo = 0;
-        sh_hi = sh_next = h_ctr->arena_next;
-        last_distinct = sh_next;
+        sh.lo = 0;
+        sh.hi = sh.next = h_ctr->arena_next;
+        fr.last_distinct = sh.next;
         return MC_OK;
     }
     // The first levels of a run are tiny: sharding them costs several collectives per level and balances nothing.
@@ -1028,20 +1144,18 @@ struct Engine : EngineBase {
     // nranks-th state of that level as its local frontier, and the sharded rounds start there.  The seen-set of each
     // rank then holds ALL prefix fingerprints (a superset of the ones it owns: harmless); rank 0 alone reports the
     // prefix's `generated`, and distinct_local excludes what other ranks already count.
-    uint64_t sh_dup = 0;
-    std::unique_ptr<mc_result> prefix_res{new mc_result()};
     int shard_begin_replicated(uint64_t min_frontier, uint64_t max_distinct, uint64_t max_levels, uint64_t *levels_out, uint32_t *nlevels) override {
-        if constexpr (PackedRows<S>::value) { set_error("this engine of generated code stores rows packed to its program's cell ranges and serves ONE GPU: create a sharded engine with shard_count > 1 (or $TLAMC_JIT_PACK=0)"); return MC_EBADCFG; }
+        if (int rc = refuse_packed()) return rc;
         if (nranks() > 8) { set_error("at most 8 shards"); return MC_EBADCFG; }
-        mc_result &res = *prefix_res;  // large (level table): not on the stack, and not shared between engines / threads
-        sh_resume = sh_ck_ok = false;
+        mc_result &res = *sh.prefix_res;  // (not shared between engines / threads)
+        sh.resume = sh.ck_ok = false;
         shard_reset_slots();
         const uint64_t saved_md = cfg.max_distinct, saved_ml = cfg.max_levels;
         cfg.max_distinct = max_distinct;  // the whole job's budgets: the prefix stops where the single-GPU run would
         cfg.max_levels = max_levels;
-        stop_frontier = min_frontier ? min_frontier : 1;
+        fr.stop_frontier = min_frontier ? min_frontier : 1;
         const int rc = run(&res);
-        stop_frontier = 0;
+        fr.stop_frontier = 0;
         cfg.max_distinct = saved_md;
         cfg.max_levels = saved_ml;
         if (rc) return rc;
@@ -1050,7 +1164,7 @@ struct Engine : EngineBase {
         for (uint32_t k = 0; k < res.levels && k < cap; k++) levels_out[k] = res.level_distinct[k];
         if (res.levels > cap) { set_error("shard_begin_replicated: level buffer too small"); return MC_EBADCFG; }
         const unsigned P = nranks(), r = cfg.shard_rank;
-        const uint64_t lo = run_lo, hi = run_hi;
+        const uint64_t lo = fr.lo, hi = fr.hi;
         const bool go_on = h_ctr->viol_key == ~0ull && hi > lo;  // otherwise finished or failed inside the prefix
         if (go_on)
             hipLaunchKernelGGL(k_take_owned<S>, dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0, stream, prm, d_arena, lo, hi, r, P, hi,
@@ -1059,180 +1173,69 @@ struct Engine : EngineBase {
         int rc2 = read_counters();
         if (rc2) return rc2;
         if ((rc2 = check_dev_error())) return rc2;
-        sh_lo = hi;
-        sh_hi = sh_next = h_ctr->arena_next;
-        sh_dup = r == 0 ? sh_hi - hi : sh_hi;
-        last_distinct = sh_next;
+        sh.lo = hi;
+        sh.hi = sh.next = h_ctr->arena_next;
+        sh.dup = r == 0 ? sh.hi - hi : sh.hi;
+        fr.last_distinct = sh.next;
         return MC_OK;
     }
-    int shard_level_size(uint64_t *n) override { *n = sh_hi - sh_lo; return MC_OK; }
-    // ------------------------------------------------------------------ one checkpoint file per rank (testout1:10)
-    // A rank's share of a sharded run cannot be rebuilt from its arena alone: the states a rank HOLDS are the ones it generated
-    // (stay levels) or was sent (move levels), the fingerprints its seen-set slice holds are the ones it OWNS.  So a rank's file is
-    // its arena, its parent pointers (index, slot, rank), its seen-set slice as it lies in HBM, its counters, and the level table of
-    // the whole job (the same on every rank; the level loop hands it over when a run ends: shard_note_levels).  Restoring needs
-    // the same world size, rank, table_capacity and spec; the next mc_shard_run* then continues with the unexpanded frontier.
-    struct ShCkHeader {
-        char magic[8];
-        uint32_t spec_id, nparams;
-        int64_t params[16];
-        uint32_t words, has_trace, rank, world;
-        uint64_t table_cap, lo, hi, next, dup, nlevels;
-    };
-    // the counters a per-rank checkpoint carries, field by field (the file held a raw DevCounters, whose layout —
-    // padding, alignment, members — changes with the kernels; "TLAMCSK1" files are refused as "not a per-rank checkpoint file")
-    struct ShCkCounters {
-        uint64_t arena_next, viol_key, via_list;
-        uint64_t generated[NSHARD], cells[NSHARD];
-        uint32_t error, pad;
-    };
-    std::vector<uint64_t> sh_levels;
-    bool sh_ck_ok = false, sh_resume = false;
+    int shard_level_size(uint64_t *n) override { *n = sh.hi - sh.lo; return MC_OK; }
     int shard_note_levels(const uint64_t *levels, uint32_t n, int32_t verdict) override {
-        sh_levels.assign(levels, levels + n);
-        sh_ck_ok = verdict == MC_V_OK || verdict == MC_V_BUDGET;
+        sh.levels.assign(levels, levels + n);
+        sh.ck_ok = verdict == MC_V_OK || verdict == MC_V_BUDGET;
         return MC_OK;
     }
     int shard_resume(uint64_t *levels_out, uint32_t *nlevels) override {
         const uint32_t cap = *nlevels;
         *nlevels = 0;
-        if (!sh_resume) return MC_OK;
-        if (sh_levels.size() > cap) { set_error("shard_resume: level buffer too small"); return MC_EBADCFG; }
-        for (size_t k = 0; k < sh_levels.size(); k++) levels_out[k] = sh_levels[k];
-        *nlevels = (uint32_t)sh_levels.size();
-        sh_resume = false;
-        return MC_OK;
-    }
-    int shard_checkpoint(const char *path) override {
-        if (!sh_ck_ok || sh_levels.empty()) { set_error("mc_shard_checkpoint: needs a sharded run that ended (finished, or stopped on a budget) without an error"); return MC_EBADCFG; }
-        HIP_TRY(hipSetDevice(cfg.device));
-        HIP_TRY(hipDeviceSynchronize());
-        FILE *f = fopen(path, "wb");
-        if (!f) { set_error(std::string("mc_shard_checkpoint: cannot write ") + path); return MC_EBADCFG; }
-        FileCloser closer{f};
-        ShCkHeader h;
-        memset(&h, 0, sizeof h);
-        memcpy(h.magic, "TLAMCSK2", 8);
-        h.spec_id = desc.spec_id;
-        h.nparams = ck_params_comparable() ? desc.nparams : 1;
-        for (uint32_t i = 0; i < h.nparams && i < 16; i++) h.params[i] = desc.params[i];
-        if (!ck_params_comparable()) h.params[0] = (int64_t)program_hash;
-        h.words = (uint32_t)W; h.has_trace = d_parent ? 1u : 0u; h.rank = cfg.shard_rank; h.world = nranks();
-        h.table_cap = table_cap | (seen_sparse ? SEEN_SPARSE : 0); h.lo = sh_lo; h.hi = sh_hi; h.next = sh_next; h.dup = sh_dup; h.nlevels = sh_levels.size();
-        int rc = MC_OK;
-        DevCounters dc;
-        HIP_TRY(hipMemcpy(&dc, d_ctr, sizeof dc, hipMemcpyDeviceToHost));
-        ShCkCounters c;
-        memset(&c, 0, sizeof c);
-        c.arena_next = dc.arena_next; c.viol_key = dc.viol_key; c.via_list = dc.via_list; c.error = dc.error;
-        for (int t = 0; t < NSHARD; t++) { c.generated[t] = dc.generated[t].v; c.cells[t] = dc.cells[t].v; }
-        if (fwrite(&h, sizeof h, 1, f) != 1 || fwrite(sh_levels.data(), sizeof(uint64_t), sh_levels.size(), f) != sh_levels.size() || fwrite(&c, sizeof c, 1, f) != 1) {
-            set_error("mc_shard_checkpoint: short write");
-            rc = MC_EBADCFG;
-        }
-        const size_t blocks = (size_t)((sh_next + 63) >> 6);
-        if (!rc) rc = dev_to_file(d_arena, blocks * (size_t)W * 64 * sizeof(uint64_t), f);
-        if (!rc && d_parent) rc = dev_to_file(d_parent, (size_t)sh_next * sizeof(uint32_t), f);
-        if (!rc && d_parent) rc = dev_to_file(d_pslot, (size_t)sh_next * sizeof(uint16_t), f);
-        if (!rc && d_prank) rc = dev_to_file(d_prank, (size_t)sh_next, f);
-        if (!rc) rc = dev_to_file(d_table, (size_t)table_cap * sizeof(uint64_t), f);
-        closer.f = nullptr;
-        if (fclose(f) != 0 && !rc) { set_error("mc_shard_checkpoint: close failed"); rc = MC_EBADCFG; }
-        return rc;
-    }
-    int shard_restore(const char *path) override {
-        if constexpr (PackedRows<S>::value) { set_error("this engine of generated code stores rows packed to its program's cell ranges and serves ONE GPU: create a sharded engine with shard_count > 1 (or $TLAMC_JIT_PACK=0)"); return MC_EBADCFG; }
-        FILE *f = fopen(path, "rb");
-        if (!f) { set_error(std::string("mc_shard_restore: cannot read ") + path); return MC_EPARSE; }
-        FileCloser closer{f};
-        ShCkHeader h;
-        int rc = MC_OK;
-        auto fail = [&](int code, const char *msg) { set_error(msg); rc = code; };
-        if (fread(&h, sizeof h, 1, f) != 1 || memcmp(h.magic, "TLAMCSK2", 8) != 0) fail(MC_EPARSE, "mc_shard_restore: not a per-rank checkpoint file (of this library version)");
-        else if (h.spec_id != desc.spec_id || h.words != (uint32_t)W) fail(MC_EBADCFG, "mc_shard_restore: the checkpoint belongs to another spec");
-        else if (ck_params_comparable() && (h.nparams != desc.nparams || memcmp(h.params, desc.params, sizeof(int64_t) * (h.nparams < 16 ? h.nparams : 16)) != 0))
-            fail(MC_EBADCFG, "mc_shard_restore: the checkpoint was written with other constants / invariants");
-        else if (!ck_params_comparable() && (h.nparams != 1 || (uint64_t)h.params[0] != program_hash))
-            fail(MC_EBADCFG, "mc_shard_restore: the checkpoint was written by another compiled program");
-        else if (h.rank != cfg.shard_rank || h.world != nranks()) fail(MC_EBADCFG, "mc_shard_restore: the file is another rank's, or of a run with another number of ranks");
-        else if (h.table_cap != (table_cap | (seen_sparse ? SEEN_SPARSE : 0)))
-            fail(MC_EBADCFG, "mc_shard_restore: table_capacity differs from the checkpointed run's, or the bucket form it implies (4 slots when the table is >= 3 x the arena): the seen-set slice is stored as it lay in HBM");
-        else if (h.next > arena_cap) fail(MC_EARENA, "mc_shard_restore: arena_capacity is smaller than the checkpoint");
-        else if (h.lo > h.hi || h.hi != h.next || h.dup > h.next || h.nlevels == 0 || h.nlevels >= MC_MAX_LEVELS) fail(MC_EPARSE, "mc_shard_restore: inconsistent header");
-        else if ((d_parent != nullptr) != (h.has_trace != 0)) fail(MC_EBADCFG, "mc_shard_restore: MC_F_TRACE differs from the checkpointed run's");
-        ShCkCounters fc;
-        memset(&fc, 0, sizeof fc);
-        if (!rc) {
-            sh_levels.assign((size_t)h.nlevels, 0);
-            if (fread(sh_levels.data(), sizeof(uint64_t), sh_levels.size(), f) != sh_levels.size() || fread(&fc, sizeof fc, 1, f) != 1) fail(MC_EPARSE, "mc_shard_restore: the checkpoint file is truncated");
-            else if (fc.arena_next != h.next || fc.viol_key != ~0ull || fc.error) fail(MC_EPARSE, "mc_shard_restore: inconsistent counters");
-        }
-        if (!rc) {
-            HIP_TRY(hipSetDevice(cfg.device));
-            HIP_TRY(hipDeviceSynchronize());
-            const size_t blocks = (size_t)((h.next + 63) >> 6);
-            rc = file_to_dev(d_arena, blocks * (size_t)W * 64 * sizeof(uint64_t), f);
-            if (!rc && d_parent) rc = file_to_dev(d_parent, (size_t)h.next * sizeof(uint32_t), f);
-            if (!rc && d_parent) rc = file_to_dev(d_pslot, (size_t)h.next * sizeof(uint16_t), f);
-            if (!rc && d_prank) rc = file_to_dev(d_prank, (size_t)h.next, f);
-            if (!rc) rc = file_to_dev(d_table, (size_t)table_cap * sizeof(uint64_t), f);
-            if (!rc && fgetc(f) != EOF) fail(MC_EPARSE, "mc_shard_restore: trailing bytes (not the file this engine's configuration wrote)");
-        }
-        if (rc) { sh_levels.clear(); return rc; }
-        DevCounters c;
-        memset(&c, 0, sizeof c);
-        c.arena_next = fc.arena_next; c.viol_key = fc.viol_key; c.via_list = fc.via_list;
-        for (int t = 0; t < NSHARD; t++) { c.generated[t].v = fc.generated[t]; c.cells[t].v = fc.cells[t]; }
-        HIP_TRY(hipMemcpy(d_ctr, &c, sizeof c, hipMemcpyHostToDevice));
-        memset(kstat, 0, sizeof kstat);
-        sh_lo = h.lo; sh_hi = h.hi; sh_next = h.next; sh_dup = h.dup;
-        last_distinct = sh_next;
-        have_viol = false;
-        sl[0].launched = sl[1].launched = false;
-        sh_resume = true;
-        sh_ck_ok = false;
+        if (!sh.resume) return MC_OK;
+        if (sh.levels.size() > cap) { set_error("shard_resume: level buffer too small"); return MC_EBADCFG; }
+        for (size_t k = 0; k < sh.levels.size(); k++) levels_out[k] = sh.levels[k];
+        *nlevels = (uint32_t)sh.levels.size();
+        sh.resume = false;
         return MC_OK;
     }
     int shard_info(void **main_stream, uint64_t *chunk_states, int32_t *traced) override {
         HIP_TRY(hipSetDevice(cfg.device));
         if (main_stream) *main_stream = (void *)stream;
         if (chunk_states) *chunk_states = chunk;
-        if (traced) *traced = d_parent != nullptr;
+        if (traced) *traced = d_parent.p != nullptr;
         return MC_OK;
     }
     size_t state_bytes() const override { return (size_t)W * 8; }
-    // Side stream of the sharded path.  By default the engine's own second stream, and every step call returns
-    // with its work finished.  A caller that runs its collectives on a HIP stream hands that stream over with
-    // shard_set_stream: compaction / probe / keep / materialise / ingest are then enqueued on it WITHOUT host
-    // synchronisation (stream order ties them to the caller's all-to-alls), and only the calls that must return
-    // counts to the host wait.
-    hipStream_t ext_stream = nullptr;
-    bool ext_side = false;
-    hipEvent_t ev_slot[2] = {nullptr, nullptr}, ev_keep[2] = {nullptr, nullptr}, ev_ans = nullptr;
-    hipStream_t side() const { return ext_side ? ext_stream : stream2; }
-    // Three kinds of kernels append states at arena_next (the chunk's locally owned new states, keep, ingest) and they run on
-    // different streams: one event chains them, each appender waits for the previous one and records when it is enqueued.
-    hipEvent_t ev_append = nullptr;
-    void append_begin(hipStream_t s) { if (ev_append) hipStreamWaitEvent(s, ev_append, 0); }
-    void append_end(hipStream_t s) {
-        if (!ev_append) hipEventCreateWithFlags(&ev_append, hipEventDisableTiming);
-        hipEventRecord(ev_append, s);
-    }
+    // the side stream of the sharded path (Shard::sh.ext_stream)
+    hipStream_t side() const { return sh.ext_side ? sh.ext_stream : stream2; }
+    void append_begin(hipStream_t s) { if (sh.ev_append.made()) hipStreamWaitEvent(s, sh.ev_append.get(), 0); }  // (Shard::sh.ev_append)
+    void append_end(hipStream_t s) { hipEventRecord(sh.ev_append.get(), s); }
     int side_done() {
-        if (!ext_side) HIP_TRY(hipStreamSynchronize(stream2));
+        if (!sh.ext_side) HIP_TRY(hipStreamSynchronize(stream2));
         return MC_OK;
     }
     int shard_set_stream(void *hip_stream, int enable) override {
         HIP_TRY(hipSetDevice(cfg.device));
         HIP_TRY(hipStreamSynchronize(side()));
-        ext_stream = (hipStream_t)hip_stream;
-        ext_side = enable != 0;
+        sh.ext_stream = (hipStream_t)hip_stream;
+        sh.ext_side = enable != 0;
+        return MC_OK;
+    }
+    // The locally owned new states of the slot's chunk (local-owner shortcut; new-list parity = slot): materialised on the second
+    // stream, in order with the other kernels that append at arena_next (keep, ingest).  The caller has ordered stream2 behind the expand.
+    int materialise_local(unsigned slot) {
+        const ShSlot &q = sh.sl[slot];
+        append_begin(stream2);
+        timed(2, 0, [&] {
+            hipLaunchKernelGGL(k_materialise<S>, dim3(mat_grid(q.ncols), NSHARD), dim3(256), 0, stream2, prm, d_arena, q.chunk_base, d_newlist, seg_cap,
+                               arena_cap, d_parent, d_pslot, d_ctr, slot, (const LevelCtl *)nullptr, (const uint64_t *)d_newfp);
+        }, stream2);
+        hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, stream2, d_ctr, slot);
+        append_end(stream2);
+        HIP_TRY(hipEventRecord(sh.ev_mat[slot].get(), stream2));
         return MC_OK;
     }
     int shard_expand_launch(unsigned slot, uint64_t first, uint64_t count, uint64_t send_cap) override {
         HIP_TRY(hipSetDevice(cfg.device));
         if (slot > 1) { set_error("shard_expand: slot must be 0 or 1"); return MC_EBADCFG; }
-        ShSlot &q = sl[slot];
+        ShSlot &q = sh.sl[slot];
         const unsigned P = nranks();
         int rc = shard_alloc(q, send_cap);
         if (rc) return rc;
@@ -1240,14 +1243,13 @@ struct Engine : EngineBase {
         q.count = count;
         q.launched = true;
         for (unsigned t = 0; t <= 8; t++) q.pend_off.off[t] = 0;
-        if (first + count > sh_hi - sh_lo) { set_error("shard_expand: chunk outside the local frontier"); return MC_EBADCFG; }
+        if (first + count > sh.hi - sh.lo) { set_error("shard_expand: chunk outside the local frontier"); return MC_EBADCFG; }
         if (count > chunk) { set_error("shard_expand: chunk larger than chunk_states"); return MC_EBADCFG; }
         if (!count) return MC_OK;
-        if (!ev_slot[slot]) HIP_TRY(hipEventCreateWithFlags(&ev_slot[slot], hipEventDisableTiming));
-        else HIP_TRY(hipStreamWaitEvent(stream, ev_slot[slot], 0));  // the slot's previous buckets have been compacted
-        if (ev_mat[slot]) HIP_TRY(hipStreamWaitEvent(stream, ev_mat[slot], 0));  // ... and its locally owned new states written
+        if (sh.ev_slot[slot].made()) HIP_TRY(hipStreamWaitEvent(stream, sh.ev_slot[slot].get(), 0));  // the slot's previous buckets have been compacted
+        if (sh.ev_mat[slot].made()) HIP_TRY(hipStreamWaitEvent(stream, sh.ev_mat[slot].get(), 0));  // ... and its locally owned new states written
         HIP_TRY(hipMemsetAsync(q.rt_cur, 0, (size_t)(P * NSHARD) * sizeof(PaddedCounter), stream));
-        const uint64_t c0 = sh_lo + first, c1 = c0 + count, base = c0 & ~63ull;
+        const uint64_t c0 = sh.lo + first, c1 = c0 + count, base = c0 & ~63ull;
         const uint64_t ncols = ((c1 - base) + 63) & ~63ull;
         q.chunk_base = base;
         RouteArgs rt{P, q.rt_cur, q.rt_fp, q.rt_src, q.rt_subcap};
@@ -1256,20 +1258,20 @@ struct Engine : EngineBase {
         q.ncols = ncols;
         timed(0, count, [&] {  // new-list parity = slot: the locally owned new states of this chunk (local-owner shortcut)
             launch_expand<S, true>(!(cfg.flags & MC_F_NOFAMILY), cfg.flags, ncols, stream, 0u, prm,
-                                   (const uint64_t *)d_arena, c0, c1, ncols, d_table, seen_arg(), d_newlist, seg_cap, d_ctr, cfg.flags, rt, slot);
+                                   (const uint64_t *)d_arena, c0, c1, ncols, d_table.p, seen_arg(), d_newlist.p, seg_cap, d_ctr.p, cfg.flags, rt, slot);
         });
         return MC_OK;
     }
     int shard_expand_finish(unsigned slot, uint64_t *send_fp, uint64_t send_cap, uint64_t *send_counts) override {
         HIP_TRY(hipSetDevice(cfg.device));
-        if (slot > 1 || !sl[slot].launched) { set_error("shard_expand_finish: no expand in flight for this slot"); return MC_EBADCFG; }
-        ShSlot &q = sl[slot];
+        if (slot > 1 || !sh.sl[slot].launched) { set_error("shard_expand_finish: no expand in flight for this slot"); return MC_EBADCFG; }
+        ShSlot &q = sh.sl[slot];
         q.launched = false;
         const unsigned P = nranks();
         for (unsigned t = 0; t < P; t++) send_counts[t] = 0;
         if (!q.count) return MC_OK;
         // one wait on the expand stream only: the side stream may still be busy with the previous round
-        PaddedCounter *cur = h_cur;
+        PaddedCounter *cur = sh.h_cur;
         HIP_TRY(hipMemcpyAsync(cur, q.rt_cur, (size_t)(P * NSHARD) * sizeof(PaddedCounter), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipMemcpyAsync(h_ctr, d_ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
@@ -1288,32 +1290,19 @@ struct Engine : EngineBase {
         // (the pending list is as long as the largest send capacity asked for so far: more candidates than it holds is "more successors
         //  per state than the fan-out allowance" — MC_EROUTE, the level loop starts over with twice the allowance — not a full arena)
         if (total >= (1ull << 31)) { set_error("shard_expand: more than 2^31 candidates in one round (lower chunk_states)"); return MC_EARENA; }
-        if (total > q.pend_cap) { set_error("shard_expand: more candidates in one round than the slot's pending list holds (raise the fan-out allowance)"); return MC_EROUTE; }
+        if (total > q.pend_src.n) { set_error("shard_expand: more candidates in one round than the slot's pending list holds (raise the fan-out allowance)"); return MC_EROUTE; }
         if (total > send_cap) { set_error("shard_expand: send buffer too small (raise the fan-out allowance)"); return MC_EROUTE; }
         q.pend_total = total;
         if (q.keep_pending) {  // the slot's previous keep still reads pend_src
-            HIP_TRY(hipStreamWaitEvent(side(), ev_keep[slot], 0));
+            HIP_TRY(hipStreamWaitEvent(side(), sh.ev_keep[slot].get(), 0));
             q.keep_pending = false;
         }
-        {   // the chunk's locally owned new states (local-owner shortcut): materialised on the side stream, in order with the
-            // other kernels that append at arena_next (keep, ingest); the expand kernel has finished (stream was synchronised)
-            const unsigned bx = (unsigned)((q.ncols + 255) / 256);
-            const unsigned gm = bx < 8 * 256 ? (bx + 7) / 8 : 256;
-            append_begin(stream2);
-            timed(2, 0, [&] {
-                hipLaunchKernelGGL(k_materialise<S>, dim3(gm ? gm : 1, NSHARD), dim3(256), 0, stream2, prm, d_arena, q.chunk_base, d_newlist, seg_cap,
-                                   arena_cap, d_parent, d_pslot, d_ctr, slot, (const LevelCtl *)nullptr, (const uint64_t *)d_newfp);
-            }, stream2);
-            hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, stream2, d_ctr, slot);
-            append_end(stream2);
-            if (!ev_mat[slot]) HIP_TRY(hipEventCreateWithFlags(&ev_mat[slot], hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(ev_mat[slot], stream2));
-        }
+        if ((rc = materialise_local(slot))) return rc;  // (the expand kernel has finished: stream was synchronised)
         if (total) {
             RouteArgs rt{P, q.rt_cur, q.rt_fp, q.rt_src, q.rt_subcap};
             hipLaunchKernelGGL(k_compact_buckets, dim3(64, P * NSHARD), dim3(256), 0, side(), rt, send_fp, q.pend_src);
         }
-        HIP_TRY(hipEventRecord(ev_slot[slot], side()));
+        HIP_TRY(hipEventRecord(sh.ev_slot[slot].get(), side()));
         return side_done();
     }
     int shard_probe(const uint64_t *recv_fp, uint64_t n, uint8_t *answers) override {
@@ -1325,50 +1314,35 @@ struct Engine : EngineBase {
         return side_done();
     }
     // ---- fixed-capacity rounds: nothing of a round waits for the host (sizes travel in band; errors surface at shard_end_level)
-    hipEvent_t ev_exp[2] = {nullptr, nullptr};
-    // the slot's new-list segment and its counters (parity = slot) are read by the local materialise + commit on the second
-    // stream: the NEXT expand into the same slot waits for them (a host that never blocks enqueues expands back to back)
-    hipEvent_t ev_mat[2] = {nullptr, nullptr};
     int shard_expand_pack(unsigned slot, uint64_t *send_fp, uint64_t cap) override {
         HIP_TRY(hipSetDevice(cfg.device));
-        if (slot > 1 || !sl[slot].launched) { set_error("shard_expand_pack: no expand in flight for this slot"); return MC_EBADCFG; }
-        ShSlot &q = sl[slot];
+        if (slot > 1 || !sh.sl[slot].launched) { set_error("shard_expand_pack: no expand in flight for this slot"); return MC_EBADCFG; }
+        ShSlot &q = sh.sl[slot];
         q.launched = false;
         const unsigned P = nranks();
-        if (cap < 2 || (uint64_t)P * cap > q.pend_cap || (uint64_t)P * cap >= (1ull << 31)) { set_error("shard_expand_pack: capacity does not fit the slot's buffers"); return MC_EBADCFG; }
+        if (cap < 2 || (uint64_t)P * cap > q.pend_src.n || (uint64_t)P * cap >= (1ull << 31)) { set_error("shard_expand_pack: capacity does not fit the slot's buffers"); return MC_EBADCFG; }
         q.pend_total = (uint64_t)P * cap;  // the sender scans the whole packed range: answers outside the counts are 0
         for (unsigned t = 0; t <= 8; t++) q.pend_off.off[t] = (t < P ? t : P) * cap;
-        if (!ev_exp[slot]) HIP_TRY(hipEventCreateWithFlags(&ev_exp[slot], hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(ev_exp[slot], stream));  // behind the slot's expand kernel (or behind nothing: an empty chunk)
+        HIP_TRY(hipEventRecord(sh.ev_exp[slot].get(), stream));  // behind the slot's expand kernel (or behind nothing: an empty chunk)
         // The buckets are compacted on the EXPAND stream, right behind the kernel that filled them: on the side stream the
         // compaction of round r+1 would queue behind the probes of round r (or those behind it), and the fingerprint exchange of
         // round r+1 could never overlap them.  The caller orders its collective behind this call with an event on that stream
         // (mc_shard_info hands it out).
         if (q.keep_pending) {  // the slot's previous keep still reads pend_src
-            HIP_TRY(hipStreamWaitEvent(stream, ev_keep[slot], 0));
+            HIP_TRY(hipStreamWaitEvent(stream, sh.ev_keep[slot].get(), 0));
             q.keep_pending = false;
         }
         if (q.count) {  // the chunk's locally owned new states (local-owner shortcut), as in shard_expand_finish
-            const unsigned bx = (unsigned)((q.ncols + 255) / 256);
-            const unsigned gm = bx < 8 * 256 ? (bx + 7) / 8 : 256;
-            HIP_TRY(hipStreamWaitEvent(stream2, ev_exp[slot], 0));
-            append_begin(stream2);
-            timed(2, 0, [&] {
-                hipLaunchKernelGGL(k_materialise<S>, dim3(gm ? gm : 1, NSHARD), dim3(256), 0, stream2, prm, d_arena, q.chunk_base, d_newlist, seg_cap,
-                                   arena_cap, d_parent, d_pslot, d_ctr, slot, (const LevelCtl *)nullptr, (const uint64_t *)d_newfp);
-            }, stream2);
-            hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, stream2, d_ctr, slot);
-            append_end(stream2);
-            if (!ev_mat[slot]) HIP_TRY(hipEventCreateWithFlags(&ev_mat[slot], hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(ev_mat[slot], stream2));
+            HIP_TRY(hipStreamWaitEvent(stream2, sh.ev_exp[slot].get(), 0));
+            const int rc = materialise_local(slot);
+            if (rc) return rc;
             RouteArgs rt{P, q.rt_cur, q.rt_fp, q.rt_src, q.rt_subcap};
             hipLaunchKernelGGL(k_compact_packed, dim3(64, P * NSHARD), dim3(256), 0, stream, rt, cap, send_fp, q.pend_src, d_ctr);
         } else {  // no chunk for this rank in this round: empty buckets
             for (unsigned t = 0; t < P; t++) HIP_TRY(hipMemsetAsync(send_fp + (uint64_t)t * cap, 0, sizeof(uint64_t), stream));
         }
-        if (!ev_slot[slot]) HIP_TRY(hipEventCreateWithFlags(&ev_slot[slot], hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(ev_slot[slot], stream));
-        if (!ext_side) HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipEventRecord(sh.ev_slot[slot].get(), stream));
+        if (!sh.ext_side) HIP_TRY(hipStreamSynchronize(stream));
         return side_done();
     }
     int shard_probe_pack(const uint64_t *recv_fp, uint64_t cap, uint8_t *answers) override {
@@ -1382,7 +1356,7 @@ struct Engine : EngineBase {
         return side_done();
     }
     int shard_keep_pack(unsigned slot, const uint8_t *answers_back, uint64_t cap) override {
-        if (slot > 1 || sl[slot].pend_total != (uint64_t)nranks() * cap) { set_error("shard_keep_pack: not the capacity the slot was packed with"); return MC_EBADCFG; }
+        if (slot > 1 || sh.sl[slot].pend_total != (uint64_t)nranks() * cap) { set_error("shard_keep_pack: not the capacity the slot was packed with"); return MC_EBADCFG; }
         return shard_keep(slot, answers_back, nullptr);
     }
     // the caller's stream waits (on the device) until the slot's last keep has consumed its answers buffer: a caller that
@@ -1390,13 +1364,13 @@ struct Engine : EngineBase {
     int shard_wait_keep(unsigned slot) override {
         if (slot > 1) return MC_EBADCFG;
         HIP_TRY(hipSetDevice(cfg.device));
-        if (sl[slot].keep_pending && ev_keep[slot]) HIP_TRY(hipStreamWaitEvent(side(), ev_keep[slot], 0));
+        if (sh.sl[slot].keep_pending) HIP_TRY(hipStreamWaitEvent(side(), sh.ev_keep[slot].get(), 0));  // (pending: the event has been recorded)
         return MC_OK;
     }
     int shard_materialise(unsigned slot, const uint8_t *answers_back, uint8_t *send_states, uint64_t send_cap, uint64_t *send_counts) override {
         HIP_TRY(hipSetDevice(cfg.device));
         if (slot > 1) return MC_EBADCFG;
-        ShSlot &q = sl[slot];
+        ShSlot &q = sh.sl[slot];
         const unsigned P = nranks();
         for (unsigned t = 0; t < P; t++) send_counts[t] = 0;
         q.moved = 0;
@@ -1404,9 +1378,9 @@ struct Engine : EngineBase {
         const unsigned bx = (unsigned)((q.pend_total + 255) / 256);
         int rc = scan_answers(answers_back, q.pend_total, side());
         if (rc) return rc;
-        hipLaunchKernelGGL(k_gather_range_ends, dim3(1), dim3(64), 0, side(), d_incl, q.pend_off, P, d_ends);
-        unsigned long long *ends = h_ends;  // the per-owner counts go back to the host: the caller sizes its all-to-all with them
-        HIP_TRY(hipMemcpyAsync(ends, d_ends, P * sizeof(unsigned long long), hipMemcpyDeviceToHost, side()));
+        hipLaunchKernelGGL(k_gather_range_ends, dim3(1), dim3(64), 0, side(), sh.d_incl, q.pend_off, P, sh.d_ends);
+        unsigned long long *ends = sh.h_ends;  // the per-owner counts go back to the host: the caller sizes its all-to-all with them
+        HIP_TRY(hipMemcpyAsync(ends, sh.d_ends, P * sizeof(unsigned long long), hipMemcpyDeviceToHost, side()));
         HIP_TRY(hipStreamSynchronize(side()));
         OwnerOffsets start;
         std::vector<PaddedCounter> cnt(P);
@@ -1415,8 +1389,8 @@ struct Engine : EngineBase {
             start.off[t] = t ? ends[t - 1] : 0;
             cnt[t].v = ends[t] - start.off[t];
         }
-        hipLaunchKernelGGL(k_compact_new, dim3(bx), dim3(256), 0, side(), answers_back, d_incl, q.pend_src, q.pend_total, q.pend_off, start, P,
-                           d_new_src);
+        hipLaunchKernelGGL(k_compact_new, dim3(bx), dim3(256), 0, side(), answers_back, sh.d_incl, q.pend_src, q.pend_total, q.pend_off, start, P,
+                           sh.d_new_src);
         BlockPlan plan;
         uint64_t blocks = 0;
         for (unsigned t = 0; t < 8; t++) {
@@ -1433,7 +1407,7 @@ struct Engine : EngineBase {
         if (blocks) {
             timed(2, blocks * 64, [&] {
                 hipLaunchKernelGGL(k_send_materialise<S>, dim3((unsigned)((blocks * 64 + 255) / 256)), dim3(256), 0, side(), prm, d_arena,
-                                   q.chunk_base, d_new_src, q.pend_off, plan, P, (uint64_t *)send_states);
+                                   q.chunk_base, sh.d_new_src, q.pend_off, plan, P, (uint64_t *)send_states);
             }, side());
         }
         return side_done();
@@ -1444,35 +1418,33 @@ struct Engine : EngineBase {
         HIP_TRY(hipSetDevice(cfg.device));
         if (n_new) *n_new = 0;
         if (slot > 1) return MC_EBADCFG;
-        ShSlot &q = sl[slot];
+        ShSlot &q = sh.sl[slot];
         if (!q.pend_total) return MC_OK;
         const unsigned bx = (unsigned)((q.pend_total + 255) / 256);
         // keep runs on the engine's own second stream, behind the caller's stream at this point (the answers
         // are ready there), so the caller's next exchange does not queue behind the materialisation
         hipStream_t ks = stream2;
-        if (ext_side) {
-            if (!ev_ans) HIP_TRY(hipEventCreateWithFlags(&ev_ans, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(ev_ans, ext_stream));
-            HIP_TRY(hipStreamWaitEvent(ks, ev_ans, 0));
+        if (sh.ext_side) {
+            HIP_TRY(hipEventRecord(sh.ev_ans.get(), sh.ext_stream));
+            HIP_TRY(hipStreamWaitEvent(ks, sh.ev_ans.get(), 0));
         }
         int rc = scan_answers(answers_back, q.pend_total, ks);
         if (rc) return rc;
         append_begin(ks);
-        const uint32_t *d_total = d_incl + (q.pend_total - 1);
+        const uint32_t *d_total = sh.d_incl + (q.pend_total - 1);
         OwnerOffsets one, zero;  // a single range covering every pending candidate
         for (unsigned t = 0; t <= 8; t++) { one.off[t] = t ? q.pend_total : 0; zero.off[t] = 0; }
-        hipLaunchKernelGGL(k_compact_new, dim3(bx), dim3(256), 0, ks, answers_back, d_incl, q.pend_src, q.pend_total, one, zero, 1u, d_new_src);
+        hipLaunchKernelGGL(k_compact_new, dim3(bx), dim3(256), 0, ks, answers_back, sh.d_incl, q.pend_src, q.pend_total, one, zero, 1u, sh.d_new_src);
         // grid sized for the upper bound (every candidate new); surplus threads leave at once
         timed(2, 0, [&] {
-            hipLaunchKernelGGL(k_materialise_list<S>, dim3(bx), dim3(256), 0, ks, prm, d_arena, q.chunk_base, d_new_src, d_total, arena_cap,
+            hipLaunchKernelGGL(k_materialise_list<S>, dim3(bx), dim3(256), 0, ks, prm, d_arena, q.chunk_base, sh.d_new_src, d_total, arena_cap,
                                d_parent, d_pslot, d_ctr);
         }, ks);
         hipLaunchKernelGGL(k_bump_arena_next, dim3(1), dim3(1), 0, ks, d_ctr, d_total, 0ull, (unsigned long long)arena_cap);
         append_end(ks);
-        if (!ev_keep[slot]) HIP_TRY(hipEventCreateWithFlags(&ev_keep[slot], hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(ev_keep[slot], ks));
+        HIP_TRY(hipEventRecord(sh.ev_keep[slot].get(), ks));
         q.keep_pending = true;
-        if (!ext_side) {
+        if (!sh.ext_side) {
             uint32_t total32 = 0;
             HIP_TRY(hipMemcpyAsync(&total32, d_total, sizeof total32, hipMemcpyDeviceToHost, ks));
             HIP_TRY(hipStreamSynchronize(ks));
@@ -1498,9 +1470,9 @@ struct Engine : EngineBase {
     int shard_materialise_parents(unsigned slot, uint64_t *send_parents) override {
         HIP_TRY(hipSetDevice(cfg.device));
         if (slot > 1) return MC_EBADCFG;
-        ShSlot &q = sl[slot];
+        ShSlot &q = sh.sl[slot];
         if (!q.moved) return MC_OK;
-        hipLaunchKernelGGL(k_send_parents, dim3((unsigned)((q.moved + 255) / 256)), dim3(256), 0, side(), (const uint32_t *)d_new_src, q.chunk_base,
+        hipLaunchKernelGGL(k_send_parents, dim3((unsigned)((q.moved + 255) / 256)), dim3(256), 0, side(), (const uint32_t *)sh.d_new_src, q.chunk_base,
                            q.pend_off, q.plan, nranks(), send_parents);
         return side_done();
     }
@@ -1520,12 +1492,11 @@ struct Engine : EngineBase {
         *found = h_ctr->viol_key != ~0ull;
         *idx = 0; *slot = 0; *verdict = MC_V_OK; *invariant = -1;
         if (*found) {
-            const unsigned long long k = h_ctr->viol_key;
-            const unsigned kind = (unsigned)(k & 7u);
-            *idx = viol_idx(k);
-            *slot = (uint32_t)(k >> 8 & 0xffffu);
-            *verdict = kind == VK_INVARIANT ? MC_V_INVARIANT : kind == VK_ASSERT ? MC_V_ASSERT : kind == VK_DEADLOCK ? MC_V_DEADLOCK : MC_V_SPECERR;
-            if (kind == VK_INVARIANT) *invariant = (int32_t)(k >> 3 & 31u);
+            const Viol v(h_ctr->viol_key);
+            *idx = viol_idx(h_ctr->viol_key);
+            *slot = v.slot;
+            *verdict = v.verdict;
+            *invariant = v.invariant;
         }
         return MC_OK;
     }
@@ -1561,17 +1532,17 @@ struct Engine : EngineBase {
     }
     int shard_end_level(uint64_t *new_local) override {
         HIP_TRY(hipSetDevice(cfg.device));
-        if (sl[0].launched || sl[1].launched) { set_error("shard_end_level: an expand is still in flight"); return MC_EBADCFG; }
+        if (sh.sl[0].launched || sh.sl[1].launched) { set_error("shard_end_level: an expand is still in flight"); return MC_EBADCFG; }
         HIP_TRY(hipStreamSynchronize(side()));
         HIP_TRY(hipStreamSynchronize(stream2));
         int rc = read_counters();
         if (rc) return rc;
         if ((rc = check_dev_error())) return rc;
-        sh_next = h_ctr->arena_next;
-        last_distinct = sh_next;
-        sh_lo = sh_hi;
-        sh_hi = sh_next;
-        *new_local = sh_hi - sh_lo;
+        sh.next = h_ctr->arena_next;
+        fr.last_distinct = sh.next;
+        sh.lo = sh.hi;
+        sh.hi = sh.next;
+        *new_local = sh.hi - sh.lo;
         return MC_OK;
     }
     // invariants of the unexpanded frontier [lo, hi) for specs that check on expansion (see k_check_frontier); no-op otherwise
@@ -1589,7 +1560,7 @@ struct Engine : EngineBase {
         HIP_TRY(hipSetDevice(cfg.device));
         HIP_TRY(hipStreamSynchronize(side()));
         HIP_TRY(hipStreamSynchronize(stream2));
-        return check_frontier(sh_lo, sh_hi);
+        return check_frontier(sh.lo, sh.hi);
     }
     int shard_counters(uint64_t *generated, uint64_t *distinct_local, int32_t *verdict) override {
         HIP_TRY(hipSetDevice(cfg.device));
@@ -1599,12 +1570,8 @@ struct Engine : EngineBase {
         if ((rc = check_dev_error())) return rc;
         *generated = 0;
         for (int t = 0; t < NSHARD; t++) *generated += h_ctr->generated[t].v;
-        *distinct_local = h_ctr->arena_next - sh_dup;
-        *verdict = MC_V_OK;
-        if (h_ctr->viol_key != ~0ull) {
-            const unsigned kind = (unsigned)(h_ctr->viol_key & 7u);
-            *verdict = kind == VK_INVARIANT ? MC_V_INVARIANT : kind == VK_ASSERT ? MC_V_ASSERT : kind == VK_DEADLOCK ? MC_V_DEADLOCK : MC_V_SPECERR;
-        }
+        *distinct_local = h_ctr->arena_next - sh.dup;
+        *verdict = h_ctr->viol_key != ~0ull ? Viol(h_ctr->viol_key).verdict : MC_V_OK;
         return MC_OK;
     }
     // ------------------------------------------------------------------------------- simulation (mc_engine_simulate; engine_sim.h)
@@ -1614,46 +1581,20 @@ struct Engine : EngineBase {
     static constexpr uint64_t SIM_ROUND = 1ull << 18;
     static constexpr uint32_t SIM_ITERS = 16;
     static constexpr uint64_t SIM_MAX_WALKS = 1ull << 40;   // walk indices of a run (the walk field of a violation key, sim_walk.h)
-    uint64_t *d_sim_buf[2] = {nullptr, nullptr};
-    uint32_t *d_sim_wst = nullptr;
-    SimCounters *d_sim_ctr = nullptr;
-    uint64_t sim_cap = 0;
-    std::vector<uint64_t> sim_trace_rows;  // the counterexample of the last simulation (rows in S's layout) and its action ids
-    std::vector<int32_t> sim_trace_acts;
-    size_t sim_trace_n = 0;
-    void sim_free() {
-        for (auto &b : d_sim_buf) { if (b) hipFree(b); b = nullptr; }
-        if (d_sim_wst) hipFree(d_sim_wst);
-        if (d_sim_ctr) hipFree(d_sim_ctr);
-        d_sim_wst = nullptr;
-        d_sim_ctr = nullptr;
-        sim_cap = 0;
-    }
-    int sim_alloc(uint64_t lanes) {
-        lanes = (lanes + 63) & ~63ull;
-        if (sim_cap >= lanes) return MC_OK;
-        sim_free();
-        HIP_TRY(hipMalloc(&d_sim_buf[0], lanes * W * sizeof(uint64_t)));
-        HIP_TRY(hipMalloc(&d_sim_buf[1], lanes * W * sizeof(uint64_t)));
-        HIP_TRY(hipMalloc(&d_sim_wst, lanes * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&d_sim_ctr, sizeof(SimCounters)));
-        sim_cap = lanes;
-        return MC_OK;
-    }
-    // one round: walks w0 .. w0+n-1 from their start to their end (or to a stop request); the counters accumulate in d_sim_ctr.
+    // one round: walks w0 .. w0+n-1 from their start to their end (or to a stop request); the counters accumulate in sim.ctr.
     // *complete: every walk of the round ended.  Progress is reported (and a stop request seen) after EVERY launch, the round's last
     // one included: a model whose walks all end within one launch must not run an unbounded simulation past mc_engine_request_stop.
     int sim_round(SimArgs a, uint64_t n, SimCounters &c, uint64_t walks_before, bool allow_stop, uint64_t rounds_done, bool *complete) {
         a.n = n;
         a.ncols = (n + 63) & ~63ull;
         *complete = false;
-        HIP_TRY(hipMemsetAsync(d_sim_wst, 0, n * sizeof(uint32_t), stream));
+        HIP_TRY(hipMemsetAsync(sim.wst, 0, n * sizeof(uint32_t), stream));
         const unsigned blocks = (unsigned)((a.ncols + 255) / 256);
         const uint64_t launches = ((uint64_t)a.depth + 1 + SIM_ITERS - 1) / SIM_ITERS;  // depth + 1 events end every walk
         for (uint64_t l = 0; l < launches; ++l) {
             hipLaunchKernelGGL(k_simulate<S>, dim3(blocks), dim3(256), 0, stream, prm, a);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&c, d_sim_ctr, sizeof c, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(&c, sim.ctr, sizeof c, hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipStreamSynchronize(stream));
             if (c.error) break;
             if (allow_stop) report_progress((uint32_t)rounds_done, c.generated, c.steps, c.walks);
@@ -1672,41 +1613,42 @@ struct Engine : EngineBase {
         if (o->num > SIM_MAX_WALKS) { set_error("simulate: at most 2^40 walks"); return MC_EBADCFG; }
         if (cfg.shard_count > 1) { set_error("simulate: not available for a sharded engine"); return MC_EBADCFG; }
         // the BFS's resident search is no longer continued by mc_engine_step, nor checkpointed
-        have_run = have_viol = false;
-        ck_pending = ck_in_place = false;
+        fr.have_run = fr.have_viol = false;
+        ck.pending = ck.in_place = false;
         stop_requested = false;
-        sim_trace_n = 0;
-        sim_trace_rows.clear();
-        sim_trace_acts.clear();
+        sim.trace_n = 0;
+        sim.trace_rows.clear();
+        sim.trace_acts.clear();
         HIP_TRY(hipSetDevice(cfg.device));
-        const uint64_t lanes = o->num && o->num < SIM_ROUND ? o->num : SIM_ROUND;
-        int rc = sim_alloc(lanes);
-        if (rc) return rc;
+        const uint64_t lanes = ((o->num && o->num < SIM_ROUND ? o->num : SIM_ROUND) + 63) & ~63ull;
+        HIP_TRY(sim.buf[0].reserve(lanes * W));
+        HIP_TRY(sim.buf[1].reserve(lanes * W));
+        HIP_TRY(sim.wst.reserve(lanes));
+        HIP_TRY(sim.ctr.reserve(1));
+        int rc;
         const uint64_t K = o->record;
-        int32_t *d_rslots = nullptr;
-        uint32_t *d_rlen = nullptr;
-        struct Freer { std::vector<void *> p; ~Freer() { for (void *q : p) hipFree(q); } } freer;
+        DevBuf<int32_t> d_rslots, d_tslots;  // the recorded walks' slots (K walks) / the counterexample's (one walk)
+        DevBuf<uint32_t> d_rlen, d_tlen;
+        DevBuf<uint64_t> d_rows;
         if (K) {
-            HIP_TRY(hipMalloc(&d_rslots, K * o->depth * sizeof(int32_t)));
-            freer.p.push_back(d_rslots);
-            HIP_TRY(hipMalloc(&d_rlen, 2 * K * sizeof(uint32_t)));
-            freer.p.push_back(d_rlen);
+            HIP_TRY(d_rslots.alloc(K * o->depth));
+            HIP_TRY(d_rlen.alloc(2 * K));
             HIP_TRY(hipMemsetAsync(d_rslots, 0xff, K * o->depth * sizeof(int32_t), stream));
             HIP_TRY(hipMemsetAsync(d_rlen, 0, 2 * K * sizeof(uint32_t), stream));
         }
         SimCounters c;
         memset(&c, 0, sizeof c);
         c.viol = ~0ull;
-        HIP_TRY(hipMemcpyAsync(d_sim_ctr, &c, sizeof c, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(sim.ctr, &c, sizeof c, hipMemcpyHostToDevice, stream));
         SimArgs a{};
         a.seed = o->seed;
-        a.buf0 = d_sim_buf[0];
-        a.buf1 = d_sim_buf[1];
-        a.wst = d_sim_wst;
+        a.buf0 = sim.buf[0];
+        a.buf1 = sim.buf[1];
+        a.wst = sim.wst;
         a.depth = o->depth;
         a.iters = SIM_ITERS;
         a.deadlock = (cfg.flags & MC_F_DEADLOCK) ? 1u : 0u;
-        a.ctr = d_sim_ctr;
+        a.ctr = sim.ctr;
         a.rec_first = 0;
         a.rec_count = K;
         a.rec_slots = d_rslots;
@@ -1744,24 +1686,18 @@ struct Engine : EngineBase {
         if (c.viol == ~0ull) return MC_OK;
         const unsigned long long key = c.viol;
         const unsigned kind = sim_key_kind(key), vslot = sim_key_slot(key);
-        out->verdict = kind == SIM_VK_INVARIANT ? MC_V_INVARIANT : kind == SIM_VK_ASSERT ? MC_V_ASSERT : kind == SIM_VK_DEADLOCK ? MC_V_DEADLOCK : MC_V_SPECERR;
+        out->verdict = verdict_of_kind(kind);
         if (kind == SIM_VK_INVARIANT) out->violated_invariant = (int)sim_key_inv(key);
         out->violating_walk = sim_key_walk(key);
         // the counterexample: walk w once more, alone, in record mode (nothing was kept per walk in the run itself)
-        int32_t *d_tslots = nullptr;
-        uint32_t *d_tlen = nullptr;
-        uint64_t *d_rows = nullptr;
-        HIP_TRY(hipMalloc(&d_tslots, (size_t)o->depth * sizeof(int32_t)));
-        freer.p.push_back(d_tslots);
-        HIP_TRY(hipMalloc(&d_tlen, 2 * sizeof(uint32_t)));
-        freer.p.push_back(d_tlen);
-        HIP_TRY(hipMalloc(&d_rows, ((size_t)o->depth + 1) * W * sizeof(uint64_t)));
-        freer.p.push_back(d_rows);
+        HIP_TRY(d_tslots.alloc((size_t)o->depth));
+        HIP_TRY(d_tlen.alloc(2));
+        HIP_TRY(d_rows.alloc(((size_t)o->depth + 1) * W));
         HIP_TRY(hipMemsetAsync(d_tslots, 0xff, (size_t)o->depth * sizeof(int32_t), stream));
         SimCounters c2;
         memset(&c2, 0, sizeof c2);
         c2.viol = ~0ull;
-        HIP_TRY(hipMemcpyAsync(d_sim_ctr, &c2, sizeof c2, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(sim.ctr, &c2, sizeof c2, hipMemcpyHostToDevice, stream));
         a.w0 = out->violating_walk;
         a.rec_first = out->violating_walk;
         a.rec_count = 1;
@@ -1777,24 +1713,24 @@ struct Engine : EngineBase {
         const bool extra = kind == SIM_VK_INVARIANT && vslot < SIM_SLOT_PARENT;
         const size_t n = len + (extra ? 1u : 0u);
         std::vector<int32_t> slots(len > 1 ? len - 1 : 1);
-        sim_trace_rows.resize(n * W);
-        HIP_TRY(hipMemcpy(sim_trace_rows.data(), d_rows, n * W * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        sim.trace_rows.resize(n * W);
+        HIP_TRY(hipMemcpy(sim.trace_rows.data(), d_rows, n * W * sizeof(uint64_t), hipMemcpyDeviceToHost));
         if (len > 1) HIP_TRY(hipMemcpy(slots.data(), d_tslots, (len - 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
-        sim_trace_acts.assign(1, -1);
-        for (size_t k = 1; k < len; ++k) sim_trace_acts.push_back(S::action_of(prm, &sim_trace_rows[(k - 1) * W], slots[k - 1]));
-        if (extra) sim_trace_acts.push_back(S::action_of(prm, &sim_trace_rows[(size_t)(len - 1) * W], (int)vslot));
-        sim_trace_n = n;
+        sim.trace_acts.assign(1, -1);
+        for (size_t k = 1; k < len; ++k) sim.trace_acts.push_back(S::action_of(prm, &sim.trace_rows[(k - 1) * W], slots[k - 1]));
+        if (extra) sim.trace_acts.push_back(S::action_of(prm, &sim.trace_rows[(size_t)(len - 1) * W], (int)vslot));
+        sim.trace_n = n;
         out->trace_len = (uint32_t)n;
         return MC_OK;
     }
     int sim_trace_out(uint8_t *states_out, int32_t *actions_out, size_t *n_inout) {
-        const size_t n = sim_trace_n;
+        const size_t n = sim.trace_n;
         if (n > *n_inout) { *n_inout = n; set_error("trace buffer too small"); return MC_EBADCFG; }
         if constexpr (HasExport<S>::value) {  // rows leave the engine in the spec's PUBLIC layout, as the BFS's traces do
-            for (size_t k = 0; k < n; ++k) S::export_row(prm, &sim_trace_rows[k * W], (uint64_t *)states_out + k * (size_t)S::EXPORT_WORDS);
+            for (size_t k = 0; k < n; ++k) S::export_row(prm, &sim.trace_rows[k * W], (uint64_t *)states_out + k * (size_t)S::EXPORT_WORDS);
         } else
-        memcpy(states_out, sim_trace_rows.data(), n * W * sizeof(uint64_t));
-        memcpy(actions_out, sim_trace_acts.data(), n * sizeof(int32_t));
+        memcpy(states_out, sim.trace_rows.data(), n * W * sizeof(uint64_t));
+        memcpy(actions_out, sim.trace_acts.data(), n * sizeof(int32_t));
         *n_inout = n;
         return MC_OK;
     }
@@ -1803,8 +1739,8 @@ struct Engine : EngineBase {
         o->insert = kstat[1];
         o->materialise = kstat[2];
         o->state_bytes = (uint64_t)W * 8;
-        o->cand_cells = kstat_cells;
-        o->inwave_states = kstat_inwave;
+        o->cand_cells = fr.cells;
+        o->inwave_states = fr.inwave;
         return MC_OK;
     }
 };
@@ -1895,8 +1831,8 @@ int mc_make_engine_6(const mc_spec_desc *d, const mc_config *c, mc::EngineBase *
     mc::VmParams p;
     if (mc::vm_make_params(d->params, d->nparams, p)) return MC_EBADCFG;
     if (hipSetDevice(c->device) != hipSuccess) { mc::set_error("hipSetDevice failed"); return MC_EHIP; }
-    int32_t *d_code = nullptr;
-    if (hipMalloc(&d_code, (size_t)p.code_len * sizeof(int32_t)) != hipSuccess ||
+    mc::DevBuf<int32_t> d_code;
+    if (d_code.alloc((size_t)p.code_len) != hipSuccess ||
         hipMemcpy(d_code, p.code, (size_t)p.code_len * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
         mc::set_error("cannot upload the PlusCal program image");
         return MC_EHIP;
@@ -1912,8 +1848,7 @@ int mc_make_engine_6(const mc_spec_desc *d, const mc_config *c, mc::EngineBase *
     const int rc = p.nv <= 16 ? mc::make_engine<mc::SpecVm16>(p, d, c, out)
                  : p.nv <= 32 ? mc::make_engine<mc::SpecVm32>(p, d, c, out)
                  : p.nv <= 64 ? mc::make_engine<mc::SpecVm64>(p, d, c, out) : mc::make_engine<mc::SpecVm>(p, d, c, out);
-    if (rc) hipFree(d_code);
-    else { (*out)->owned_device_blob = d_code; (*out)->program_hash = ph ? ph : 1; }
+    if (!rc) { (*out)->owned_device_blob = std::move(d_code); (*out)->program_hash = ph ? ph : 1; }
     return rc;
 }
 #endif
