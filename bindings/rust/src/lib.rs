@@ -16,6 +16,7 @@ pub const MC_F_GENERIC: u32 = 128;
 pub const MC_F_DEADLOCK: u32 = 1;
 pub const MC_F_TRACE: u32 = 2;
 pub const MC_F_JIT: u32 = 262144; // MC_SPEC_PCAL: the compiled program as generated code, built for the device when the engine is created
+pub const MC_F_COVERAGE: u32 = 16777216; // TLC's -coverage: per-action counts (mc_engine_coverage); implies MC_F_TRACE, one-GPU engines only
 pub const MC_MAX_LEVELS: usize = 4096;
 
 #[repr(C)]
@@ -49,6 +50,9 @@ pub struct mc_sim_result {
     pub walks: u64, pub steps: u64, pub generated: u64, pub violating_walk: u64, pub max_depth: u32, pub verdict: i32,
     pub violated_invariant: i32, pub trace_len: u32, pub seconds: f64,
 }
+// one entry of mc_engine_coverage: action id (-1 = Init), the states it was first to find, the successors it generated
+#[repr(C)]
+pub struct mc_action_coverage { pub action: i32, pub pad: u32, pub distinct: u64, pub generated: u64 }
 #[repr(C)]
 pub struct mc_engine { _private: [u8; 0] }
 #[repr(C)]
@@ -61,6 +65,8 @@ extern "C" {
     pub fn mc_engine_request_stop(e: *mut mc_engine) -> c_int;
     pub fn mc_engine_simulate(e: *mut mc_engine, opts: *const mc_sim_opts, out: *mut mc_sim_result) -> c_int;
     pub fn mc_engine_trace(e: *mut mc_engine, states: *mut u8, actions: *mut i32, n_inout: *mut usize) -> c_int;
+    // entries for Init and every action of the model, in action-id order; *n_inout: capacity in, count out
+    pub fn mc_engine_coverage(e: *mut mc_engine, out: *mut mc_action_coverage, n_inout: *mut usize) -> c_int;
     pub fn mc_engine_read_states(e: *mut mc_engine, first: u64, count: u64, out: *mut u8) -> c_int;
     // TLC's checkpoint / -recover (testout1:10): write / reload the states found so far; the next run continues
     pub fn mc_engine_checkpoint(e: *mut mc_engine, path: *const c_char) -> c_int;

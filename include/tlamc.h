@@ -116,6 +116,10 @@ typedef struct {
                             interpreter and says so on stderr */
 #define MC_F_GENERIC 128u /* mc_check_files: run a PlusCal module through the compiled program (MC_SPEC_PCAL) even
                              when a hand lowering of its algorithm exists (A/B of the two paths)  */
+#define MC_F_COVERAGE 16777216u /* TLC's -coverage: count, per action of the model, the successors it generated and the distinct states it
+                             was first to find (mc_engine_coverage below; mc_check_files appends "The coverage statistics" to its
+                             report).  Implies MC_F_TRACE.  One-GPU engines only: mc_engine_create refuses it with shard_count > 1.
+                             (Bits 19 - 23 are the kernels' own: engine_kernels.h.)  Without it nothing is launched or allocated for it. */
 
 typedef struct {
     int32_t device;          /* HIP device ordinal                                              */
@@ -190,6 +194,31 @@ int mc_engine_request_stop(mc_engine *e);
  * the initial state).  *n_inout: capacity in, count out. */
 int mc_engine_trace(mc_engine *e, uint8_t *states_out, int32_t *actions_out, size_t *n_inout);
 int mc_engine_kernel_stats(mc_engine *e, mc_kernel_stats *out);
+
+/* ------------------------------------------------------------------ coverage (TLC's `-coverage`)
+ * "Did every action of my spec ever fire?"  An engine created with MC_F_COVERAGE counts, while it searches (breadth-first search
+ * only: mc_engine_run / mc_engine_step), per action id of the model (mc_action_name) and for Init (action id -1):
+ *   generated[a]  the successors counted in mc_result.generated that action a produced: every (expanded state, slot) pair whose
+ *                 evaluation is enabled — a failed Assert, an evaluation error, an out-of-model successor and a self loop count too,
+ *                 exactly as they count in mc_result.generated.  generated[Init] = the initial states generated.  The sum over the
+ *                 entries is mc_result.generated.
+ *   distinct[a]   the stored states whose recorded (parent, slot) is action a, i.e. the states a was FIRST to find;
+ *                 distinct[Init] = the stored initial states.  The sum is mc_result.distinct.  When two actions reach the same new
+ *                 state within one level, which of them is credited is the engine's race (as it is TLC's with several workers):
+ *                 generated[] is a function of the model, distinct[] only between bounds (DESIGN.md "Coverage").
+ * The levels covered are exactly the levels the search expanded: counting stops where the search stops (max_levels / max_distinct,
+ * or the end of the level that found a violation).  mc_engine_step accumulates across the calls that continue one search; a search
+ * that starts over starts its counts over.  A run that continues a restored checkpoint recounts the checkpointed levels from the
+ * arena and the parent pointers the file brought.  An action with 0 : 0 never fired: a guard that cannot hold, a label no process reaches.
+ * Compiled PlusCal programs (interpreted or MC_F_JIT) have one entry per label and one for the terminating disjunct ("Terminating").
+ * mc_engine_coverage: the entries for Init and every action of the model, in action-id order, zero rows included.  *n_inout: capacity
+ * in, count out (MC_EBADCFG with the count when the buffer is too small).  MC_ESTATE on an engine created without MC_F_COVERAGE. */
+typedef struct {
+    int32_t action;           /* action id (mc_action_name), -1 = Init                                   */
+    uint32_t pad;
+    uint64_t distinct, generated;
+} mc_action_coverage;
+int mc_engine_coverage(mc_engine *e, mc_action_coverage *out, size_t *n_inout);
 /* copy `count` resident states starting at arena index `first` (discovery order: level by level)
  * to the host, mc_state_bytes() bytes each — TLC's "states/" dump, for tests and tooling */
 int mc_engine_read_states(mc_engine *e, uint64_t first, uint64_t count, uint8_t *out);

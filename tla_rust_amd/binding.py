@@ -12,6 +12,7 @@ MC_MAX_LEVELS = 4096
 SPEC_IDS = {"atomic_add": 1, "pcal_intro": 2, "raft": 3, "ssi": 4, "pcal": 5, "paxos": 6}
 VERDICTS = ["ok", "invariant", "assert", "deadlock", "spec-error", "budget", "assume"]
 MC_F_DEADLOCK, MC_F_TRACE, MC_F_TIMING, MC_F_MATRIX, MC_F_NOPROBE, MC_F_NOFAMILY = 1, 2, 4, 8, 16, 32
+MC_F_COVERAGE = 1 << 24  # TLC's -coverage: per-action counts (Engine(coverage=True), Engine.coverage(); include/tlamc.h)
 MC_F_UNVERIFIED = 512  # use the built-in lowering even when the module a wrapper EXTENDS cannot be found (include/tlamc.h)
 
 
@@ -86,6 +87,11 @@ class Transport(C.Structure):
                 ("all_to_all_others", T_A2A)]   # optional: NULL (a positional constructor leaves it so) = use all_to_all
 
 
+class ActionCoverage(C.Structure):
+    """mc_action_coverage"""
+    _fields_ = [("action", C.c_int32), ("pad", C.c_uint32), ("distinct", C.c_uint64), ("generated", C.c_uint64)]
+
+
 class SimOpts(C.Structure):
     _fields_ = [("num", C.c_uint64), ("seed", C.c_uint64), ("depth", C.c_uint32), ("record", C.c_uint32),
                 ("record_slots", C.POINTER(C.c_int32)), ("record_len", C.POINTER(C.c_uint32)), ("record_end", C.POINTER(C.c_uint32))]
@@ -134,6 +140,7 @@ def lib():
     L.mc_engine_simulate.argtypes = [C.c_void_p, C.POINTER(SimOpts), C.POINTER(SimResult)]
     L.mc_engine_trace.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]
     L.mc_engine_kernel_stats.argtypes = [C.c_void_p, C.POINTER(KernelStats)]
+    L.mc_engine_coverage.argtypes = [C.c_void_p, C.POINTER(ActionCoverage), C.POINTER(C.c_size_t)]
     L.mc_engine_read_states.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
     L.mc_engine_debug_reexpand.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_double)]
     L.mc_engine_destroy.argtypes = [C.c_void_p]
@@ -274,12 +281,13 @@ class Engine:
     """One model-checking engine on one GPU (mc_engine_create / run / trace / destroy)."""
 
     def __init__(self, spec, params, device=0, table_capacity=0, arena_capacity=0, chunk_states=0, max_levels=0,
-                 max_distinct=0, deadlock=True, trace=True, timing=False, matrix=False, shard_rank=0, shard_count=1, debug_flags=0, jit=False):
+                 max_distinct=0, deadlock=True, trace=True, timing=False, matrix=False, shard_rank=0, shard_count=1, debug_flags=0, jit=False,
+                 coverage=False):
         self.spec, self.params = spec, list(params)
         self.desc = spec_desc(spec, params)
         # jit (MC_SPEC_PCAL): MC_F_JIT — the compiled program as generated code, built for the device when the engine is created
         flags = (MC_F_DEADLOCK if deadlock else 0) | (MC_F_TRACE if trace else 0) | (MC_F_TIMING if timing else 0) | \
-            (MC_F_MATRIX if matrix else 0) | (262144 if jit else 0) | debug_flags
+            (MC_F_MATRIX if matrix else 0) | (262144 if jit else 0) | (MC_F_COVERAGE if coverage else 0) | debug_flags
         self.cfg = Config(device, flags, table_capacity, arena_capacity, chunk_states, max_levels, max_distinct,
                           shard_rank, shard_count)
         self._h = C.c_void_p()
@@ -314,6 +322,19 @@ class Engine:
             out["recorded"] = [dict(len=ln[k], end=SIM_ENDS.get(en[k]), slots=[slots[k * depth + s] for s in range(max(ln[k] - 1, 0))])
                                for k in range(record)]
         return out
+
+    def coverage(self):
+        """mc_engine_coverage (TLC's -coverage; an engine created with coverage=True): {action name: (distinct, generated)} for "Init"
+        and every action of the model, in action-id order, zero rows included — the states each action was first to find and the
+        successors it generated over the levels the search has expanded."""
+        n = C.c_size_t(0)
+        rc = lib().mc_engine_coverage(self._h, None, C.byref(n))
+        if rc != -1 or not n.value:   # (MC_EBADCFG + the count is the answer to a buffer of no entries)
+            _check(rc, "mc_engine_coverage")
+        rows = (ActionCoverage * n.value)()
+        _check(lib().mc_engine_coverage(self._h, rows, C.byref(n)), "mc_engine_coverage")
+        return {("Init" if r.action < 0 else lib().mc_action_name(C.byref(self.desc), r.action).decode()): (int(r.distinct), int(r.generated))
+                for r in rows[:n.value]}
 
     def trace(self):
         """[(action name, state text)] of the last counterexample (of the last run or simulation)."""

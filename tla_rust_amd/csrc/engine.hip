@@ -62,6 +62,7 @@ static void set_error(const std::string &s) { mc_set_error_internal(s.c_str()); 
 #include "engine_kernels.h"   // namespace mc { ... every kernel ... }
 #include "engine_pairs.h"     // k_expand_pairs: the by-pairs expand + insert + write kernel (specs with S::PAIR_FAMILIES)
 #include "engine_sim.h"       // k_simulate: simulation mode, one lane per random walk (mc_engine_simulate)
+#include "engine_coverage.h"  // k_coverage_generated / k_coverage_distinct: per-action counts (MC_F_COVERAGE, mc_engine_coverage)
 namespace mc {
 
 // ------------------------------------------------------------------------------------- host side
@@ -119,6 +120,7 @@ struct EngineBase {
     virtual int shard_restore(const char *path) = 0;
     virtual size_t state_bytes() const = 0;
     virtual int simulate(const mc_sim_opts *opts, mc_sim_result *out) = 0;
+    virtual int coverage(mc_action_coverage *out, size_t *n_inout) = 0;
 };
 
 static uint64_t round_pow2(uint64_t v) {
@@ -318,6 +320,14 @@ struct Engine : EngineBase {
         std::vector<int32_t> trace_acts;   // ... and their action ids
         size_t trace_n = 0;
     } sim;
+    // ---- coverage (MC_F_COVERAGE, mc_engine_coverage): per-action histograms, bin 0 = Init, bin a + 1 = action id a
+    struct Cov {
+        bool on = false;
+        int nbins = 0;
+        DevBuf<unsigned long long> bins;   // [2 * nbins]: generated, then distinct; bumped by the kernels of engine_coverage.h
+        std::vector<uint64_t> host;        // the bins as the last run left them (+ Init's generated, which no kernel counts)
+        uint64_t init_generated = 0;
+    } cov;
 
     // slot slices of a generic-kernel launch (k_expand_insert): as many as it takes to give the device a few thousand wavefronts,
     // for specs whose slots all go through the loop (no unrolled prefix) and that have enough of them; TLAMC_NOSLICE=1 = A/B
@@ -396,6 +406,68 @@ struct Engine : EngineBase {
         HIP_TRY(d_lc.alloc(1));
         HIP_TRY(h_lc.alloc(1));
         timer.enabled = (cfg.flags & MC_F_TIMING) != 0;
+        if (cfg.flags & MC_F_COVERAGE) {
+            cov.nbins = CovAction<S>::nbins(prm);
+            if (cov.nbins > COV_MAX_BINS) { set_error("MC_F_COVERAGE: the model has more actions than the coverage histogram has bins (" + std::to_string(COV_MAX_BINS - 1) + ")"); return MC_EBADCFG; }
+            HIP_TRY(cov.bins.alloc((size_t)2 * cov.nbins));
+            HIP_TRY(hipMemset(cov.bins, 0, (size_t)2 * cov.nbins * sizeof(unsigned long long)));
+            cov.host.assign((size_t)2 * cov.nbins, 0);
+            cov.on = true;
+        }
+        return MC_OK;
+    }
+
+    // ------------------------------------------------------------------------------- coverage (engine_coverage.h)
+    // All on `stream`, behind the expand kernels of the level they count: the arena rows and trace records they read are final by then.
+    // generated: the states [lo, hi) a level expanded, in the chunks the expand kernel saw.
+    void cov_generated(uint64_t lo, uint64_t hi) {
+        for (uint64_t c0 = lo; c0 < hi;) {
+            const uint64_t base = c0 & ~63ull;
+            const uint64_t c1 = base + chunk < hi ? base + chunk : hi;
+            const uint64_t ncols = ((c1 - base) + 63) & ~63ull;
+            hipLaunchKernelGGL(k_coverage_generated<S>, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, stream, prm, (const uint64_t *)d_arena,
+                               c0, c1, ncols, cov.bins.p, cov.nbins);
+            c0 = c1;
+        }
+    }
+    // distinct: the states [lo, hi) a level added (or Init stored), by their trace records
+    void cov_distinct(uint64_t lo, uint64_t hi) {
+        for (uint64_t c0 = lo; c0 < hi; c0 += chunk) {
+            const uint64_t c1 = c0 + chunk < hi ? c0 + chunk : hi;
+            hipLaunchKernelGGL(k_coverage_distinct<S>, dim3((unsigned)((c1 - c0 + 255) / 256)), dim3(256), 0, stream, prm, (const uint64_t *)d_arena,
+                               (const uint32_t *)d_parent, (const uint16_t *)d_pslot, c0, c1, cov.bins.p + cov.nbins, cov.nbins);
+        }
+    }
+    // a search that starts over: empty bins, then what is in the arena already — Init's states, or (a restored checkpoint, whose parent
+    // pointers came with it) every level the checkpointed run expanded, [0, expanded), and every state it stored, [0, stored)
+    int cov_begin(uint64_t expanded, uint64_t stored) {
+        HIP_TRY(hipMemsetAsync(cov.bins, 0, (size_t)2 * cov.nbins * sizeof(unsigned long long), stream));
+        cov.init_generated = S::num_init(prm);
+        cov_generated(0, expanded);
+        cov_distinct(0, stored);
+        return MC_OK;
+    }
+    int cov_end() {
+        HIP_TRY(hipMemcpyAsync(cov.host.data(), cov.bins, cov.host.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        cov.host[0] += cov.init_generated;
+        return MC_OK;
+    }
+    int coverage(mc_action_coverage *out, size_t *n_inout) override {
+        if (!cov.on) { set_error("mc_engine_coverage: the engine was created without MC_F_COVERAGE"); return MC_ESTATE; }
+        size_t n = 1;
+        for (int a = 0; a + 1 < cov.nbins; a++) n += CovAction<S>::listed(prm, a) ? 1 : 0;
+        if (n > *n_inout || !out) { *n_inout = n; set_error("mc_engine_coverage: buffer too small"); return MC_EBADCFG; }
+        size_t k = 0;
+        for (int a = -1; a + 1 < cov.nbins; a++) {
+            if (a >= 0 && !CovAction<S>::listed(prm, a)) continue;
+            out[k].action = a;
+            out[k].pad = 0;
+            out[k].generated = cov.host[(size_t)a + 1];
+            out[k].distinct = cov.host[(size_t)cov.nbins + a + 1];
+            k++;
+        }
+        *n_inout = n;
         return MC_OK;
     }
 
@@ -600,6 +672,8 @@ struct Engine : EngineBase {
         uint32_t level = 1;
         out->level_distinct[0] = hi;
         fr.level_start.push_back(0);
+        // (a step that continues in place keeps counting; every other search starts its counts over)
+        if (cov.on && !in_place && (rc = cov_begin(resuming ? ck.lo : 0, hi))) return rc;
         if (resuming) {  // continue with the frontier [lo, hi) = the last, unexpanded level of the checkpointed run
             fr.level_start = ck.level_start;
             level = (uint32_t)fr.level_start.size();
@@ -649,6 +723,7 @@ struct Engine : EngineBase {
                 if ((rc = check_dev_error())) return rc;
                 for (unsigned k = 0; k < h_lc->nlev; k++) {
                     kstat[0].units += hi - lo;  // states expanded by this level (the launches were timed with 0 units)
+                    if (cov.on) { cov_generated(lo, hi); cov_distinct(hi, h_lc->level_hi[k]); }
                     if ((rc = close_level(lo, hi, h_lc->level_hi[k], level, out))) return rc;
                 }
                 progress(level, lo, hi);
@@ -713,9 +788,11 @@ struct Engine : EngineBase {
                 const double growth = hi > lo ? (double)(h_ctr->arena_next - hi) / (double)(hi - lo) : 1.0;
                 fr.mat_list_hint = (uint64_t)((double)(via / (chunk_no ? chunk_no : 1u)) * (growth > 1.0 ? growth : 1.0)) + 1;
             }
+            if (cov.on) { cov_generated(lo, hi); cov_distinct(hi, h_ctr->arena_next); }
             if ((rc = close_level(lo, hi, h_ctr->arena_next, level, out))) return rc;
             progress(level, lo, hi);
         }
+        if (cov.on && (rc = cov_end())) return rc;
         // a run that stops with an unexpanded frontier (budget) has not evaluated that level's check-on-expand invariants yet
         if (hi > lo && h_ctr->viol_key == ~0ull && !fr.stop_frontier && (rc = check_frontier(lo, hi))) return rc;
         const auto t1 = std::chrono::steady_clock::now();
@@ -1898,6 +1975,13 @@ int mc_engine_create(const mc_spec_desc *spec, const mc_config *cfg, mc_engine *
     *out = nullptr;
     if (mc_device_count() <= 0) { set_error("no HIP device: libtlamc has no CPU fallback"); return MC_EHIP; }
     g_last_error.clear();
+    mc_config with_trace;
+    if (cfg->flags & MC_F_COVERAGE) {
+        if (cfg->shard_count > 1) { set_error("MC_F_COVERAGE: not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
+        with_trace = *cfg;
+        with_trace.flags |= MC_F_TRACE;   // distinct[a] is read off the trace records
+        cfg = &with_trace;
+    }
     EngineBase *impl = nullptr;
     const int group = spec_group(spec);
     int rc = MC_EBADCFG;
@@ -1950,6 +2034,7 @@ int mc_engine_trace(mc_engine *e, uint8_t *states_out, int32_t *actions_out, siz
 int mc_engine_simulate(mc_engine *e, const mc_sim_opts *opts, mc_sim_result *out) {
     return e && opts && out ? e->impl->simulate(opts, out) : MC_EBADCFG;
 }
+int mc_engine_coverage(mc_engine *e, mc_action_coverage *out, size_t *n_inout) { return e && n_inout ? e->impl->coverage(out, n_inout) : MC_EBADCFG; }
 int mc_engine_kernel_stats(mc_engine *e, mc_kernel_stats *out) { return e && out ? e->impl->kernel_stats(out) : MC_EBADCFG; }
 int mc_engine_read_states(mc_engine *e, uint64_t first, uint64_t count, uint8_t *out) {
     return e && (out || !count) ? e->impl->read_states(first, count, out) : MC_EBADCFG;

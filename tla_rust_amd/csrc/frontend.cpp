@@ -1177,6 +1177,7 @@ static int host_evaluate(const char *tla_path, const char *cfg_path, const mc_co
     }
     o.put("Module %s has no GPU lowering: evaluated on the host by the general TLA+ evaluator.\n", module.c_str());
     o.put("Finished computing initial states: %llu distinct state%s generated.\n", (unsigned long long)r.init_states, r.init_states == 1 ? "" : "s");
+    if (cfg->flags & MC_F_COVERAGE) o.put("Warning: -coverage is not available for a module evaluated on the host\n");   // (the counts are the GPU engine's)
     if (!r.unchecked_properties.empty()) {
         // Liveness is out of scope — saying nothing about it is not (Liveness/LiveHourClock.cfg:10 PROPERTIES AlwaysTick AllTimes
         // TypeInvariance: TLC checks all three; here only []HCini is).  The line comes BEFORE the verdict it qualifies.
@@ -1461,6 +1462,17 @@ int mc_check_files_ckpt(const char *tla_path, const char *cfg_path, const mc_con
               "  because two distinct states had the same fingerprint:\n  calculated (optimistic):  val = %.2g\n", opt);
     } else {
         put_error_report(o, e, R, res->verdict, res->violated_invariant, res->trace_len);
+    }
+    if (cfg->flags & MC_F_COVERAGE) {   // TLC's -coverage: one row per action, "<Name>: distinct:generated" (the layout is ours: INTEGRATION.md)
+        size_t n = 0;
+        mc_engine_coverage(e, nullptr, &n);   // (the count)
+        std::vector<mc_action_coverage> rows(n ? n : 1);
+        if ((rc = mc_engine_coverage(e, rows.data(), &n))) { mc_engine_destroy(e); return rc; }
+        o.put("The coverage statistics :\n");
+        for (size_t k = 0; k < n; k++)
+            o.put("<%s>: %llu:%llu\n", rows[k].action < 0 ? "Init" : mc_action_name(&d, rows[k].action), (unsigned long long)rows[k].distinct,
+                  (unsigned long long)rows[k].generated);
+        o.put("End of statistics.\n");
     }
     o.put("%llu states generated, %llu distinct states found, %llu states left on queue.\n", (unsigned long long)res->generated,
           (unsigned long long)res->distinct, (unsigned long long)res->queue_left);

@@ -5,6 +5,7 @@
 //   mc X.tla [-config X.cfg] [-deadlock] [-workers N] [-device D] [-generic] [-dump FILE]
 //            [-maxdistinct N] [-maxlevels N] [-tablelog2 T] [-arena N] [-chunk N]
 //            [-checkpoint FILE] [-recover FILE] [-gpus P [-samedevice | -torch] [-exchange exact|measured|packed] [-fanout N]] [-noprogress] [-I DIR]
+//            [-coverage [MINUTES]]
 //   mc X.tla -simulate [num=N] [-depth D] [-seed S] [-config X.cfg] [-deadlock] [-jit] [-device D] [-noprogress] [-I DIR]
 //   mc --transpile X.tla [Y.tla ...]      the `pcal2tla *tla` of the reference's Makefile:3-4: inserts (or
 //                                         replaces) the TLA+ translation of the PlusCal algorithm in place,
@@ -45,6 +46,11 @@
 //             depth give the same walks and the same report.  The report has the error and its behaviour as the search's has, "The
 //             number of states generated: G" and the walks, but no distinct-state count or search depth: nothing was searched
 //             exhaustively.  -gpus, -dump, -checkpoint and -recover do not apply; a module without a GPU lowering is refused.
+// -coverage [N]: TLC's -coverage: after the search the report lists, for Init and for every action of the model (every label of a PlusCal
+//             algorithm and its terminating disjunct), "<Name>: D:G" — the distinct states the action was first to find and the states it
+//             generated; an action with 0:0 never fired (MC_F_COVERAGE, mc_engine_coverage).  TLC's argument, the minutes between two
+//             reports, is accepted and ignored: the counts are printed once, at the end.  Not with -simulate, -gpus or -recover (a
+//             recovered run has no counts for its checkpointed part); a module evaluated on the host gets a warning instead.
 // -deadlock : as with TLC, do NOT check for deadlock.  -workers is accepted and ignored (the
 // GPU is the worker pool).  Exit status: 0 no error, 12 safety violation (invariant / assert),
 // 11 deadlock, 1 any other failure — TLC's convention.
@@ -332,6 +338,11 @@ int main(int argc, char **argv) {
     }
     for (int i = 1; i < argc; i++)
         if (!strcmp(argv[i], "-simulate") && gpus) { fprintf(stderr, "mc: -gpus is not available with -simulate\n"); return 1; }
+    for (int i = 1; i < argc; i++)   // (before any rank is started, and before anything touches a device)
+        if (!strcmp(argv[i], "-coverage"))
+            for (int j = 1; j < argc; j++)
+                for (const char *other : {"-simulate", "-gpus", "-recover"})
+                    if (!strcmp(argv[j], other)) { fprintf(stderr, "mc: -coverage is not available with %s\n", other); return 1; }
     if (gpus && torch_door) return exec_multi(gpus, argc, argv);
     const char *env_rank = getenv("MC_RANK");
     if (gpus && !env_rank) {
@@ -374,6 +385,11 @@ int main(int argc, char **argv) {
         else if (arg("-seed")) {
             if (!parse_u64(argv[++i], &sim.seed)) { fprintf(stderr, "mc: -seed needs a non-negative integer\n"); return 1; }
             have_seed = true;
+        }
+        else if (!strcmp(argv[i], "-coverage")) {
+            cfg.flags |= MC_F_COVERAGE;
+            uint64_t minutes = 0;   // TLC's interval between two coverage reports: accepted, not used
+            if (i + 1 < argc && parse_u64(argv[i + 1], &minutes)) ++i;
         }
         else if (!strcmp(argv[i], "-deadlock")) cfg.flags &= ~MC_F_DEADLOCK;
         else if (arg("-dump")) dump = argv[++i];
@@ -419,6 +435,7 @@ int main(int argc, char **argv) {
                 "usage: mc X.tla [-config X.cfg] [-deadlock] [-dump FILE] [-generic] [-jit] [-unverified] [-device D] [-I DIR]\n"
                 "                [-maxdistinct N] [-maxlevels N] [-tablelog2 T] [-arena N] [-chunk N]\n"
                 "                [-checkpoint FILE] [-recover FILE] [-gpus P [-torch]]                    check X.tla like `tlc X.tla`\n"
+                "                [-coverage [MINUTES]]                                                    ... and list every action's distinct:generated counts\n"
                 "       mc X.tla -simulate [num=N] [-depth D] [-seed S] [...]                             random walks like `tlc -simulate`\n"
                 "       mc --transpile X.tla [Y.tla ...]                                                  translate like `pcal2tla`\n"
                 "exit status: 0 no error, 12 invariant / assertion violated, 11 deadlock, 1 anything else\n");

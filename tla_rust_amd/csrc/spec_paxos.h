@@ -434,7 +434,7 @@ struct SpecPaxos {
     }
 
     // ------------------------------------------------------------------ host side: actions and TLA+ text
-    static int action_of(const Params &p, const uint64_t *, int slot) {
+    MC_HD static int action_of(const Params &p, const uint64_t *, int slot) {
         if (p.kind == 1) return slot < p.na * p.nb ? 0 : 1;
         if (slot < p.nb) return 2;
         slot -= p.nb;
