@@ -16,6 +16,8 @@ pub const MC_F_GENERIC: u32 = 128;
 pub const MC_F_DEADLOCK: u32 = 1;
 pub const MC_F_TRACE: u32 = 2;
 pub const MC_F_JIT: u32 = 262144; // MC_SPEC_PCAL: the compiled program as generated code, built for the device when the engine is created
+pub const MC_DOT_ACTIONLABELS: u32 = 1; // mc_check_files_dot: the action name on every edge
+pub const MC_DOT_COLORIZE: u32 = 2;     // ... and a colour per action, with a legend
 pub const MC_F_COVERAGE: u32 = 16777216; // TLC's -coverage: per-action counts (mc_engine_coverage); implies MC_F_TRACE, one-GPU engines only
 pub const MC_MAX_LEVELS: usize = 4096;
 
@@ -53,6 +55,12 @@ pub struct mc_sim_result {
 // one entry of mc_engine_coverage: action id (-1 = Init), the states it was first to find, the successors it generated
 #[repr(C)]
 pub struct mc_action_coverage { pub action: i32, pub pad: u32, pub distinct: u64, pub generated: u64 }
+// what mc_engine_graph built: the state graph of the last search in CSR form (rows by arena index); 64 bytes
+#[repr(C)]
+pub struct mc_graph_info {
+    pub states: u64, pub expanded: u64, pub init_states: u64, pub edges: u64, pub self_loops: u64, pub dropped: u64,
+    pub max_out_degree: u32, pub pad: u32, pub seconds: f64,
+}
 #[repr(C)]
 pub struct mc_engine { _private: [u8; 0] }
 #[repr(C)]
@@ -67,6 +75,11 @@ extern "C" {
     pub fn mc_engine_trace(e: *mut mc_engine, states: *mut u8, actions: *mut i32, n_inout: *mut usize) -> c_int;
     // entries for Init and every action of the model, in action-id order; *n_inout: capacity in, count out
     pub fn mc_engine_coverage(e: *mut mc_engine, out: *mut mc_action_coverage, n_inout: *mut usize) -> c_int;
+    // the state graph, built on the device after a search and kept until the next one; graph_read: the rows of states
+    // [first, first + count): count + 1 offsets relative to the first, *nedges_inout capacity in / edges out
+    pub fn mc_engine_graph(e: *mut mc_engine, out: *mut mc_graph_info) -> c_int;
+    pub fn mc_engine_graph_read(e: *mut mc_engine, first: u64, count: u64, offsets_out: *mut u64, dst_out: *mut u32, action_out: *mut i32,
+                                nedges_inout: *mut usize) -> c_int;
     pub fn mc_engine_read_states(e: *mut mc_engine, first: u64, count: u64, out: *mut u8) -> c_int;
     // TLC's checkpoint / -recover (testout1:10): write / reload the states found so far; the next run continues
     pub fn mc_engine_checkpoint(e: *mut mc_engine, path: *const c_char) -> c_int;
@@ -80,6 +93,13 @@ extern "C" {
                             prog_out: *mut *mut mc_program) -> c_int;
     pub fn mc_check_files(tla: *const c_char, cfg_path: *const c_char, cfg: *const mc_config, report: *mut c_char,
                           cap: usize, out: *mut mc_result) -> c_int;
+    // TLC's -dump dot[,actionlabels][,colorize]: mc_check_files, and the state graph goes to dot_path (node k = State k of the plain
+    // dump); _dumps: both dumps from one search, with mc_check_files_ckpt's recover / checkpoint paths (any of the paths may be null)
+    pub fn mc_check_files_dot(tla: *const c_char, cfg_path: *const c_char, cfg: *const mc_config, report: *mut c_char, report_cap: usize,
+                              out: *mut mc_result, dot_path: *const c_char, dot_flags: u32) -> c_int;
+    pub fn mc_check_files_dumps(tla: *const c_char, cfg_path: *const c_char, cfg: *const mc_config, report: *mut c_char, report_cap: usize,
+                                out: *mut mc_result, dump_path: *const c_char, dot_path: *const c_char, dot_flags: u32,
+                                recover_path: *const c_char, checkpoint_path: *const c_char) -> c_int;
     pub fn mc_simulate_files(tla: *const c_char, cfg_path: *const c_char, cfg: *const mc_config, opts: *const mc_sim_opts,
                              report: *mut c_char, cap: usize, out: *mut mc_sim_result, interrupt: *const c_int) -> c_int;
     // PlusCal front-end: `pcal2tla` and the compiler to the GPU interpreter (include/tlamc.h)

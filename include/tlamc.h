@@ -219,6 +219,44 @@ typedef struct {
     uint64_t distinct, generated;
 } mc_action_coverage;
 int mc_engine_coverage(mc_engine *e, mc_action_coverage *out, size_t *n_inout);
+
+/* ------------------------------------------------------------------ the state graph (TLC's `-dump dot`)
+ * After a search the engine knows every state it found; mc_engine_graph adds how they connect: the edge list of the reachable graph in
+ * CSR form, built on the device from the resident arena and seen-set, and kept there until the next search.  State i of the graph is
+ * arena index i (mc_engine_read_states; state i + 1 of `-dump`); row i of dst[] / action[] is [offsets[i], offsets[i + 1]), in slot
+ * order; action ids are mc_action_name's, the ones mc_engine_coverage lists.
+ *   * A pair (expanded state, slot) that counts in mc_result.generated contributes: an edge to the state itself (a stuttering step);
+ *     an edge to the stored state its successor is; or nothing but a count in `dropped` — a successor that is stored nowhere: a failed
+ *     Assert, an evaluation error, a successor outside the CONSTRAINT, an invariant-breaking successor of a lowering that does not
+ *     store those.  So  initial states generated + edges + dropped == mc_result.generated  for every model (the first term is
+ *     mc_engine_coverage's generated[Init]).
+ *   * The states with out-edges are the ones the search expanded — the levels mc_engine_coverage counts: up to max_levels /
+ *     max_distinct, or to the end of the level that found a violation.  The unexpanded last level (the queue) has degree 0; so has a
+ *     terminal state inside an expanded level.
+ * mc_engine_graph is valid after any mc_engine_run / mc_engine_step that returned a result (ok, budget or a violation), needs no flag,
+ * and changes nothing a following mc_engine_step computes.  MC_ESTATE before the first run, after mc_engine_simulate, and on a
+ * restored engine that has not run yet; MC_EBADCFG on a sharded engine and for a search of 2^31 - 1 states or more (the scan's item
+ * count); MC_EARENA (the byte count in mc_last_error) when the device has no room for it: 4 bytes per seen-set slot while it is built, then 8 bytes per state and 6 per edge.  A stored state or an
+ * unflagged in-model successor that the seen-set does not hold fails the call with MC_ESTATE and builds no graph (mc_last_error names
+ * the first such state and slot; two different states with one fingerprint are the only legitimate cause).  The next run / step /
+ * simulate / restore releases the graph.
+ * mc_engine_graph_read: the rows of states [first, first + count).  offsets_out: count + 1 entries, relative to offsets_out[0] = 0;
+ * *nedges_inout: capacity of dst_out / action_out in, edges out (MC_EBADCFG with the count when they are too small).  MC_ESTATE
+ * without a built graph. */
+typedef struct {
+    uint64_t states;        /* = mc_result.distinct of the search the graph belongs to         */
+    uint64_t expanded;      /* states whose successors were generated (the rest: the queue)    */
+    uint64_t init_states;   /* stored initial states: arena indices 0 .. init_states-1         */
+    uint64_t edges;         /* entries of dst[] / action[]                                     */
+    uint64_t self_loops;    /* of those, dst == src                                            */
+    uint64_t dropped;       /* generated successors that are stored nowhere                    */
+    uint32_t max_out_degree;
+    uint32_t pad;
+    double   seconds;       /* index + both passes, device work included                       */
+} mc_graph_info;
+int mc_engine_graph(mc_engine *e, mc_graph_info *out);
+int mc_engine_graph_read(mc_engine *e, uint64_t first, uint64_t count, uint64_t *offsets_out /* count + 1 */, uint32_t *dst_out,
+                         int32_t *action_out, size_t *nedges_inout);
 /* copy `count` resident states starting at arena index `first` (discovery order: level by level)
  * to the host, mc_state_bytes() bytes each — TLC's "states/" dump, for tests and tooling */
 int mc_engine_read_states(mc_engine *e, uint64_t first, uint64_t count, uint8_t *out);
@@ -596,6 +634,21 @@ int mc_check_files_dump(const char *tla_path, const char *cfg_path, const mc_con
  * "-- Checkpointing of run <path> completed." (testout1:10) */
 int mc_check_files_ckpt(const char *tla_path, const char *cfg_path, const mc_config *cfg, char *report, size_t report_cap,
                         mc_result *out, const char *dump_path, const char *recover_path, const char *checkpoint_path);
+/* mc_check_files, and the state graph is written to dot_path in TLC's `-dump dot[,actionlabels][,colorize]` layout: "strict digraph
+ * DiskGraph", one node per state labelled with its text (initial states filled), one line per edge of mc_engine_graph, with
+ * MC_DOT_ACTIONLABELS the action's name on it, with MC_DOT_COLORIZE a colour per action and a legend.  Node k is arena index k - 1:
+ * the state `-dump` prints as "State k:".  The report gains "The state graph has <states> states and <edges> transitions (<self_loops>
+ * self loops)." after the depth line.  Refused where mc_check_files_dump is (a module evaluated on the host, a cfg without a behaviour).
+ * mc_check_files_dumps: both files from ONE search, so that they number the states alike (either path may be NULL), with
+ * mc_check_files_ckpt's recover_path / checkpoint_path (or NULL): a recovered search that has run has its seen-set again, so its
+ * graph — checkpointed levels included — is built like any other.  A dot file that cannot be written completely is removed. */
+#define MC_DOT_ACTIONLABELS 1u
+#define MC_DOT_COLORIZE 2u
+int mc_check_files_dot(const char *tla_path, const char *cfg_path, const mc_config *cfg, char *report, size_t report_cap,
+                       mc_result *out, const char *dot_path, unsigned dot_flags);
+int mc_check_files_dumps(const char *tla_path, const char *cfg_path, const mc_config *cfg, char *report, size_t report_cap,
+                         mc_result *out, const char *dump_path, const char *dot_path, unsigned dot_flags, const char *recover_path,
+                         const char *checkpoint_path);
 /* `mc X.tla -simulate`: the module and its cfg resolved as mc_check_files resolves them, then mc_engine_simulate with `opts`; the report
  * (seed, the error and its behaviour as in mc_check_files, "The number of states generated: G", the walks and the longest one) goes
  * to `report`.  A module without a GPU lowering is refused (MC_ENOSPEC).  *interrupt (optional; a SIGINT handler's flag) stops the

@@ -92,6 +92,16 @@ class ActionCoverage(C.Structure):
     _fields_ = [("action", C.c_int32), ("pad", C.c_uint32), ("distinct", C.c_uint64), ("generated", C.c_uint64)]
 
 
+class GraphInfo(C.Structure):
+    """mc_graph_info"""
+    _fields_ = [("states", C.c_uint64), ("expanded", C.c_uint64), ("init_states", C.c_uint64), ("edges", C.c_uint64),
+                ("self_loops", C.c_uint64), ("dropped", C.c_uint64), ("max_out_degree", C.c_uint32), ("pad", C.c_uint32),
+                ("seconds", C.c_double)]
+
+
+MC_DOT_ACTIONLABELS, MC_DOT_COLORIZE = 1, 2   # mc_check_files_dot
+
+
 class SimOpts(C.Structure):
     _fields_ = [("num", C.c_uint64), ("seed", C.c_uint64), ("depth", C.c_uint32), ("record", C.c_uint32),
                 ("record_slots", C.POINTER(C.c_int32)), ("record_len", C.POINTER(C.c_uint32)), ("record_end", C.POINTER(C.c_uint32))]
@@ -141,6 +151,8 @@ def lib():
     L.mc_engine_trace.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]
     L.mc_engine_kernel_stats.argtypes = [C.c_void_p, C.POINTER(KernelStats)]
     L.mc_engine_coverage.argtypes = [C.c_void_p, C.POINTER(ActionCoverage), C.POINTER(C.c_size_t)]
+    L.mc_engine_graph.argtypes = [C.c_void_p, C.POINTER(GraphInfo)]
+    L.mc_engine_graph_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
     L.mc_engine_read_states.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
     L.mc_engine_debug_reexpand.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_double)]
     L.mc_engine_destroy.argtypes = [C.c_void_p]
@@ -209,6 +221,8 @@ def lib():
         if hasattr(L, "mc_resolve_files"):
             L.mc_resolve_files.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(SpecDesc), C.POINTER(C.c_void_p)]
         L.mc_check_files.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Config), C.c_char_p, C.c_size_t, C.POINTER(CResult)]
+        L.mc_check_files_dot.argtypes = L.mc_check_files.argtypes + [C.c_char_p, C.c_uint]
+        L.mc_check_files_dumps.argtypes = L.mc_check_files.argtypes + [C.c_char_p, C.c_char_p, C.c_uint, C.c_char_p, C.c_char_p]
     if hasattr(L, "mc_program_compile"):
         L.mc_pcal_translate.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
         L.mc_program_compile.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
@@ -335,6 +349,44 @@ class Engine:
         _check(lib().mc_engine_coverage(self._h, rows, C.byref(n)), "mc_engine_coverage")
         return {("Init" if r.action < 0 else lib().mc_action_name(C.byref(self.desc), r.action).decode()): (int(r.distinct), int(r.generated))
                 for r in rows[:n.value]}
+
+    def graph_info(self):
+        """mc_engine_graph: build the state graph of the last search on the device (it stays there until the next search) and return
+        its mc_graph_info as a dict: states, expanded, init_states, edges, self_loops, dropped, max_out_degree, seconds."""
+        gi = GraphInfo()
+        _check(lib().mc_engine_graph(self._h, C.byref(gi)), "mc_engine_graph")
+        return Result((k, getattr(gi, k)) for k, _ in GraphInfo._fields_ if k != "pad")
+
+    def graph_read(self, first, count, edge_capacity):
+        """mc_engine_graph_read: (offsets[count + 1] relative to the first row, dst, action) of states first .. first + count - 1"""
+        import numpy as np
+        off = np.zeros(count + 1, dtype=np.uint64)
+        dst, act = np.zeros(max(1, edge_capacity), dtype=np.uint32), np.zeros(max(1, edge_capacity), dtype=np.int32)
+        n = C.c_size_t(edge_capacity)
+        _check(lib().mc_engine_graph_read(self._h, first, count, off.ctypes.data, dst.ctypes.data, act.ctypes.data, C.byref(n)), "mc_engine_graph_read")
+        return off, dst[:n.value], act[:n.value]
+
+    def graph(self, batch=1 << 16):
+        """(info, offsets, dst, action): the state graph of the last search in CSR form, as numpy arrays read in batches of `batch`
+        states.  Row i (arena index i: state_texts(i, 1)) is dst[offsets[i]:offsets[i + 1]] — arena indices — with action[...] the
+        action ids of mc_action_name; offsets has info.states + 1 entries and offsets[-1] == info.edges."""
+        import numpy as np
+        info = self.graph_info()
+        offsets = np.zeros(info.states + 1, dtype=np.uint64)
+        dst, act = np.zeros(info.edges, dtype=np.uint32), np.zeros(info.edges, dtype=np.int32)
+        done = 0
+        for first in range(0, info.states, batch):
+            count = min(batch, info.states - first)
+            n = C.c_size_t(0)
+            rc = lib().mc_engine_graph_read(self._h, first, count, None, None, None, C.byref(n))   # (MC_EBADCFG + the count: the batch's edges)
+            if rc != -1:
+                _check(rc, "mc_engine_graph_read")
+            off, d, a = self.graph_read(first, count, n.value)
+            offsets[first:first + count + 1] = off + np.uint64(done)
+            dst[done:done + len(d)], act[done:done + len(a)] = d, a
+            done += len(d)
+        assert done == info.edges, (done, info.edges)
+        return info, offsets, dst, act
 
     def trace(self):
         """[(action name, state text)] of the last counterexample (of the last run or simulation)."""
@@ -675,4 +727,18 @@ def check_files(tla_path, cfg_path=None, device=0, **kw):
     rc = lib().mc_check_files(str(tla_path).encode(), str(cfg_path).encode() if cfg_path else None, C.byref(cfg), buf,
                               len(buf), C.byref(r))
     _check(rc, "mc_check_files")
+    return _result(r), buf.value.decode()
+
+
+def check_files_dot(tla_path, dot_path, cfg_path=None, device=0, actionlabels=False, colorize=False, dump_path=None, **kw):
+    """`tlc X.tla -dump dot[,actionlabels][,colorize] FILE` end to end (mc_check_files_dumps): the state graph goes to dot_path and, with
+    dump_path, the states to that file, numbered alike; returns (Result, report text)."""
+    cfg = Config(device, MC_F_DEADLOCK | MC_F_TRACE | (MC_F_UNVERIFIED if kw.get("unverified") else 0), kw.get("table_capacity", 0), kw.get("arena_capacity", 0),
+                 kw.get("chunk_states", 0), kw.get("max_levels", 0), kw.get("max_distinct", 0), 0, 1)
+    r = CResult()
+    buf = C.create_string_buffer(1 << 20)
+    flags = (MC_DOT_ACTIONLABELS if actionlabels else 0) | (MC_DOT_COLORIZE if colorize else 0)
+    rc = lib().mc_check_files_dumps(str(tla_path).encode(), str(cfg_path).encode() if cfg_path else None, C.byref(cfg), buf, len(buf), C.byref(r),
+                                    str(dump_path).encode() if dump_path else None, str(dot_path).encode(), flags, None, None)
+    _check(rc, "mc_check_files_dumps")
     return _result(r), buf.value.decode()

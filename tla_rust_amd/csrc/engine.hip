@@ -63,6 +63,7 @@ static void set_error(const std::string &s) { mc_set_error_internal(s.c_str()); 
 #include "engine_pairs.h"     // k_expand_pairs: the by-pairs expand + insert + write kernel (specs with S::PAIR_FAMILIES)
 #include "engine_sim.h"       // k_simulate: simulation mode, one lane per random walk (mc_engine_simulate)
 #include "engine_coverage.h"  // k_coverage_generated / k_coverage_distinct: per-action counts (MC_F_COVERAGE, mc_engine_coverage)
+#include "engine_graph.h"     // k_graph_index / k_graph_degree / k_graph_fill: the state graph in CSR form (mc_engine_graph)
 namespace mc {
 
 // ------------------------------------------------------------------------------------- host side
@@ -121,6 +122,8 @@ struct EngineBase {
     virtual size_t state_bytes() const = 0;
     virtual int simulate(const mc_sim_opts *opts, mc_sim_result *out) = 0;
     virtual int coverage(mc_action_coverage *out, size_t *n_inout) = 0;
+    virtual int graph(mc_graph_info *out) = 0;
+    virtual int graph_read(uint64_t first, uint64_t count, uint64_t *offsets_out, uint32_t *dst_out, int32_t *action_out, size_t *nedges_inout) = 0;
 };
 
 static uint64_t round_pow2(uint64_t v) {
@@ -328,6 +331,16 @@ struct Engine : EngineBase {
         std::vector<uint64_t> host;        // the bins as the last run left them (+ Init's generated, which no kernel counts)
         uint64_t init_generated = 0;
     } cov;
+    // ---- the state graph (mc_engine_graph; engine_graph.h): built on demand from the arena and the seen-set a search left, gone with
+    // the next search (run / step / simulate / restore) or with the engine
+    struct Graph {
+        bool built = false;
+        DevBuf<uint64_t> offsets;   // [states + 1]: row i of dst / act is [offsets[i], offsets[i + 1]); doubles as the out-degree table
+        DevBuf<uint32_t> dst;       // [edges] arena index of the successor
+        DevBuf<int16_t> act;        // [edges] action id (CovAction<S>::of: mc_action_name's)
+        mc_graph_info info{};
+        void release() { built = false; offsets.reset(); dst.reset(); act.reset(); }
+    } gr;
 
     // slot slices of a generic-kernel launch (k_expand_insert): as many as it takes to give the device a few thousand wavefronts,
     // for specs whose slots all go through the loop (no unrolled prefix) and that have enough of them; TLAMC_NOSLICE=1 = A/B
@@ -468,6 +481,125 @@ struct Engine : EngineBase {
             k++;
         }
         *n_inout = n;
+        return MC_OK;
+    }
+
+    // ------------------------------------------------------------------------------- the state graph (engine_graph.h)
+    // All on `stream`, after a search has ended: rows, fingerprints and counters are final and only read.  The states with out-edges
+    // are [0, fr.lo): run() moves `lo` past a level exactly when it has expanded it — the same (lo, hi) it hands to cov_generated —
+    // so the levels coverage counts and the levels that have rows here cannot differ.
+    template <class T>
+    int graph_alloc(DevBuf<T> &b, size_t count, const char *what) {
+        if (b.alloc(count ? count : 1) == hipSuccess) return MC_OK;
+        (void)hipGetLastError();   // (the failed allocation is reported here, not by the next HIP call)
+        set_error("mc_engine_graph: cannot allocate " + std::to_string((unsigned long long)(count * sizeof(T))) + " bytes of device memory for " + what);
+        return MC_EARENA;
+    }
+    template <class K, class... A>
+    void graph_chunks(K kernel, uint64_t lo, uint64_t hi, A... args) {   // the chunks cov_generated launches
+        for (uint64_t c0 = lo; c0 < hi;) {
+            const uint64_t base = c0 & ~63ull;
+            const uint64_t c1 = base + chunk < hi ? base + chunk : hi;
+            const uint64_t ncols = ((c1 - base) + 63) & ~63ull;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, stream, prm, (const uint64_t *)d_arena, c0, c1, ncols,
+                               (const uint64_t *)d_table, seen_arg(), args...);
+            c0 = c1;
+        }
+    }
+    int graph(mc_graph_info *out) override {
+        memset(out, 0, sizeof *out);
+        if (cfg.shard_count > 1) { set_error("mc_engine_graph: not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
+        if (!fr.have_run || ck.pending) {
+            set_error("mc_engine_graph: needs a search of this engine that returned a result (mc_engine_run / mc_engine_step; not a simulation, "
+                      "not a restored checkpoint that has not run yet: its seen-set is not built)");
+            return MC_ESTATE;
+        }
+        gr.release();
+        const uint64_t n = fr.last_distinct, expanded = fr.lo;
+        if (n + 1 > 0x7fffffffull) { set_error("mc_engine_graph: at most 2^31 - 2 states (the scan's item count)"); return MC_EBADCFG; }
+        HIP_TRY(hipSetDevice(cfg.device));
+        const auto t0 = std::chrono::steady_clock::now();
+        DevBuf<uint32_t> slot_index, degree;   // build-time only: gone when this call returns
+        DevBuf<GraphCounters> d_gc;
+        DevBuf<char> scan_tmp;
+        int rc;
+        if ((rc = graph_alloc(slot_index, table_cap, "the fingerprint -> state index"))) return rc;
+        if ((rc = graph_alloc(degree, n + 1, "the out-degrees"))) return rc;
+        if ((rc = graph_alloc(gr.offsets, n + 1, "the row offsets"))) { gr.release(); return rc; }
+        if ((rc = graph_alloc(d_gc, 1, "the counters"))) { gr.release(); return rc; }
+        const int built = graph_build(n, expanded, slot_index, degree, d_gc, scan_tmp);
+        if (built) { gr.release(); return built; }
+        gr.info.states = n;
+        gr.info.expanded = expanded;
+        gr.info.init_states = fr.level_start.size() > 1 ? fr.level_start[1] : n;
+        gr.info.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        gr.built = true;
+        *out = gr.info;
+        return MC_OK;
+    }
+    int graph_build(uint64_t n, uint64_t expanded, DevBuf<uint32_t> &slot_index, DevBuf<uint32_t> &degree, DevBuf<GraphCounters> &d_gc, DevBuf<char> &scan_tmp) {
+        GraphCounters gc;
+        memset(&gc, 0, sizeof gc);
+        gc.first_bad = ~0ull;
+        HIP_TRY(hipMemcpyAsync(d_gc, &gc, sizeof gc, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(slot_index, 0xff, table_cap * sizeof(uint32_t), stream));
+        HIP_TRY(hipMemsetAsync(degree, 0, (n + 1) * sizeof(uint32_t), stream));
+        if (n) hipLaunchKernelGGL(k_graph_index<S>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, prm, (const uint64_t *)d_arena, n,
+                                  (const uint64_t *)d_table, seen_arg(), slot_index.p, table_cap, d_gc.p);
+        graph_chunks(k_graph_degree<S>, 0, expanded, degree.p, d_gc.p);
+        HIP_TRY(hipGetLastError());
+        hipcub::TransformInputIterator<uint64_t, GraphDegreeCast, const uint32_t *> in(degree.p, GraphDegreeCast());
+        size_t need = 0;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, in, gr.offsets.p, (int)(n + 1), stream));
+        if (int rc = graph_alloc(scan_tmp, need, "the scan")) return rc;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp.p, need, in, gr.offsets.p, (int)(n + 1), stream));
+        uint64_t edges = 0;
+        HIP_TRY(hipMemcpyAsync(&edges, gr.offsets.p + n, sizeof edges, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&gc, d_gc, sizeof gc, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (int rc = graph_inconsistent(gc)) return rc;
+        if (int rc = graph_alloc(gr.dst, edges, "the edges' successors")) return rc;
+        if (int rc = graph_alloc(gr.act, edges, "the edges' actions")) return rc;
+        graph_chunks(k_graph_fill<S>, 0, expanded, (const uint32_t *)slot_index.p, table_cap, (const uint64_t *)gr.offsets.p, gr.dst.p, gr.act.p, d_gc.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&gc, d_gc, sizeof gc, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (int rc = graph_inconsistent(gc)) return rc;
+        gr.info.edges = edges;
+        gr.info.self_loops = gc.self_loops;
+        gr.info.dropped = gc.dropped;
+        gr.info.max_out_degree = gc.max_degree;
+        return MC_OK;
+    }
+    static int graph_inconsistent(const GraphCounters &gc) {
+        if (!gc.missing_states && !gc.missing_succ) return MC_OK;
+        const unsigned long long idx = gc.first_bad >> 16;
+        const unsigned slot = (unsigned)(gc.first_bad & 0xffffu);
+        set_error("mc_engine_graph: the seen-set does not hold " + std::to_string(gc.missing_states) + " stored state(s) and " + std::to_string(gc.missing_succ) +
+                  " in-model successor(s); the first: state " + std::to_string(idx) + (slot == GRAPH_SLOT_SELF ? " itself" : ", slot " + std::to_string(slot)) +
+                  " (two different states with one 64-bit fingerprint are the only legitimate cause: the second is never stored); no graph was built");
+        return MC_ESTATE;
+    }
+    int graph_read(uint64_t first, uint64_t count, uint64_t *offsets_out, uint32_t *dst_out, int32_t *action_out, size_t *nedges_inout) override {
+        if (!gr.built) { set_error("mc_engine_graph_read: no graph (mc_engine_graph builds it; the next search releases it)"); return MC_ESTATE; }
+        if (first > gr.info.states || count > gr.info.states - first) { set_error("mc_engine_graph_read: range beyond the graph's states"); return MC_EBADCFG; }
+        HIP_TRY(hipSetDevice(cfg.device));
+        std::vector<uint64_t> off((size_t)count + 1);
+        HIP_TRY(hipMemcpy(off.data(), gr.offsets.p + first, off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        const uint64_t e0 = off[0], ne = off[count] - e0;
+        if (ne > *nedges_inout || !offsets_out || (ne && (!dst_out || !action_out))) {
+            *nedges_inout = (size_t)ne;
+            set_error("mc_engine_graph_read: buffer too small (" + std::to_string((unsigned long long)ne) + " edges)");
+            return MC_EBADCFG;
+        }
+        for (uint64_t k = 0; k <= count; k++) offsets_out[k] = off[k] - e0;
+        if (ne) {
+            std::vector<int16_t> a16((size_t)ne);
+            HIP_TRY(hipMemcpy(dst_out, gr.dst.p + e0, ne * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(a16.data(), gr.act.p + e0, ne * sizeof(int16_t), hipMemcpyDeviceToHost));
+            for (uint64_t k = 0; k < ne; k++) action_out[k] = a16[k];
+        }
+        *nedges_inout = (size_t)ne;
         return MC_OK;
     }
 
@@ -643,6 +775,7 @@ struct Engine : EngineBase {
         fr.have_viol = false;
         sim.trace_n = 0;
         stop_requested = false;
+        gr.release();
         fr.have_run = false;  // set again on the success path only: a run that fails half-way (MC_EARENA, MC_ETABLEFULL, MC_EOVERFLOW)
                            // leaves fingerprints of an unfinished level in the seen-set — the next step / checkpoint must not continue it
         fr.level_start.clear();
@@ -943,6 +1076,7 @@ struct Engine : EngineBase {
     }
     int restore(const char *path) override {
         if (cfg.shard_count > 1) { set_error("restore: not available for a sharded engine"); return MC_EBADCFG; }
+        gr.release();
         FileCloser f{fopen(path, "rb")};
         if (!f.f) return ck_fail(MC_EPARSE, "restore", std::string("cannot read ") + path);
         CkHeader h;
@@ -1693,6 +1827,7 @@ struct Engine : EngineBase {
         fr.have_run = fr.have_viol = false;
         ck.pending = ck.in_place = false;
         stop_requested = false;
+        gr.release();
         sim.trace_n = 0;
         sim.trace_rows.clear();
         sim.trace_acts.clear();
@@ -2035,6 +2170,10 @@ int mc_engine_simulate(mc_engine *e, const mc_sim_opts *opts, mc_sim_result *out
     return e && opts && out ? e->impl->simulate(opts, out) : MC_EBADCFG;
 }
 int mc_engine_coverage(mc_engine *e, mc_action_coverage *out, size_t *n_inout) { return e && n_inout ? e->impl->coverage(out, n_inout) : MC_EBADCFG; }
+int mc_engine_graph(mc_engine *e, mc_graph_info *out) { return e && out ? e->impl->graph(out) : MC_EBADCFG; }
+int mc_engine_graph_read(mc_engine *e, uint64_t first, uint64_t count, uint64_t *offsets_out, uint32_t *dst_out, int32_t *action_out, size_t *nedges_inout) {
+    return e && nedges_inout ? e->impl->graph_read(first, count, offsets_out, dst_out, action_out, nedges_inout) : MC_EBADCFG;
+}
 int mc_engine_kernel_stats(mc_engine *e, mc_kernel_stats *out) { return e && out ? e->impl->kernel_stats(out) : MC_EBADCFG; }
 int mc_engine_read_states(mc_engine *e, uint64_t first, uint64_t count, uint8_t *out) {
     return e && (out || !count) ? e->impl->read_states(first, count, out) : MC_EBADCFG;

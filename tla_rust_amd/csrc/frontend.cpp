@@ -1312,8 +1312,100 @@ static bool jit_compiler_present() {
     return stat(hc && *hc ? hc : "/opt/rocm/bin/hipcc", &st) == 0 && (st.st_mode & S_IXUSR);
 }
 
+// TLC's `-dump dot`: the graph of mc_engine_graph as "strict digraph DiskGraph", streamed in batches of states (the rows of a batch
+// and their texts are all the host ever holds).  Node k = arena index k - 1 = "State k:" of the plain dump.
+static void dot_escape(const char *s, std::string &out) {
+    out.clear();
+    for (; *s; ++s) {
+        if (*s == '\n') out += "\\n";
+        else if (*s == '"' || *s == '\\') { out += '\\'; out += *s; }
+        else out += *s;
+    }
+}
+static int write_dot(mc_engine *e, const mc_spec_desc &d, const mc_graph_info &gi, const char *path, unsigned flags) {
+    FILE *f = fopen(path, "w");
+    if (!f) return fe_fail(MC_EPARSE, "cannot write %s", path);
+    const bool labels = (flags & MC_DOT_ACTIONLABELS) != 0, colors = (flags & MC_DOT_COLORIZE) != 0;
+    fprintf(f, "strict digraph DiskGraph {\n");
+    if (colors) fprintf(f, "edge [colorscheme=\"paired12\"]\n");
+    fprintf(f, "nodesep=0.35;\nsubgraph cluster_graph {\ncolor=\"white\";\n");
+    const size_t W = mc_state_bytes(&d);
+    const uint64_t batch = 1 << 14;
+    std::vector<uint8_t> buf(batch * W);
+    std::vector<char> txt(1 << 16);
+    std::vector<uint64_t> off(batch + 1);
+    std::vector<uint32_t> dst(1 << 16);
+    std::vector<int32_t> act(1 << 16);
+    std::vector<bool> used;   // action ids that label an edge: the legend's entries
+    std::string esc;
+    int rc = MC_OK;
+    for (uint64_t first = 0; first < gi.states && !rc; first += batch) {
+        const uint64_t n = gi.states - first < batch ? gi.states - first : batch;
+        if ((rc = mc_engine_read_states(e, first, n, buf.data()))) break;
+        size_t ne = dst.size();
+        rc = mc_engine_graph_read(e, first, n, off.data(), dst.data(), act.data(), &ne);
+        if (rc == MC_EBADCFG && ne > dst.size()) {   // (the answer to a short buffer: the batch's edge count)
+            dst.resize(ne);
+            act.resize(ne);
+            rc = mc_engine_graph_read(e, first, n, off.data(), dst.data(), act.data(), &ne);
+        }
+        if (rc) break;
+        for (uint64_t k = 0; k < n; k++) {
+            mc_state_format(&d, &buf[k * W], txt.data(), txt.size());
+            dot_escape(txt.data(), esc);
+            fprintf(f, "%llu [label=\"%s\"%s]\n", (unsigned long long)(first + k + 1), esc.c_str(), first + k < gi.init_states ? ",style = filled" : "");
+        }
+        for (uint64_t k = 0; k < n; k++)
+            for (uint64_t j = off[k]; j < off[k + 1]; j++) {
+                fprintf(f, "%llu -> %llu", (unsigned long long)(first + k + 1), (unsigned long long)dst[j] + 1);
+                if (labels || colors) {
+                    const int a = act[j];
+                    if (a >= 0 && (size_t)a >= used.size()) used.resize((size_t)a + 1, false);
+                    if (a >= 0) used[(size_t)a] = true;
+                    fputs(" [", f);
+                    if (labels) { dot_escape(mc_action_name(&d, a), esc); fprintf(f, "label=\"%s\"", esc.c_str()); }
+                    if (colors) fprintf(f, "%scolor=\"%d\",fontcolor=\"%d\"", labels ? "," : "", (a < 0 ? 0 : a) % 12 + 1, (a < 0 ? 0 : a) % 12 + 1);
+                    fputs("]", f);
+                }
+                fputs(";\n", f);
+            }
+    }
+    if (!rc) {
+        fprintf(f, "}\n");
+        if (colors) {   // TLC's legend: one filled record per action, in the edges' colours
+            fprintf(f, "subgraph cluster_legend {graph[style=bold];label = \"Next State Actions\" style=\"solid\"\n"
+                       "node [ labeljust=\"l\",colorscheme=\"paired12\",style=filled,shape=record ]\n");
+            for (size_t a = 0; a < used.size(); a++)
+                if (used[a]) { dot_escape(mc_action_name(&d, (int)a), esc); fprintf(f, "\"%s\" [label=\"%s\",fillcolor=%d]\n", esc.c_str(), esc.c_str(), (int)(a % 12) + 1); }
+            fprintf(f, "}\n");
+        }
+        fprintf(f, "}\n");
+    }
+    if (fclose(f) != 0 && !rc) rc = fe_fail(MC_EPARSE, "cannot write %s", path);
+    if (rc) remove(path);   // (a read that failed mid-stream leaves no truncated graph behind)
+    return rc;
+}
+
+static int check_files_impl(const char *tla_path, const char *cfg_path, const mc_config *cfg, char *report, size_t report_cap,
+                            mc_result *res, const char *dump_path, const char *recover_path, const char *checkpoint_path,
+                            const char *dot_path, unsigned dot_flags);
 int mc_check_files_ckpt(const char *tla_path, const char *cfg_path, const mc_config *cfg, char *report, size_t report_cap,
                         mc_result *res, const char *dump_path, const char *recover_path, const char *checkpoint_path) {
+    return check_files_impl(tla_path, cfg_path, cfg, report, report_cap, res, dump_path, recover_path, checkpoint_path, nullptr, 0u);
+}
+int mc_check_files_dot(const char *tla_path, const char *cfg_path, const mc_config *cfg, char *report, size_t report_cap,
+                       mc_result *res, const char *dot_path, unsigned dot_flags) {
+    return mc_check_files_dumps(tla_path, cfg_path, cfg, report, report_cap, res, nullptr, dot_path, dot_flags, nullptr, nullptr);
+}
+int mc_check_files_dumps(const char *tla_path, const char *cfg_path, const mc_config *cfg, char *report, size_t report_cap,
+                         mc_result *res, const char *dump_path, const char *dot_path, unsigned dot_flags, const char *recover_path,
+                         const char *checkpoint_path) {
+    if (dot_flags & ~(MC_DOT_ACTIONLABELS | MC_DOT_COLORIZE)) return fe_fail(MC_EBADCFG, "mc_check_files_dot: unknown flag");
+    return check_files_impl(tla_path, cfg_path, cfg, report, report_cap, res, dump_path, recover_path, checkpoint_path, dot_path, dot_flags);
+}
+static int check_files_impl(const char *tla_path, const char *cfg_path, const mc_config *cfg, char *report, size_t report_cap,
+                            mc_result *res, const char *dump_path, const char *recover_path, const char *checkpoint_path,
+                            const char *dot_path, unsigned dot_flags) {
     if (!tla_path || !cfg || !report || !report_cap || !res) return MC_EBADCFG;
     report[0] = 0;
     // A cfg that names no behaviour (neither SPECIFICATION nor INIT / NEXT) asks for the module's ASSUMEs to be evaluated — TLC's "No
@@ -1324,14 +1416,14 @@ int mc_check_files_ckpt(const char *tla_path, const char *cfg_path, const mc_con
         if (!read_file(tla_path, tla)) return fe_fail(MC_EPARSE, "cannot read %s", tla_path);
         if (!module_name(tla, module)) return fe_fail(MC_EPARSE, "%s: no MODULE header", tla_path);
         if (tla.find("--algorithm") == std::string::npos && tla.find("--fair") == std::string::npos) {
-            if (dump_path || recover_path || checkpoint_path) return fe_fail(MC_ENOSPEC, "%s: -dump / -recover / -checkpoint need a behaviour spec", module.c_str());
+            if (dump_path || dot_path || recover_path || checkpoint_path) return fe_fail(MC_ENOSPEC, "%s: -dump / -recover / -checkpoint need a behaviour spec", module.c_str());
             return host_evaluate(tla_path, cfg_path, cfg, module, report, report_cap, res);
         }
     }
     Resolved R;
     int rc = resolve_files(tla_path, cfg_path, cfg->flags, R);
     if (rc == MC_ENOSPEC && !R.module.empty() && !lowered_family(R.module, R.tla)) {
-        if (dump_path || recover_path || checkpoint_path) return fe_fail(MC_ENOSPEC, "%s: -dump / -recover / -checkpoint need a GPU lowering (the module is evaluated on the host)", R.module.c_str());
+        if (dump_path || dot_path || recover_path || checkpoint_path) return fe_fail(MC_ENOSPEC, "%s: -dump / -recover / -checkpoint need a GPU lowering (the module is evaluated on the host)", R.module.c_str());
         return host_evaluate(tla_path, cfg_path, cfg, R.module, report, report_cap, res);
     }
     if (rc) return rc;
@@ -1477,6 +1569,12 @@ int mc_check_files_ckpt(const char *tla_path, const char *cfg_path, const mc_con
     o.put("%llu states generated, %llu distinct states found, %llu states left on queue.\n", (unsigned long long)res->generated,
           (unsigned long long)res->distinct, (unsigned long long)res->queue_left);
     o.put("The depth of the complete state graph search is %u.\n", res->depth);
+    if (dot_path) {  // TLC -dump dot: the graph of the engine that finished the search
+        mc_graph_info gi;
+        if ((rc = mc_engine_graph(e, &gi)) || (rc = write_dot(e, d, gi, dot_path, dot_flags))) { mc_engine_destroy(e); return rc; }
+        o.put("The state graph has %llu states and %llu transitions (%llu self loops).\n", (unsigned long long)gi.states, (unsigned long long)gi.edges,
+              (unsigned long long)gi.self_loops);
+    }
     if (dump_path) {  // TLC -dump: every distinct state, in the order it was found
         FILE *f = fopen(dump_path, "w");
         if (!f) { mc_engine_destroy(e); return fe_fail(MC_EPARSE, "cannot write %s", dump_path); }

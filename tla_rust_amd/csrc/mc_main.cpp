@@ -2,7 +2,7 @@
 // Makefile:6-7 / README.md:262 (same inputs: X.tla with X.cfg beside it; same report lines:
 // README.md:267-321).  All work happens behind the C ABI (include/tlamc.h).
 //
-//   mc X.tla [-config X.cfg] [-deadlock] [-workers N] [-device D] [-generic] [-dump FILE]
+//   mc X.tla [-config X.cfg] [-deadlock] [-workers N] [-device D] [-generic] [-dump FILE] [-dump dot[,actionlabels][,colorize] FILE]
 //            [-maxdistinct N] [-maxlevels N] [-tablelog2 T] [-arena N] [-chunk N]
 //            [-checkpoint FILE] [-recover FILE] [-gpus P [-samedevice | -torch] [-exchange exact|measured|packed] [-fanout N]] [-noprogress] [-I DIR]
 //            [-coverage [MINUTES]]
@@ -25,6 +25,10 @@
 //             neither beside the wrapper nor under $TLA_PATH the run is refused, unless this option accepts the built-in
 //             lowering unchecked (the report then starts with a warning).
 // -dump FILE: like TLC's -dump, write every distinct state found to FILE.
+// -dump dot[,actionlabels][,colorize] FILE: like TLC's, write the state graph to FILE in GraphViz's dot language (mc_engine_graph,
+//             mc_check_files_dot): one node per state, one line per transition, with actionlabels the action's name on it, with colorize
+//             a colour per action and a legend.  Node k is the state `-dump FILE` prints as "State k:"; both forms may be given in one
+//             run and then number the states alike.  The report gains "The state graph has ... states and ... transitions".
 // -checkpoint FILE / -recover FILE: TLC's checkpointing (testout1:10) and -recover: write the run (all states found, level
 //             boundaries, counters, parent pointers) after a search that stopped on -maxlevels / -maxdistinct without an
 //             error; continue such a run later, with the same X.tla / X.cfg.  With -gpus P: one file per rank,
@@ -343,6 +347,12 @@ int main(int argc, char **argv) {
             for (int j = 1; j < argc; j++)
                 for (const char *other : {"-simulate", "-gpus", "-recover"})
                     if (!strcmp(argv[j], other)) { fprintf(stderr, "mc: -coverage is not available with %s\n", other); return 1; }
+    if (gpus && !getenv("MC_RANK"))
+        for (int i = 1; i < argc; i++)
+            if (!strcmp(argv[i], "-dump") && i + 1 < argc && (!strcmp(argv[i + 1], "dot") || !strncmp(argv[i + 1], "dot,", 4))) {
+                fprintf(stderr, "mc: -dump is not available with -gpus\n");
+                return 1;
+            }
     if (gpus && torch_door) return exec_multi(gpus, argc, argv);
     const char *env_rank = getenv("MC_RANK");
     if (gpus && !env_rank) {
@@ -354,7 +364,8 @@ int main(int argc, char **argv) {
         for (int i = 2; i < argc; i++) rc |= transpile(argv[i]);
         return rc;
     }
-    const char *tla = nullptr, *cfgp = nullptr, *dump = nullptr, *recover = nullptr, *ckpt = nullptr;
+    const char *tla = nullptr, *cfgp = nullptr, *dump = nullptr, *recover = nullptr, *ckpt = nullptr, *dot = nullptr;
+    unsigned dot_flags = 0;
     bool simulate = false, have_seed = false, have_depth = false;
     mc_sim_opts sim;
     memset(&sim, 0, sizeof sim);
@@ -392,6 +403,18 @@ int main(int argc, char **argv) {
             if (i + 1 < argc && parse_u64(argv[i + 1], &minutes)) ++i;
         }
         else if (!strcmp(argv[i], "-deadlock")) cfg.flags &= ~MC_F_DEADLOCK;
+        else if (arg("-dump") && (!strcmp(argv[i + 1], "dot") || !strncmp(argv[i + 1], "dot,", 4))) {   // TLC: -dump dot[,actionlabels][,colorize] FILE
+            for (const char *s = argv[++i] + 3; *s;) {
+                const char *e = strchr(++s, ',');
+                const std::string sub(s, e ? (size_t)(e - s) : strlen(s));
+                if (sub == "actionlabels") dot_flags |= MC_DOT_ACTIONLABELS;
+                else if (sub == "colorize") dot_flags |= MC_DOT_COLORIZE;
+                else { fprintf(stderr, "mc: unknown -dump option %s\n", sub.c_str()); return 1; }
+                s += sub.size();
+            }
+            if (i + 1 >= argc) { fprintf(stderr, "mc: -dump dot needs a file name\n"); return 1; }
+            dot = argv[++i];
+        }
         else if (arg("-dump")) dump = argv[++i];
         else if (arg("-checkpoint")) ckpt = argv[++i];
         else if (arg("-recover")) recover = argv[++i];
@@ -433,6 +456,7 @@ int main(int argc, char **argv) {
     if (!tla) {
         fprintf(stderr,
                 "usage: mc X.tla [-config X.cfg] [-deadlock] [-dump FILE] [-generic] [-jit] [-unverified] [-device D] [-I DIR]\n"
+                "                [-dump dot[,actionlabels][,colorize] FILE]                               ... and write the state graph (node k = State k of -dump FILE)\n"
                 "                [-maxdistinct N] [-maxlevels N] [-tablelog2 T] [-arena N] [-chunk N]\n"
                 "                [-checkpoint FILE] [-recover FILE] [-gpus P [-torch]]                    check X.tla like `tlc X.tla`\n"
                 "                [-coverage [MINUTES]]                                                    ... and list every action's distinct:generated counts\n"
@@ -442,14 +466,15 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (!simulate && (have_depth || have_seed)) { fprintf(stderr, "mc: %s needs -simulate\n", have_depth ? "-depth" : "-seed"); return 1; }
-    if (simulate) return run_simulation(tla, cfgp, cfg, sim, have_seed, dump ? "-dump" : ckpt ? "-checkpoint" : recover ? "-recover" : nullptr);
+    if (simulate) return run_simulation(tla, cfgp, cfg, sim, have_seed, dump || dot ? "-dump" : ckpt ? "-checkpoint" : recover ? "-recover" : nullptr);
     if (gpus) {  // one rank of `mc X.tla -gpus P`
-        if (dump) { fprintf(stderr, "mc: -dump is not available with -gpus\n"); return 1; }
+        if (dump || dot) { fprintf(stderr, "mc: -dump is not available with -gpus\n"); return 1; }
         return run_rank(tla, cfgp, cfg, atoi(env_rank), gpus, getenv("MC_IDFILE"), ckpt, recover);
     }
     std::vector<char> report(1 << 22);
     static mc_result res;
-    const int rc = mc_check_files_ckpt(tla, cfgp, &cfg, report.data(), report.size(), &res, dump, recover, ckpt);
+    const int rc = dot ? mc_check_files_dumps(tla, cfgp, &cfg, report.data(), report.size(), &res, dump, dot, dot_flags, recover, ckpt)
+                       : mc_check_files_ckpt(tla, cfgp, &cfg, report.data(), report.size(), &res, dump, recover, ckpt);
     if (rc) {
         fprintf(stderr, "mc: %s: %s\n", mc_strerror(rc), mc_last_error());
         return 1;

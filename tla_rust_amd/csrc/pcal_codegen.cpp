@@ -789,7 +789,7 @@ extern "C" void *mc_jit_factory_opts(const void *program /* pcal::Program * */, 
     const std::string csrc = lib + "/../csrc", inc = lib + "/../../include";
     if (!exists(csrc + "/engine.hip")) { mc::set_error("jit: the engine sources are not beside the library (" + csrc + ")"); return nullptr; }
     uint64_t h = fnv(gen);
-    for (const char *f : {"/engine.hip", "/hip_owned.h", "/engine_kernels.h", "/engine_pairs.h", "/engine_sim.h", "/sim_walk.h", "/engine_coverage.h", "/coverage.h", "/spec_gen.h", "/spec_vm.h", "/mc_common.h"}) {
+    for (const char *f : {"/engine.hip", "/hip_owned.h", "/engine_kernels.h", "/engine_pairs.h", "/engine_sim.h", "/sim_walk.h", "/engine_coverage.h", "/coverage.h", "/engine_graph.h", "/graph.h", "/spec_gen.h", "/spec_vm.h", "/mc_common.h"}) {
         struct stat st;
         if (stat((csrc + f).c_str(), &st) == 0) h = (h ^ (uint64_t)st.st_mtime ^ ((uint64_t)st.st_size << 20)) * 0x100000001b3ull;
     }
