@@ -62,6 +62,13 @@ pub struct mc_graph_info {
     pub max_out_degree: u32, pub pad: u32, pub seconds: f64,
 }
 #[repr(C)]
+pub struct mc_scc_info {
+    pub states: u64, pub components: u64, pub nontrivial: u64, pub largest: u64,
+    pub trim_rounds: u32, pub colour_rounds: u32, pub backward_rounds: u32, pub passes: u32, pub seconds: f64,
+}
+#[repr(C)]
+pub struct mc_live_info { pub violated: i32, pub pad: u32, pub fair_components: u64, pub root: u64, pub root_size: u64, pub seconds: f64 }
+#[repr(C)]
 pub struct mc_engine { _private: [u8; 0] }
 #[repr(C)]
 pub struct mc_program { _private: [u8; 0] }
@@ -80,6 +87,13 @@ extern "C" {
     pub fn mc_engine_graph(e: *mut mc_engine, out: *mut mc_graph_info) -> c_int;
     pub fn mc_engine_graph_read(e: *mut mc_engine, first: u64, count: u64, offsets_out: *mut u64, dst_out: *mut u32, action_out: *mut i32,
                                 nedges_inout: *mut usize) -> c_int;
+    // strongly connected components of that graph (scc[i] = the least arena index of state i's component) and `Termination` under weak
+    // fairness of the process instances in the mask (compiled PlusCal programs; include/tlamc.h)
+    pub fn mc_engine_scc(e: *mut mc_engine, out: *mut mc_scc_info) -> c_int;
+    pub fn mc_engine_scc_read(e: *mut mc_engine, first: u64, count: u64, scc_out: *mut u32) -> c_int;
+    pub fn mc_engine_liveness(e: *mut mc_engine, weak_fair_mask: u64, out: *mut mc_live_info) -> c_int;
+    pub fn mc_engine_liveness_trace(e: *mut mc_engine, prefix_out: *mut u32, nprefix_inout: *mut usize, cycle_out: *mut u32,
+                                    ncycle_inout: *mut usize) -> c_int;
     pub fn mc_engine_read_states(e: *mut mc_engine, first: u64, count: u64, out: *mut u8) -> c_int;
     // TLC's checkpoint / -recover (testout1:10): write / reload the states found so far; the next run continues
     pub fn mc_engine_checkpoint(e: *mut mc_engine, path: *const c_char) -> c_int;
@@ -109,6 +123,10 @@ extern "C" {
     pub fn mc_program_translated(p: *const mc_program) -> *const c_char;
     pub fn mc_program_codegen(p: *const mc_program, buf: *mut c_char, cap: usize) -> std::os::raw::c_long;
     pub fn mc_program_invariant(p: *const mc_program, index: c_int) -> *const c_char;
+    // fairness of the algorithm (bit k of the mask: process instance k is weakly fair; *refusal: why Termination cannot be checked, or
+    // null; returns the number of instances) and the cfg's PROPERTY names (null past the last)
+    pub fn mc_program_fairness(p: *const mc_program, weak_fair_mask: *mut u64, refusal: *mut *const c_char) -> c_int;
+    pub fn mc_program_property(p: *const mc_program, index: c_int) -> *const c_char;
     pub fn mc_program_free(p: *mut mc_program);
     pub fn mc_state_bytes(spec: *const mc_spec_desc) -> usize;
     pub fn mc_state_format(spec: *const mc_spec_desc, state: *const u8, buf: *mut c_char, cap: usize) -> c_int;

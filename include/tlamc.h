@@ -46,6 +46,8 @@ extern "C" {
 #define MC_V_BUDGET 5      /* stopped by max_levels / max_distinct                            */
 #define MC_V_ASSUME 6      /* an ASSUME of the module is false (TLC's "No Behavior Spec" mode: a cfg that names neither SPECIFICATION
                             * nor INIT / NEXT — SpecifyingSystems/SimpleMath/SimpleMath.cfg — makes mc_check_files evaluate the ASSUMEs) */
+#define MC_V_LIVENESS 7    /* "Temporal properties were violated": PROPERTY Termination of a fair PlusCal algorithm (mc_check_files only:
+                            * the search's own verdict was MC_V_OK; mc_engine_liveness decided on its state graph)                      */
 
 /* ------------------------------------------------------------------ lowered specs */
 #define MC_SPEC_ATOMIC_ADD 1 /* reference atomic_add.tla:4-23, N adders + checker; params {N}          */
@@ -257,6 +259,50 @@ typedef struct {
 int mc_engine_graph(mc_engine *e, mc_graph_info *out);
 int mc_engine_graph_read(mc_engine *e, uint64_t first, uint64_t count, uint64_t *offsets_out /* count + 1 */, uint32_t *dst_out,
                          int32_t *action_out, size_t *nedges_inout);
+
+/* ------------------------------------------------------------------ strongly connected components, and Termination under weak fairness
+ * mc_engine_scc: the strongly connected components of the graph of mc_engine_graph (built first if it is not), found on the device by
+ * trimming and forward colouring / backward reachability over the CSR arrays and their transpose.  Edges that end where they start
+ * count for nothing: a state is a component of its own unless a cycle through ANOTHER state passes it.  The id of a component is the
+ * least arena index among its states, so mc_engine_scc_read's array is a function of the graph alone.  Every lowering; the errors are
+ * mc_engine_graph's.  Device memory beside the graph: 16 bytes per state and 4 per edge (MC_EARENA with the byte count).
+ * mc_engine_liveness: does every behaviour of  Init /\ [][Next]_vars /\ \A p \in Fair : WF_vars(proc_p)  reach the state in which
+ * all processes are Done (the translation's `Termination`)?  Fair = the process instances whose bit is set in weak_fair_mask (bit k =
+ * instance k, in the order of the slots; mc_program_fairness gives the mask a program's `fair` keywords ask for).  Exact over the
+ * COMPLETE graph: a component C is fair iff every fair process either takes a step u -> v, u # v, inside C or is disabled in some
+ * state of C; the property is violated iff some fair component holds no Done state.  Compiled PlusCal
+ * programs only (MC_ENOSPEC otherwise); MC_ESTATE unless the engine's last search finished without a violation and with an empty
+ * queue; MC_EBADCFG on a sharded engine, and for a mask that names more instances than the program has.  1 byte per edge and 20 per
+ * state more.
+ * mc_engine_liveness_trace: the counterexample of the last violated check as arena indices (mc_engine_read_states turns them into
+ * states).  prefix: a path of the graph from an initial state to the chosen component's least state — the fair component closest to
+ * the initial states.  cycle: a closed walk inside the component from that state (cycle[0] == prefix[last]); the last entry has an
+ * edge back to cycle[0]; for every fair process it takes a real step of the process or passes a state where it is disabled.  0 cycle
+ * entries: the behaviour stutters for ever in prefix[last].  *n*_inout: capacities in, counts out (MC_EBADCFG with the counts when
+ * too small).  Deterministic.  All of this is released where the graph is. */
+typedef struct {
+    uint64_t states;
+    uint64_t components;       /* one-state components included                                      */
+    uint64_t nontrivial;       /* components of more than one state                                  */
+    uint64_t largest;          /* states of the largest component                                    */
+    uint32_t trim_rounds;      /* sweeps launched, in batches of 8 (a batch that changes nothing ends a fixed point) */
+    uint32_t colour_rounds;
+    uint32_t backward_rounds;
+    uint32_t passes;           /* trim + colouring passes that found some nontrivial component       */
+    double   seconds;          /* transpose included, graph build excluded                           */
+} mc_scc_info;
+typedef struct {
+    int32_t  violated;         /* 0: Termination holds, 1: violated                                  */
+    uint32_t pad;
+    uint64_t fair_components;  /* fair components without a Done state                               */
+    uint64_t root;             /* the least id among them (valid when violated)                      */
+    uint64_t root_size;        /* its number of states                                               */
+    double   seconds;          /* per-edge processes, reduction and verdict (components excluded)    */
+} mc_live_info;
+int mc_engine_scc(mc_engine *e, mc_scc_info *out);
+int mc_engine_scc_read(mc_engine *e, uint64_t first, uint64_t count, uint32_t *scc_out);
+int mc_engine_liveness(mc_engine *e, uint64_t weak_fair_mask, mc_live_info *out);
+int mc_engine_liveness_trace(mc_engine *e, uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout);
 /* copy `count` resident states starting at arena index `first` (discovery order: level by level)
  * to the host, mc_state_bytes() bytes each — TLC's "states/" dump, for tests and tooling */
 int mc_engine_read_states(mc_engine *e, uint64_t first, uint64_t count, uint8_t *out);
@@ -584,6 +630,13 @@ const char *mc_program_translated(const mc_program *p);               /* the mod
 long mc_program_codegen(const mc_program *p, char *buf, size_t cap);
 const char *mc_program_invariant(const mc_program *p, int index);     /* name of INVARIANT number index */
 int mc_program_assert_pos(const mc_program *p, int index, int *line, int *col);  /* source position of an assert */
+/* fairness of the algorithm: *weak_fair_mask = the process instances declared `fair` (or all of them, `--fair algorithm`), bit k =
+ * instance k in slot order; returns the number of instances.  *refusal (either may be NULL): NULL when mc_engine_liveness decides
+ * `Termination` for this program, else the reason it cannot (`fair+`, a `+` / `-` label in a fair process, procedures). */
+int mc_program_fairness(const mc_program *p, uint64_t *weak_fair_mask, const char **refusal);
+/* the cfg's PROPERTY / PROPERTIES names, in cfg order; NULL past the last (what a caller that runs the search itself — `mc -gpus` —
+ * must name as NOT checked) */
+const char *mc_program_property(const mc_program *p, int index);
 void mc_program_free(mc_program *p);
 
 /* ------------------------------------------------------------------ helpers (host only) */

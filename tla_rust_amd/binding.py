@@ -10,7 +10,7 @@ LIB_PATH = Path(os.environ["TLAMC_LIB"]) if os.environ.get("TLAMC_LIB") else PKG
 
 MC_MAX_LEVELS = 4096
 SPEC_IDS = {"atomic_add": 1, "pcal_intro": 2, "raft": 3, "ssi": 4, "pcal": 5, "paxos": 6}
-VERDICTS = ["ok", "invariant", "assert", "deadlock", "spec-error", "budget", "assume"]
+VERDICTS = ["ok", "invariant", "assert", "deadlock", "spec-error", "budget", "assume", "liveness"]
 MC_F_DEADLOCK, MC_F_TRACE, MC_F_TIMING, MC_F_MATRIX, MC_F_NOPROBE, MC_F_NOFAMILY = 1, 2, 4, 8, 16, 32
 MC_F_COVERAGE = 1 << 24  # TLC's -coverage: per-action counts (Engine(coverage=True), Engine.coverage(); include/tlamc.h)
 MC_F_UNVERIFIED = 512  # use the built-in lowering even when the module a wrapper EXTENDS cannot be found (include/tlamc.h)
@@ -99,6 +99,19 @@ class GraphInfo(C.Structure):
                 ("seconds", C.c_double)]
 
 
+class SccInfo(C.Structure):
+    """mc_scc_info"""
+    _fields_ = [("states", C.c_uint64), ("components", C.c_uint64), ("nontrivial", C.c_uint64), ("largest", C.c_uint64),
+                ("trim_rounds", C.c_uint32), ("colour_rounds", C.c_uint32), ("backward_rounds", C.c_uint32), ("passes", C.c_uint32),
+                ("seconds", C.c_double)]
+
+
+class LiveInfo(C.Structure):
+    """mc_live_info"""
+    _fields_ = [("violated", C.c_int32), ("pad", C.c_uint32), ("fair_components", C.c_uint64), ("root", C.c_uint64),
+                ("root_size", C.c_uint64), ("seconds", C.c_double)]
+
+
 MC_DOT_ACTIONLABELS, MC_DOT_COLORIZE = 1, 2   # mc_check_files_dot
 
 
@@ -153,6 +166,10 @@ def lib():
     L.mc_engine_coverage.argtypes = [C.c_void_p, C.POINTER(ActionCoverage), C.POINTER(C.c_size_t)]
     L.mc_engine_graph.argtypes = [C.c_void_p, C.POINTER(GraphInfo)]
     L.mc_engine_graph_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+    L.mc_engine_scc.argtypes = [C.c_void_p, C.POINTER(SccInfo)]
+    L.mc_engine_scc_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.mc_engine_liveness.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(LiveInfo)]
+    L.mc_engine_liveness_trace.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_size_t)]
     L.mc_engine_read_states.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
     L.mc_engine_debug_reexpand.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_double)]
     L.mc_engine_destroy.argtypes = [C.c_void_p]
@@ -231,6 +248,9 @@ def lib():
         L.mc_program_translated.restype = C.c_char_p
         L.mc_program_invariant.argtypes = [C.c_void_p, C.c_int]
         L.mc_program_invariant.restype = C.c_char_p
+        L.mc_program_fairness.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_char_p)]
+        L.mc_program_property.argtypes = [C.c_void_p, C.c_int]
+        L.mc_program_property.restype = C.c_char_p
         L.mc_program_free.argtypes = [C.c_void_p]
         L.mc_program_free.restype = None
     _lib = L
@@ -387,6 +407,40 @@ class Engine:
             done += len(d)
         assert done == info.edges, (done, info.edges)
         return info, offsets, dst, act
+
+    def scc(self):
+        """mc_engine_scc + mc_engine_scc_read: (info, scc) — the strongly connected components of the state graph of the last search (built
+        if it is not), found on the device; scc[i] is the least arena index of state i's component (numpy uint32).  info: states,
+        components, nontrivial, largest, trim_rounds, colour_rounds, backward_rounds, passes, seconds."""
+        si = SccInfo()
+        _check(lib().mc_engine_scc(self._h, C.byref(si)), "mc_engine_scc")
+        return Result((k, getattr(si, k)) for k, _ in SccInfo._fields_), self.scc_read(0, si.states)
+
+    def scc_read(self, first, count):
+        import numpy as np
+        out = np.zeros(max(1, count), dtype=np.uint32)
+        _check(lib().mc_engine_scc_read(self._h, first, count, out.ctypes.data), "mc_engine_scc_read")
+        return out[:count]
+
+    def liveness(self, weak_fair_mask):
+        """mc_engine_liveness: `Termination` under weak fairness of the process instances in the mask (Program.fair_mask), decided on the
+        complete state graph of the last search: a dict with violated, fair_components, root, root_size, seconds."""
+        li = LiveInfo()
+        _check(lib().mc_engine_liveness(self._h, weak_fair_mask, C.byref(li)), "mc_engine_liveness")
+        return Result((k, getattr(li, k)) for k, _ in LiveInfo._fields_ if k != "pad")
+
+    def liveness_trace(self):
+        """mc_engine_liveness_trace: (prefix, cycle) of the last violated liveness check, as lists of arena indices: a path from an
+        initial state to cycle[0], and a closed walk (its last state has an edge to cycle[0]); an empty cycle = stuttering for ever
+        in prefix[-1]."""
+        import numpy as np
+        np_, nc = C.c_size_t(0), C.c_size_t(0)
+        rc = lib().mc_engine_liveness_trace(self._h, None, C.byref(np_), None, C.byref(nc))   # (MC_EBADCFG + the counts)
+        if rc != -1:
+            _check(rc, "mc_engine_liveness_trace")
+        prefix, cycle = np.zeros(max(1, np_.value), dtype=np.uint32), np.zeros(max(1, nc.value), dtype=np.uint32)
+        _check(lib().mc_engine_liveness_trace(self._h, prefix.ctypes.data, C.byref(np_), cycle.ctypes.data, C.byref(nc)), "mc_engine_liveness_trace")
+        return prefix[:np_.value].tolist(), cycle[:nc.value].tolist()
 
     def trace(self):
         """[(action name, state text)] of the last counterexample (of the last run or simulation)."""
@@ -660,6 +714,10 @@ class Program:
         d = SpecDesc()
         _check(lib().mc_program_spec(h, C.byref(d)), "mc_program_spec")
         self.params = [int(d.params[0])]
+        mask, why = C.c_uint64(0), C.c_char_p()
+        self.ninst = _check(lib().mc_program_fairness(h, C.byref(mask), C.byref(why)), "mc_program_fairness")
+        self.fair_mask = int(mask.value)             # bit k: process instance k (slot order) is weakly fair
+        self.live_refusal = why.value.decode() if why.value else None   # why Engine.liveness cannot decide Termination for it (None: it can)
 
     def translated(self):
         return lib().mc_program_translated(self._h).decode()
@@ -711,6 +769,9 @@ class ResolvedSpec:
         self.spec = names[int(d.spec_id)]
         self.params = [int(d.params[i]) for i in range(d.nparams)]
         self._prog = prog
+        self.properties = []   # the cfg's PROPERTY names of a compiled PlusCal program: a sharded search names them as NOT checked
+        while prog and lib().mc_program_property(prog, len(self.properties)):
+            self.properties.append(lib().mc_program_property(prog, len(self.properties)).decode())
 
     def close(self):
         if self._prog:

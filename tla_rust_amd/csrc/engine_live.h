@@ -1,0 +1,264 @@
+// engine_live.h — the DEVICE half of the strongly-connected-components pass (mc_engine_scc) and of the fairness check built on it
+// (mc_engine_liveness).  Included by engine.hip only (inside namespace mc, after engine_graph.h).  Everything here is a consumer of the
+// CSR arrays of mc_engine_graph (offsets / dst) and of nothing else, except k_live_proc, which walks the arena once more to say which
+// process instance takes each edge.  The rule itself is liveness.h's, MC_HD code the host runs too.
+//
+//   transpose   k_live_indegree (atomics) -> hipcub exclusive scan in 64 bits -> k_live_tfill.  Edges that end where they start are left
+//               out: no consumer wants them.  A row of the transpose is in no particular order (the fill's atomics decide); every reader
+//               either looks at the whole row or takes its least entry.
+//   SCC         trim, then colouring, repeated until no state is live (scc[v] == SCC_LIVE):
+//                 k_scc_trim     a live state with no live in-edge or no live out-edge is its own component
+//                 k_scc_colour   colour[v] = max(colour[v], colour[u]) over the live in-edges u -> v, to a fixed point: the largest arena
+//                                index that reaches v.  The states with colour[v] == v are roots (k_scc_roots).
+//                 k_scc_back     a live state with an out-edge to a state already given to ITS colour's root joins that root: backward
+//                                reachability from the root inside its colour class = the root's component
+//               then k_scc_least / k_scc_renumber: scc[v] = the LEAST arena index of v's component (roots are the largest), so the
+//               numbering is a function of the graph alone; k_scc_sizes counts the members.
+//               One lane per state over its CSR row; rows of one wavefront's lanes have any lengths (every loop is the lane's own, no
+//               wavefront operation inside).  A sweep that changed something sets a per-workgroup bit in LDS, and one lane of the
+//               workgroup raises the device flag; the host reads the flag once per SCC_BATCH sweeps.  Sweeps update in place: a lane may
+//               see a value another lane wrote in the same sweep — every update is monotone (live -> assigned, colours only grow), so that
+//               only makes the fixed point come sooner.
+//   fairness    k_live_proc<S>   the walk of graph_walk (same slot loop, same graph_edge decisions: edge k of a row is the k-th counted
+//                                slot) writes proc[] beside act[]
+//               k_live_reduce    per state the en / taken masks and the Done flag (live_state), OR-ed into the component's entry at
+//                                scc[v]: plain stores for one-state components, else one atomic per set of lanes that agree on it
+//               k_live_verdict   per component root the rule (live_violates); the number of fair non-Done components and the least root
+//
+// Memory, beside the graph's 8 bytes per state and 6 per edge: 16 bytes per state (transpose offsets 8, scc 4, colour / size 4) and 4 per
+// edge (transpose) for mc_engine_scc, 4 more per state while the transpose is built; mc_engine_liveness adds 1 byte per edge (proc) and 20
+// per state (taken 8, disabled 8, Done 4).
+#ifndef TLAMC_ENGINE_LIVE_H
+#define TLAMC_ENGINE_LIVE_H
+
+#include "liveness.h"
+
+namespace mc {
+
+// (the kernels that are no templates are `static`: engine.hip is compiled once per group of lowerings, and every copy has its own)
+
+constexpr uint32_t SCC_LIVE = 0xffffffffu;   // scc[v] of a state no component has been found for yet
+constexpr int SCC_BATCH = 8;                 // sweeps launched between two reads of the "changed" flag
+
+struct LiveCounters {
+    unsigned long long components, nontrivial, fair_components;
+    unsigned largest, first_root;   // first_root: the least root among the fair non-Done components, ~0u = none
+};
+
+// the workgroup's "changed" bit: LDS, then one store to the device flag
+__device__ __forceinline__ void live_raise(bool changed, unsigned *flag) {
+    __shared__ unsigned wg_changed;
+    if (threadIdx.x == 0) wg_changed = 0;
+    __syncthreads();
+    if (changed) wg_changed = 1;   // (every writer writes 1)
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_changed) *flag = 1;
+}
+
+// ---- transpose
+static __global__ void __launch_bounds__(256)
+k_live_indegree(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, uint32_t *indeg) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    for (uint64_t k = offsets[v], end = offsets[v + 1]; k < end; ++k) {
+        const uint32_t d = dst[k];
+        if (d != (uint32_t)v && d < n) atomicAdd(&indeg[d], 1u);
+    }
+}
+static __global__ void __launch_bounds__(256)
+k_live_tfill(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const uint64_t *__restrict__ toff,
+             uint32_t *cursor, uint32_t *__restrict__ tsrc) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    for (uint64_t k = offsets[v], end = offsets[v + 1]; k < end; ++k) {
+        const uint32_t d = dst[k];
+        if (d == (uint32_t)v || d >= n) continue;
+        const uint64_t at = toff[d] + atomicAdd(&cursor[d], 1u);
+        if (at < toff[d + 1]) tsrc[at] = (uint32_t)v;   // (k_live_indegree counted this edge: the bound holds, and is checked all the same)
+    }
+}
+
+// ---- SCC
+static __global__ void __launch_bounds__(256)
+k_scc_trim(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const uint64_t *__restrict__ toff,
+           const uint32_t *__restrict__ tsrc, uint32_t *scc, unsigned *flag) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool changed = false;
+    if (v < n && scc[v] == SCC_LIVE) {
+        bool out = false, in = false;
+        for (uint64_t k = offsets[v], end = offsets[v + 1]; k < end && !out; ++k) {
+            const uint32_t d = dst[k];
+            out = d != (uint32_t)v && d < n && scc[d] == SCC_LIVE;
+        }
+        for (uint64_t k = toff[v], end = toff[v + 1]; out && k < end && !in; ++k) in = scc[tsrc[k]] == SCC_LIVE;   // (the transpose holds no self loop)
+        if (!out || !in) { scc[v] = (uint32_t)v; changed = true; }
+    }
+    live_raise(changed, flag);
+}
+static __global__ void __launch_bounds__(256)
+k_scc_colour_init(uint64_t n, const uint32_t *__restrict__ scc, uint32_t *__restrict__ colour, unsigned *flag) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = v < n && scc[v] == SCC_LIVE;
+    if (v < n) colour[v] = (uint32_t)v;
+    live_raise(live, flag);   // (here the flag says: some state is still live)
+}
+static __global__ void __launch_bounds__(256)
+k_scc_colour(uint64_t n, const uint64_t *__restrict__ toff, const uint32_t *__restrict__ tsrc, const uint32_t *__restrict__ scc,
+             uint32_t *colour, unsigned *flag) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool changed = false;
+    if (v < n && scc[v] == SCC_LIVE) {
+        const uint32_t mine = colour[v];
+        uint32_t c = mine;
+        for (uint64_t k = toff[v], end = toff[v + 1]; k < end; ++k) {
+            const uint32_t u = tsrc[k];
+            if (scc[u] != SCC_LIVE) continue;
+            const uint32_t cu = colour[u];
+            c = cu > c ? cu : c;
+        }
+        if (c > mine) { colour[v] = c; changed = true; }
+    }
+    live_raise(changed, flag);
+}
+static __global__ void __launch_bounds__(256)
+k_scc_roots(uint64_t n, uint32_t *__restrict__ scc, const uint32_t *__restrict__ colour) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v < n && scc[v] == SCC_LIVE && colour[v] == (uint32_t)v) scc[v] = (uint32_t)v;
+}
+// (a root is live when its colour is computed, so no state was given to it before this round: scc[d] == colour[v] means "d reaches the
+// root of v's colour class and is of that class")
+static __global__ void __launch_bounds__(256)
+k_scc_back(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, uint32_t *scc,
+           const uint32_t *__restrict__ colour, unsigned *flag) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool changed = false;
+    if (v < n && scc[v] == SCC_LIVE) {
+        const uint32_t c = colour[v];
+        for (uint64_t k = offsets[v], end = offsets[v + 1]; k < end; ++k) {
+            const uint32_t d = dst[k];
+            if (d != (uint32_t)v && d < n && scc[d] == c && colour[d] == c) { scc[v] = c; changed = true; break; }
+        }
+    }
+    live_raise(changed, flag);
+}
+static __global__ void __launch_bounds__(256)
+k_scc_least(uint64_t n, const uint32_t *__restrict__ scc, uint32_t *least) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    const uint32_t r = scc[v];
+    if (r < n && r != (uint32_t)v) atomicMin(&least[r], (uint32_t)v);   // (a root is its component's LARGEST index: only smaller ones matter)
+}
+static __global__ void __launch_bounds__(256)
+k_scc_renumber(uint64_t n, uint32_t *__restrict__ scc, const uint32_t *__restrict__ least) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    const uint32_t r = scc[v];
+    if (r < n) { const uint32_t l = least[r]; scc[v] = l < r ? l : r; }
+}
+static __global__ void __launch_bounds__(256)
+k_scc_sizes(uint64_t n, const uint32_t *__restrict__ scc, uint32_t *size) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    const uint32_t r = scc[v];
+    if (r < n) atomicAdd(&size[r], 1u);
+}
+static __global__ void __launch_bounds__(256)
+k_scc_stats(uint64_t n, const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, LiveCounters *lc) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool root = v < n && scc[v] == (uint32_t)v;
+    const unsigned sz = root ? size[v] : 0u;
+    const unsigned roots = (unsigned)__popcll(__ballot(root)), big = (unsigned)__popcll(__ballot(sz > 1)), wmax = wave_max_u32(sz);
+    if ((threadIdx.x & 63) == 0 && roots) {
+        atomicAdd(&lc->components, (unsigned long long)roots);
+        if (big) atomicAdd(&lc->nontrivial, (unsigned long long)big);
+        atomicMax(&lc->largest, wmax);
+    }
+}
+
+// ---- fairness
+// proc[] beside act[]: graph_walk's loop once more (the chunks, the columns, the wavefront's largest nslots, graph_edge), writing the
+// process instance of every counted slot at the edge's place
+template <class S>
+__global__ void __launch_bounds__(256)
+k_live_proc(typename S::Params prm, const uint64_t *__restrict__ arena, uint64_t lo, uint64_t hi, uint64_t ncols,
+            const uint64_t *__restrict__ table, uint64_t seen, const uint64_t *__restrict__ offsets, int8_t *__restrict__ proc) {
+    const uint64_t col = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t idx = (lo & ~63ull) + col;
+    const bool active = col < ncols && idx >= lo && idx < hi;
+    const CWordRef s = arena_cref(arena, active ? idx : lo, S::words(prm));
+    typename S::Local loc;
+    int ns = 0;
+    uint64_t out = 0, end = 0;
+    if (active) {
+        S::load(prm, s, loc);
+        ns = S::nslots(prm, loc);
+        out = offsets[idx];
+        end = offsets[idx + 1];
+    }
+    const int wns = (int)wave_max_u32((unsigned)ns);
+    for (int slot = 0; slot < wns; ++slot) {
+        if (slot >= ns) continue;   // (no wavefront operation inside the loop)
+        uint64_t f = 0, pos;
+        const unsigned kind = graph_edge(S::eval(prm, loc, s, slot, f), f, table, seen, pos);
+        if (kind != GE_SELF && kind != GE_EDGE) continue;
+        if (out < end) proc[out] = (int8_t)LiveProc<S>::of(prm, slot);
+        ++out;
+    }
+}
+
+__device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
+    return v;
+}
+
+static __global__ void __launch_bounds__(256)
+k_live_reduce(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ proc,
+              const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, uint64_t all, unsigned long long *taken,
+              unsigned long long *disabled, unsigned *done) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = v < n;
+    uint64_t en = 0, tk = 0;
+    bool dn = false;
+    uint32_t comp = 0;
+    if (active) {
+        const uint64_t o = offsets[v];
+        live_state((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc, &en, &tk, &dn);
+        comp = scc[v];
+    }
+    const uint64_t dis = active ? live_disabled(all, en) : 0;
+    // a one-state component has one writer; the entries were cleared before the launch
+    const bool alone = active && size[comp] == 1;
+    if (alone) { taken[comp] = tk; disabled[comp] = dis; done[comp] = dn ? 1u : 0u; }
+    // the others: one atomic per set of lanes that agree on the component (the loop's condition is the same in every lane)
+    unsigned long long rest = __ballot(active && !alone);
+    const unsigned lane = threadIdx.x & 63;
+    while (rest) {
+        const int lead = __ffsll((long long)rest) - 1;
+        const uint32_t c0 = (uint32_t)__shfl((int)comp, lead);
+        const bool same = active && !alone && comp == c0;
+        const unsigned long long t = wave_or_u64(same ? tk : 0ull), d = wave_or_u64(same ? dis : 0ull);
+        const unsigned long long dd = __ballot(same && dn);
+        if ((int)lane == lead) {
+            if (t) atomicOr(&taken[c0], t);
+            if (d) atomicOr(&disabled[c0], d);
+            if (dd) atomicOr(&done[c0], 1u);
+        }
+        rest &= ~__ballot(same);
+    }
+}
+
+static __global__ void __launch_bounds__(256)
+k_live_verdict(uint64_t n, const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, const unsigned long long *__restrict__ taken,
+               const unsigned long long *__restrict__ disabled, const unsigned *__restrict__ done, uint64_t all, uint64_t fair, LiveCounters *lc) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool bad = v < n && scc[v] == (uint32_t)v && live_violates(all, fair, taken[v], disabled[v], done[v] != 0, size[v]);
+    const unsigned long long b = __ballot(bad);
+    if (b && (int)(threadIdx.x & 63) == __ffsll((long long)b) - 1) {   // (the first bad lane of a wavefront holds its least root)
+        atomicAdd(&lc->fair_components, (unsigned long long)__popcll(b));
+        atomicMin(&lc->first_root, (unsigned)v);
+    }
+}
+
+}  // namespace mc
+
+#endif  // TLAMC_ENGINE_LIVE_H

@@ -38,7 +38,17 @@ extern "C" void mc_set_error_internal(const char *msg);  // engine.hip
 
 struct mc_program {
     pcal::Program prog;
+    std::vector<std::string> properties;   // the cfg's PROPERTY / PROPERTIES names (mc_program_property)
 };
+const char *mc_program_property(const mc_program *p, int index) {
+    return p && index >= 0 && (size_t)index < p->properties.size() ? p->properties[(size_t)index].c_str() : nullptr;
+}
+int mc_program_fairness(const mc_program *p, uint64_t *weak_fair_mask, const char **refusal) {
+    if (!p) return MC_EBADCFG;
+    if (weak_fair_mask) *weak_fair_mask = p->prog.fair_mask;
+    if (refusal) *refusal = p->prog.live_refusal.empty() ? nullptr : p->prog.live_refusal.c_str();
+    return p->prog.ninst;
+}
 extern "C" long pcal_codegen_text(const pcal::Program *p, char *buf, size_t cap);   // pcal_codegen.cpp
 
 namespace {
@@ -623,12 +633,14 @@ int mc_program_compile(const char *tla_text, const char *cfg_text, mc_program **
     if (!tla_text || !out) return MC_EBADCFG;
     *out = nullptr;
     pcal::Config cf;
+    std::vector<std::string> properties;
     if (cfg_text) {
         mc_cfg *c = nullptr;
         const int rc = mc_cfg_parse(cfg_text, strlen(cfg_text), &c);
         if (rc) return rc;
         cf.invariants = c->invariants;
         cf.constraints = c->constraints;
+        properties = c->properties;
         for (const auto &k : c->constants) {
             if (k.replacement) { mc_cfg_free(c); return fe_fail(MC_ENOSPEC, "CONSTANT %s <- ...: definition overrides are not supported for PlusCal programs", k.name.c_str()); }
             cf.constants.push_back({k.name, to_const(k.value)});
@@ -642,6 +654,7 @@ int mc_program_compile(const char *tla_text, const char *cfg_text, mc_program **
     std::string err = pcal::parse_module(text, m);
     if (!err.empty()) return fe_fail(MC_EPARSE, "PlusCal: %s", err.c_str());
     auto *p = new mc_program();
+    p->properties = properties;
     err = pcal::compile(m, text, cf, p->prog);
     if (!err.empty()) { delete p; return fe_fail(MC_ENOSPEC, "PlusCal: %s", err.c_str()); }
     *out = p;
@@ -964,6 +977,7 @@ struct Resolved {
     std::string tla, module, def_text, def_module_name;  // def_*: text + name of the module that holds the action definitions
     std::string warning;  // printed at the top of the report (MC_F_UNVERIFIED)
     int check_deadlock = -1;   // the cfg's CHECK_DEADLOCK statement (-1: none)
+    std::vector<std::string> properties;   // the cfg's PROPERTY / PROPERTIES (a compiled PlusCal program: `Termination` is checked after the search)
     ~Resolved() { if (prog) mc_program_free(prog); }
 };
 }  // namespace
@@ -994,6 +1008,7 @@ static int resolve_files(const char *tla_path, const char *cfg_path, unsigned fl
     int rc = mc_cfg_parse(cfgtext.c_str(), cfgtext.size(), &c);
     if (rc) return rc;
     R.check_deadlock = c->check_deadlock;
+    R.properties = c->properties;
     memset(&d, 0, sizeof d);
     // A PlusCal module goes through the hand lowering when its algorithm text is one the registry knows, and
     // through the compiled program (spec_vm.h) otherwise — or always with MC_F_GENERIC (A/B of the two paths).
@@ -1544,6 +1559,74 @@ static int check_files_impl(const char *tla_path, const char *cfg_path, const mc
     if (!R.warning.empty()) o.put("%s", R.warning.c_str());
     o.put("Finished computing initial states: %llu distinct state%s generated.\n", (unsigned long long)res->level_distinct[0],
           res->level_distinct[0] == 1 ? "" : "s");
+    // PROPERTY Termination of a compiled PlusCal program: decided on the state graph of the engine that finished the search
+    // (mc_engine_liveness); whatever is not checked is named, BEFORE the verdict it qualifies
+    std::vector<uint32_t> live_prefix, live_cycle;
+    bool live_violated = false;
+    if (generic && !R.properties.empty()) {
+        uint64_t fair = 0;
+        const char *refusal = nullptr;
+        mc_program_fairness(prog, &fair, &refusal);
+        const bool complete = res->verdict == MC_V_OK && res->queue_left == 0;
+        bool checked = false;   // Termination was decided (a cfg that names it twice is checked once)
+        for (const auto &name : R.properties) {
+            std::string why;
+            if (name != "Termination") why = "only the translation's Termination is supported";
+            else if (refusal) why = refusal;
+            else if (!complete) why = "the search did not finish (a violation or a budget): liveness needs the complete state graph";
+            if (!why.empty()) {   // refused: named and counted
+                res->unchecked_properties++;
+                o.put("Warning: temporal property %s NOT checked: %s.\n", name.c_str(), why.c_str());
+                continue;
+            }
+            if (checked) continue;
+            checked = true;
+            mc_live_info li;
+            if ((rc = mc_engine_liveness(e, fair, &li))) { mc_engine_destroy(e); return rc; }
+            if (!li.violated) continue;
+            size_t np = 0, nc = 0;
+            rc = mc_engine_liveness_trace(e, nullptr, &np, nullptr, &nc);   // (MC_EBADCFG with the counts is the answer to no buffers)
+            if (rc != MC_EBADCFG || !np) { mc_engine_destroy(e); return rc ? rc : MC_ESTATE; }
+            live_prefix.resize(np);
+            live_cycle.resize(nc ? nc : 1);
+            if ((rc = mc_engine_liveness_trace(e, live_prefix.data(), &np, live_cycle.data(), &nc))) { mc_engine_destroy(e); return rc; }
+            live_prefix.resize(np);
+            live_cycle.resize(nc);
+            live_violated = true;
+        }
+    }
+    if (live_violated) {
+        res->verdict = MC_V_LIVENESS;
+        res->trace_len = (uint32_t)(live_prefix.size() + (live_cycle.empty() ? 0 : live_cycle.size() - 1));
+    }
+    if (res->verdict == MC_V_LIVENESS) {   // TLC's layout for a liveness counterexample
+        const size_t W = mc_state_bytes(&d);
+        std::vector<uint8_t> row(W);
+        std::vector<char> txt(1 << 16);
+        auto action_of = [&](uint32_t u, uint32_t v) -> const char * {   // the action of the first edge u -> v
+            size_t ne = 0;
+            mc_engine_graph_read(e, u, 1, nullptr, nullptr, nullptr, &ne);
+            std::vector<uint64_t> off(2);
+            std::vector<uint32_t> dst(ne ? ne : 1);
+            std::vector<int32_t> act(ne ? ne : 1);
+            if ((rc = mc_engine_graph_read(e, u, 1, off.data(), dst.data(), act.data(), &ne))) return "?";   // (rc ends the report below)
+            for (size_t k = 0; k < ne; k++) if (dst[k] == v) return mc_action_name(&d, act[k]);
+            rc = fe_fail(MC_ESTATE, "liveness counterexample: no edge %u -> %u in the state graph", u, v);
+            return "?";
+        };
+        std::vector<uint32_t> path = live_prefix;
+        for (size_t k = 1; k < live_cycle.size(); k++) path.push_back(live_cycle[k]);
+        o.put("Error: Temporal properties were violated.\n\nError: The following behavior constitutes a counter-example:\n\n");
+        for (size_t k = 0; k < path.size(); k++) {
+            if ((rc = mc_engine_read_states(e, path[k], 1, row.data()))) { mc_engine_destroy(e); return rc; }
+            mc_state_format(&d, row.data(), txt.data(), txt.size());
+            if (!k) o.put("State 1: <Initial predicate>\n%s\n\n", txt.data());
+            else o.put("State %zu: <%s>\n%s\n\n", k + 1, action_of(path[k - 1], path[k]), txt.data());
+        }
+        if (live_cycle.empty()) o.put("State %zu: Stuttering\n", path.size() + 1);
+        else o.put("Back to state %zu: <%s>\n", live_prefix.size(), action_of(path.back(), live_cycle[0]));
+        if (rc) { mc_engine_destroy(e); return rc; }
+    } else
     if (res->verdict == MC_V_OK || res->verdict == MC_V_BUDGET) {
         if (res->verdict == MC_V_OK) o.put("Model checking completed. No error has been found.\n");
         else o.put("Search stopped by the level/state budget; no error has been found so far.\n");

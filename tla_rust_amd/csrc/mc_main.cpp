@@ -251,6 +251,12 @@ static int run_rank(const char *tla, const char *cfgp, mc_config cfg, int rank, 
     if (!rc && rank == 0) {  // TLC's closing lines (README.md:319-320, testout2:260-266), as tla_rust_amd/mc_multi.py prints them
         const unsigned long long n0 = res.levels ? (unsigned long long)res.level_distinct[0] : 0ull;
         printf("Finished computing initial states: %llu distinct state%s generated.\n", n0, n0 == 1 ? "" : "s");
+        // a sharded search keeps no state graph in one place: the cfg's temporal properties are named, never passed over
+        for (int k = 0; prog && mc_program_property(prog, k); k++) {
+            res.unchecked_properties++;
+            printf("Warning: temporal property %s NOT checked: the search is sharded over %d engines (-gpus); liveness needs the state graph of one engine.\n",
+                   mc_program_property(prog, k), world);
+        }
         if (res.verdict == MC_V_OK) printf("Model checking completed. No error has been found.\n");
         else if (res.verdict == MC_V_BUDGET) printf("Search stopped by the level/state budget; no error has been found so far.\n");
         if (ckpt_done) printf("-- Checkpointing of run %s completed.\n", ckpt);  // testout1:10 (one file per rank: %s.rank<r>of<P>)
@@ -460,9 +466,11 @@ int main(int argc, char **argv) {
                 "                [-maxdistinct N] [-maxlevels N] [-tablelog2 T] [-arena N] [-chunk N]\n"
                 "                [-checkpoint FILE] [-recover FILE] [-gpus P [-torch]]                    check X.tla like `tlc X.tla`\n"
                 "                [-coverage [MINUTES]]                                                    ... and list every action's distinct:generated counts\n"
+                "                a PlusCal X.tla whose X.cfg says PROPERTY Termination: checked under the algorithm's weak fairness (`fair process`,\n"
+                "                `--fair algorithm`) on the complete state graph\n"
                 "       mc X.tla -simulate [num=N] [-depth D] [-seed S] [...]                             random walks like `tlc -simulate`\n"
                 "       mc --transpile X.tla [Y.tla ...]                                                  translate like `pcal2tla`\n"
-                "exit status: 0 no error, 12 invariant / assertion violated, 11 deadlock, 1 anything else\n");
+                "exit status: 0 no error, 12 invariant / assertion violated, 11 deadlock, 13 liveness (Termination) violated, 1 anything else\n");
         return 1;
     }
     if (!simulate && (have_depth || have_seed)) { fprintf(stderr, "mc: %s needs -simulate\n", have_depth ? "-depth" : "-seed"); return 1; }
@@ -481,5 +489,6 @@ int main(int argc, char **argv) {
     }
     fputs(report.data(), stdout);
     if (res.verdict == MC_V_OK || res.verdict == MC_V_BUDGET) return 0;
+    if (res.verdict == MC_V_LIVENESS) return 13;   // TLC's exit status for a violated liveness property
     return res.verdict == MC_V_DEADLOCK ? 11 : 12;
 }

@@ -510,6 +510,7 @@ struct Parser {
     }
     std::vector<Macro> *macros = nullptr;
     bool in_macro = false;
+    bool saw_label_mod = false;   // a `+` / `-` label modifier since the flag was last cleared (one process body)
     std::vector<SP> stmts() {
         std::vector<SP> v;
         while (!at_block_end()) {
@@ -603,7 +604,7 @@ struct Parser {
         if (cur().t == Tok::IDENT && peek().t == Tok::SYM && peek().s == ":") {
             s->label = t[i].s;
             i += 2;
-            if (is_sym("+") || is_sym("-")) i++;  // fairness modifiers carry no meaning for safety checking
+            if (is_sym("+") || is_sym("-")) { s->fair_mod = cur().s[0]; saw_label_mod = true; i++; }  // fairness modifiers: no meaning for safety checking; liveness refuses them
         }
         s->pos = {cur().line, cur().col};
         if (cur().t != Tok::IDENT) fail("expected a statement");
@@ -757,7 +758,7 @@ struct Parser {
         if (cur().t == Tok::IDENT && peek().t == Tok::SYM && peek().s == ":") {
             s->label = t[i].s;
             i += 2;
-            if (is_sym("+") || is_sym("-")) i++;
+            if (is_sym("+") || is_sym("-")) { s->fair_mod = cur().s[0]; saw_label_mod = true; i++; }
         }
         s->pos = {cur().line, cur().col};
         if (is_sym("{")) {  // a compound statement in a sequence: its statements join the sequence
@@ -838,10 +839,13 @@ struct Parser {
             m.procs.push_back(p);
         } else {
             while (is_id("process") || is_id("fair")) {
-                if (is_id("fair")) { i++; if (is_sym("+")) i++; }
+                int fair = 0;
+                if (is_id("fair")) { i++; fair = 1; if (is_sym("+")) { i++; fair = 2; } }
                 expect_id("process");
                 expect_sym("(");
                 Proc p;
+                p.fair = fair;
+                saw_label_mod = false;
                 p.name = ident("a process name");
                 if (is_sym("=")) { i++; }
                 else { expect_sym("\\in"); p.is_set = true; }
@@ -849,6 +853,7 @@ struct Parser {
                 expect_sym(")");
                 if (is_id("variables") || is_id("variable")) { i++; p.locals = vardecls(); }
                 p.body = c_block();
+                p.label_mods = saw_label_mod;
                 m.procs.push_back(p);
             }
             if (m.procs.empty()) fail("expected `{` or `process`");
@@ -950,9 +955,12 @@ struct Parser {
             m.procs.push_back(p);
         } else {
             while (is_id("process") || is_id("fair")) {
-                if (is_id("fair")) { i++; if (is_sym("+")) i++; }
+                int fair = 0;
+                if (is_id("fair")) { i++; fair = 1; if (is_sym("+")) { i++; fair = 2; } }
                 expect_id("process");
                 Proc p;
+                p.fair = fair;
+                saw_label_mod = false;
                 p.name = ident("a process name");
                 if (is_sym("=")) { i++; }
                 else { expect_sym("\\in"); p.is_set = true; }
@@ -963,6 +971,7 @@ struct Parser {
                 expect_id("end");
                 expect_id("process");
                 if (is_sym(";")) i++;
+                p.label_mods = saw_label_mod;
                 m.procs.push_back(p);
             }
             if (m.procs.empty()) fail("expected `begin` or `process`");
@@ -2243,7 +2252,7 @@ std::string parse_module(const std::string &text, Module &m) {
         size_t a = text.find("--algorithm");
         const size_t fa = text.find("--fair algorithm");
         size_t kw_len = strlen("--algorithm");
-        if (fa != std::string::npos && (a == std::string::npos || fa < a)) { a = fa; kw_len = strlen("--fair algorithm"); }
+        if (fa != std::string::npos && (a == std::string::npos || fa < a)) { a = fa; kw_len = strlen("--fair algorithm"); m.fair_algorithm = true; }
         if (a == std::string::npos) return "no PlusCal algorithm (`--algorithm`) in the module";
         const size_t cbeg = text.rfind("(*", a);
         if (cbeg == std::string::npos) return "the PlusCal algorithm must be inside a (* ... *) comment";
@@ -2949,7 +2958,26 @@ std::string translate(const Module &m) {
         o += "           \\/ (* Disjunct to prevent deadlock on termination *)\n";
         o += "              ((\\A self \\in ProcSet: pc[self] = \"Done\") /\\ UNCHANGED vars)\n\n";
     }
-    o += "Spec == Init /\\ [][Next]_vars\n\n";
+    {   // pcal2tla's fairness conjuncts: WF_vars(Next) for a uniprocess `--fair algorithm`, one conjunct per fair process otherwise
+        // (approximated for what liveness checking refuses: `+` / `-` labels do not restrict or strengthen the conjunct label by label, and
+        //  procedures get no conjuncts of their own, as pcal2tla would write them)
+        std::vector<std::string> fairness;
+        if (!multi) { if (m.fair_algorithm) fairness.push_back("WF_vars(Next)"); }
+        else
+            for (const auto &p : m.procs) {
+                const int fair = p.fair ? p.fair : m.fair_algorithm ? 1 : 0;
+                if (!fair) continue;
+                const std::string f = fair == 2 ? "SF" : "WF";
+                if (p.is_set) fairness.push_back("\\A self \\in " + pe(p.id, none, empty, empty) + " : " + f + "_vars(" + p.name + "(self))");
+                else fairness.push_back(f + "_vars(" + p.name + ")");
+            }
+        if (fairness.empty()) o += "Spec == Init /\\ [][Next]_vars\n\n";
+        else {
+            o += "Spec == /\\ Init /\\ [][Next]_vars\n";
+            for (const auto &f : fairness) o += "        /\\ " + f + "\n";
+            o += "\n";
+        }
+    }
     o += multi ? "Termination == <>(\\A self \\in ProcSet: pc[self] = \"Done\")\n\n" : "Termination == <>(pc = \"Done\")\n\n";
     o += "\\* END TRANSLATION\n";
     return o;

@@ -33,6 +33,7 @@ using SP = std::shared_ptr<Stmt>;
 struct Stmt {
     enum K { ASSIGN, IF, WHILE, EITHER, WITH, AWAIT, ASSERT, SKIP, GOTO, PRINT, CALL, RETURN } k = SKIP;
     std::string label;                     // "" = unlabeled
+    char fair_mod = 0;                     // the label's fairness modifier: '+' (`l:+`), '-' (`l:-`) or 0
     Pos pos;                               // of the statement keyword / lhs (asserts print it)
     std::string var;                       // ASSIGN lhs, WITH variable, GOTO target
     EP idx;                                // ASSIGN lhs index (x[i] := e), may be null
@@ -57,6 +58,9 @@ struct VarDecl {
 struct Proc {
     std::string name;
     bool is_set = false;   // process P \in S   vs   process P = e
+    int fair = 0;          // 0 = `process`, 1 = `fair process` (weak fairness), 2 = `fair+ process` (strong)
+    bool label_mods = false;   // some label of the body carries a `+` / `-` modifier (Stmt::fair_mod; kept here too: the passes that
+                               // rebuild statements — records, procedures — keep a label's name only)
     EP id;
     std::vector<VarDecl> locals;
     std::vector<SP> body;
@@ -104,6 +108,7 @@ struct Macro {
 struct Module {
     std::string name;
     std::string algorithm;
+    bool fair_algorithm = false;            // `--fair algorithm`: every process is (weakly) fair; a uniprocess one gets WF_vars(Next)
     std::vector<std::string> constants;     // CONSTANT(S) declared by the module
     std::vector<VarDecl> globals;
     std::vector<Proc> procs;                // a uniprocess algorithm is one Proc with an empty name
@@ -197,6 +202,9 @@ struct Program {
     struct AssertPos { int line, col; };
     std::vector<AssertPos> asserts;
     std::string module, translated;       // module name; the module text with the translation inserted
+    // fairness (liveness.h): bit k = process instance k (the slot order: slot / maxch) is weakly fair
+    unsigned long long fair_mask = 0;
+    std::string live_refusal;             // "" = `Termination` can be checked on the state graph; else why not
 };
 
 // Returns "" or an error message.

@@ -1608,6 +1608,25 @@ struct Compiler {
         procset.clear();
         for (const auto &x : insts) procset.push_back(x.self);
         P.ninst = (int)insts.size();
+        {   // fairness, per instance in the slot order (slot / maxch); what liveness checking cannot take is said here, once
+            std::function<bool(const std::vector<SP> &)> has_mod = [&](const std::vector<SP> &v) {
+                for (const auto &st : v) {
+                    if (st->fair_mod) return true;
+                    for (const auto &b : st->blocks) if (has_mod(b)) return true;
+                }
+                return false;
+            };
+            for (size_t k = 0; k < insts.size(); k++) {
+                const int fair = insts[k].p->fair ? insts[k].p->fair : m.fair_algorithm ? 1 : 0;
+                if (!fair) continue;
+                if (k < 64) P.fair_mask |= 1ull << k;
+                const std::string who = insts[k].p->name.empty() ? std::string("the algorithm") : "process " + insts[k].p->name;
+                if (fair == 2 && P.live_refusal.empty()) P.live_refusal = who + " is `fair+` (strong fairness); only weak fairness is supported";
+                if ((insts[k].p->label_mods || has_mod(insts[k].p->body)) && P.live_refusal.empty()) P.live_refusal = who + " is fair and has a label with a `+` / `-` fairness modifier";
+            }
+            if (m.had_procedures) P.live_refusal = "the algorithm has procedures (their actions get fairness conjuncts of their own)";
+            if (insts.size() > 64) P.live_refusal = "more than 64 process instances";
+        }
         // variables: globals, pc, process locals (the VARIABLES order of the translation)
         int nv = 0;
         auto add_var = [&](const std::string &name, bool array, const std::vector<long long> &ids, char type) {

@@ -56,9 +56,12 @@ def parse(argv):
     return o
 
 
-def report(r, world, seconds, trace=None):
+def report(r, world, seconds, trace=None, properties=()):
     """TLC's closing lines for a sharded run (format of README.md:319-320 / testout2:260-266)."""
     out = [f"Finished computing initial states: {r.levels[0] if r.levels else 0} distinct state{'' if r.levels and r.levels[0] == 1 else 's'} generated."]
+    for name in properties:   # a sharded search keeps no state graph in one place: named, never passed over
+        out.append(f"Warning: temporal property {name} NOT checked: the search is sharded over {world} engines (-gpus); "
+                   "liveness needs the state graph of one engine.")
     if r.verdict == "ok":
         out.append("Model checking completed. No error has been found.")
     elif r.verdict == "budget":
@@ -113,11 +116,12 @@ def main(argv=None):
     dt = time.perf_counter() - t0
     trace = chk.counterexample() if r.verdict not in ("ok", "budget") else None   # collective: every rank walks along
     chk.close()
+    properties = list(rs.properties)
     rs.close()
     if launched:
         dist.destroy_process_group()  # before rank 0's (possibly long) one-GPU re-run: the other ranks are done
     if rank == 0:
-        text = report(r, world, dt, trace)
+        text = report(r, world, dt, trace, properties)
         if r.verdict not in ("ok", "budget") and not o["generic"] and o["rerun"]:
             try:  # the counterexample: one GPU, the same search bounded to the error's depth
                 from . import check_files
