@@ -71,4 +71,5 @@ def test_the_counter_stamp_covers_device_code_only():
     assert "engine_kernels.h" in (root / "profiles" / "summarize_pmc.py").read_text()
     host, dev = (root / "tla_rust_amd" / "csrc" / "engine.hip").read_text(), (root / "tla_rust_amd" / "csrc" / "engine_kernels.h").read_text()
     assert "__global__" not in host, "a kernel in the host half"
+    assert "__global__" not in (root / "tla_rust_amd" / "csrc" / "state_graph.hip").read_text(), "a kernel in the host half of the graph passes"
     assert "hipMalloc" not in dev and "struct Engine" not in dev and len(b.kernel_source_hash()) == 16

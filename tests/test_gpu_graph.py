@@ -288,6 +288,59 @@ def test_a_compiled_program_interpreted_and_as_generated_code(amd):
         prog.close()
 
 
+def test_three_engines_of_three_units_share_the_graph_passes(amd):
+    """The passes over the CSR arrays (reads, components, the fairness check) are compiled once for the library and serve the engine of
+    every translation unit: a hand lowering's (atomic_add), another one's (the Voting model of 77 states under SYMMETRY) and the unit of
+    generated code built at load time (two_loops, jit).  Three engines alive at once, their calls interleaved: each gets what it gets
+    alone, so the shared object keeps nothing between calls.  (The sweep counts of mc_scc_info are left out: sweeps update in place, and
+    how many it takes to reach the fixed point is the wavefronts' race; `seconds` is a time.)"""
+    import livegraph
+    m = livegraph.MODELS["two_loops"]
+    prog = amd.Program((livegraph.DIR / m.tla).read_text(), (livegraph.DIR / m.cfg).read_text())
+    engines = [amd.Engine("atomic_add", [3], **KW), amd.Engine("paxos", [1, 3, 2, 2, 1, 3, 1], deadlock=False, **KW),
+               amd.Engine("pcal", prog.params, jit=True, **KW)]
+    a, v, t = engines
+    ginfo = lambda i: {k: x for k, x in dict(i).items() if k != "seconds"}   # noqa: E731
+    sinfo = lambda i: {k: x for k, x in dict(i).items() if k != "seconds" and not k.endswith("_rounds")}   # noqa: E731
+    try:
+        results = [e.run() for e in engines]
+        assert [r.verdict for r in results] == ["ok"] * 3 and [r.distinct for r in results[:2]] == [9, 77]
+        alone = []
+        for e in engines:   # one engine at a time: graph, components
+            info, offsets, dst, act = e.graph()
+            si, scc = e.scc()
+            alone.append((ginfo(info), offsets, dst, act, sinfo(si), scc))
+        assert alone[2][4]["nontrivial"] == 3
+        li = t.liveness(prog.fair_mask)
+        trace = t.liveness_trace()
+        assert li.violated == 1 and trace[0]
+        # interleaved: every build of one engine between two of another
+        gi = {}
+        for e in (t, a, v):
+            gi[e] = ginfo(e.graph_info())
+        si = {}
+        for e in (v, t, a):
+            si[e] = e.scc()
+        for e in (a, v, t):
+            info, offsets, dst, act = e.graph()                  # (rebuilds: the components above are released with the old graph)
+            g0, o0, d0, a0, s0, c0 = alone[engines.index(e)]
+            assert gi[e] == g0 == ginfo(info) and (offsets == o0).all() and (dst == d0).all() and (act == a0).all()
+            assert sinfo(si[e][0]) == s0 and (si[e][1] == c0).all()
+        # the fairness check of one engine around the others' calls
+        assert dict(t.liveness(prog.fair_mask), seconds=0) == dict(li, seconds=0)
+        a.scc()
+        v.graph_info()
+        assert t.liveness_trace() == trace
+        v.scc()
+        assert dict(t.liveness(prog.fair_mask), seconds=0) == dict(li, seconds=0) and t.liveness_trace() == trace
+        assert (a.scc()[1] == alone[0][5]).all() and (v.scc()[1] == alone[1][5]).all() and (t.scc()[1] == alone[2][5]).all()
+        print("two_loops", dict(t.graph_info()), dict(t.scc()[0]))
+    finally:
+        for e in engines:
+            e.close()
+        prog.close()
+
+
 # ------------------------------------------------------------------------------------------------ mc
 NODE = re.compile(r'^(\d+) \[label="((?:[^"\\]|\\.)*)"(,style = filled)?\]$')
 EDGE = re.compile(r'^(\d+) -> (\d+)(?: \[label="((?:[^"\\]|\\.)*)"\])?;$')

@@ -13,6 +13,17 @@ CLI = OUT / "mc"
 
 SOURCES = ["engine.hip", "frontend.cpp"]
 
+# What each object of engine.hip depends on: ENGINE_BASE for every unit, ENGINE_OWN[tu] for the lowerings the unit instantiates kernels of
+# (engine.hip includes every spec header through spec_registry.h; a unit's code changes only with its own).  state_graph.hip, the host
+# half of what consumes the state graph's CSR arrays, is one object for all of them: the spec units never see engine_live.h.
+# tests/test_engine_layout.py checks the lists against the files' #include lines.
+ENGINE_BASE = ["engine.hip", "hip_owned.h", "engine_kernels.h", "engine_sim.h", "sim_walk.h", "engine_coverage.h", "coverage.h", "engine_graph.h",
+               "graph.h", "liveness.h", "state_graph.h", "spec_gen.h", "mc_common.h", "spec_registry.h", "../../include/tlamc.h"]
+ENGINE_OWN = {0: ["spec_pluscal.h", "spec_raft.h", "spec_ssi.h", "spec_vm.h", "spec_paxos.h", "engine_pairs.h"], 7: ["spec_paxos.h"], 1: ["spec_pluscal.h"],
+              2: ["spec_raft.h"], 3: ["spec_raft.h"], 4: ["spec_raft.h"], 5: ["spec_ssi.h", "engine_pairs.h"], 6: ["spec_vm.h"]}
+STATE_GRAPH_DEPS = ["state_graph.hip", "state_graph.h", "engine_live.h", "hip_owned.h", "liveness.h", "graph.h", "coverage.h", "mc_common.h", "spec_registry.h",
+                    "spec_gen.h", "spec_pluscal.h", "spec_raft.h", "spec_ssi.h", "spec_vm.h", "spec_paxos.h", "../../include/tlamc.h"]
+
 
 def _stale(target, deps):
     if not target.exists():
@@ -37,15 +48,17 @@ def build(force=False, verbose=False):
         common += os.environ["TLAMC_EXTRA_DEFS"].split()
     if os.environ.get("TLAMC_PHASE_PROF"):   # per-phase cycle counters inside k_expand_family (profiles/phase_prof.py): a profiling build
         common.append("-DMC_PHASE_PROF")
-    base = [CSRC / "engine.hip", CSRC / "hip_owned.h", CSRC / "engine_kernels.h", CSRC / "engine_sim.h", CSRC / "sim_walk.h", CSRC / "engine_coverage.h", CSRC / "coverage.h", CSRC / "engine_graph.h", CSRC / "graph.h", CSRC / "engine_live.h", CSRC / "liveness.h", CSRC / "spec_gen.h", CSRC / "mc_common.h", CSRC / "spec_registry.h", PKG.parent / "include" / "tlamc.h"]
-    own = {0: ["spec_pluscal.h", "spec_raft.h", "spec_ssi.h", "spec_vm.h", "spec_paxos.h", "engine_pairs.h"], 7: ["spec_paxos.h"], 1: ["spec_pluscal.h"], 2: ["spec_raft.h"],
-           3: ["spec_raft.h"], 4: ["spec_raft.h"], 5: ["spec_ssi.h", "engine_pairs.h"], 6: ["spec_vm.h"]}
     jobs, objs = [], []
     for tu in range(8):
         obj = OUT / f"engine_tu{tu}.o"
         objs.append(obj)
-        if force or _stale(obj, base + [CSRC / h for h in own[tu]]):
+        if force or _stale(obj, [CSRC / h for h in ENGINE_BASE + ENGINE_OWN[tu]]):
             jobs.append((obj, subprocess.Popen(common + ["-x", "hip", f"-DMC_TU={tu}", "-c", str(CSRC / "engine.hip"), "-o", str(obj)])))
+    # the state graph's consumers (SCC, fairness, reads) and the device scans: one object, whatever the lowering
+    obj = OUT / "state_graph.o"
+    objs.append(obj)
+    if force or _stale(obj, [CSRC / d for d in STATE_GRAPH_DEPS]):
+        jobs.append((obj, subprocess.Popen(common + ["-x", "hip", "-c", str(CSRC / "state_graph.hip"), "-o", str(obj)])))
     host_deps = {"frontend": ["frontend.cpp", "pcal.h", "spec_vm.h", "mc_common.h", "tlaeval.h"], "pcal": ["pcal.cpp", "pcal.h"],
                  "tlaeval": ["tlaeval.cpp", "tlaeval.h"],
                  "pcal_compile": ["pcal_compile.cpp", "pcal.h", "spec_vm.h", "mc_common.h"],

@@ -26,7 +26,6 @@
 // Algorithmic HBM bytes per distinct state = 2*W + 8*(G/D)  (SURVEY.md §8d): each state is written once and read once, each
 // in-model successor touches one seen-set word; DESIGN.md §5 has what the kernels really move and what bounds them.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <chrono>
@@ -36,7 +35,7 @@
 #include <vector>
 
 #include "spec_registry.h"
-#include "hip_owned.h"        // DevBuf, PinnedBuf, Event, Stream: every HIP resource of the host half is held by one of these
+#include "hip_owned.h"        // DevBuf, PinnedBuf, Event, Stream: every HIP resource of the host half is held by one of these; HIP_TRY, set_error
 
 namespace mc {
 
@@ -46,26 +45,12 @@ namespace mc {
 #define MC_TU -1  // single translation unit: everything
 #endif
 }  // namespace mc
-extern "C" void mc_set_error_internal(const char *msg);
-namespace mc {
-static void set_error(const std::string &s) { mc_set_error_internal(s.c_str()); }
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) {                                                                    \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                          \
-            return MC_EHIP;                                                                        \
-        }                                                                                          \
-    } while (0)
-
-}  // namespace mc
 #include "engine_kernels.h"   // namespace mc { ... every kernel ... }
 #include "engine_pairs.h"     // k_expand_pairs: the by-pairs expand + insert + write kernel (specs with S::PAIR_FAMILIES)
 #include "engine_sim.h"       // k_simulate: simulation mode, one lane per random walk (mc_engine_simulate)
 #include "engine_coverage.h"  // k_coverage_generated / k_coverage_distinct: per-action counts (MC_F_COVERAGE, mc_engine_coverage)
-#include "engine_graph.h"     // k_graph_index / k_graph_degree / k_graph_fill: the state graph in CSR form (mc_engine_graph)
-#include "engine_live.h"      // k_scc_* / k_live_*: strongly connected components of that graph and the fairness check (mc_engine_scc, mc_engine_liveness)
+#include "engine_graph.h"     // k_graph_index / k_graph_degree / k_graph_fill / k_live_proc: the state graph in CSR form (mc_engine_graph)
+#include "state_graph.h"      // StateGraph: what consumes that form (reads, mc_engine_scc, mc_engine_liveness), and the device scans; compiled once
 namespace mc {
 
 // ------------------------------------------------------------------------------------- host side
@@ -124,12 +109,27 @@ struct EngineBase {
     virtual size_t state_bytes() const = 0;
     virtual int simulate(const mc_sim_opts *opts, mc_sim_result *out) = 0;
     virtual int coverage(mc_action_coverage *out, size_t *n_inout) = 0;
+    // ---- the state graph (state_graph.h).  The two calls that walk the arena with the lowering's kernels are the engine's; the rest
+    // consumes the CSR arrays and is the StateGraph's.  Engine<S>::alloc says where the graph's engine keeps what those calls need.
+    StateGraph gr;
+    bool sharded = false;                               // shard_count > 1: no graph
+    hipStream_t graph_stream = nullptr;                 // the engine's main stream
+    const std::vector<uint64_t> *graph_levels = nullptr;   // the level table of the last search
     virtual int graph(mc_graph_info *out) = 0;
-    virtual int graph_read(uint64_t first, uint64_t count, uint64_t *offsets_out, uint32_t *dst_out, int32_t *action_out, size_t *nedges_inout) = 0;
-    virtual int scc(mc_scc_info *out) = 0;
-    virtual int scc_read(uint64_t first, uint64_t count, uint32_t *scc_out) = 0;
     virtual int liveness(uint64_t weak_fair_mask, mc_live_info *out) = 0;
-    virtual int liveness_trace(uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout) = 0;
+    int graph_read(uint64_t first, uint64_t count, uint64_t *offsets_out, uint32_t *dst_out, int32_t *action_out, size_t *nedges_inout) {
+        return gr.read(first, count, offsets_out, dst_out, action_out, nedges_inout);
+    }
+    int scc(mc_scc_info *out) {
+        memset(out, 0, sizeof *out);
+        if (sharded) { set_error("mc_engine_scc: not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
+        if (!gr.built) { mc_graph_info gi; if (int rc = graph(&gi)) return rc; }
+        return gr.scc(graph_stream, out);
+    }
+    int scc_read(uint64_t first, uint64_t count, uint32_t *scc_out) { return gr.scc_read(first, count, scc_out); }
+    int liveness_trace(uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout) {
+        return gr.live_trace(*graph_levels, prefix_out, nprefix_inout, cycle_out, ncycle_inout);
+    }
 };
 
 static uint64_t round_pow2(uint64_t v) {
@@ -337,34 +337,6 @@ struct Engine : EngineBase {
         std::vector<uint64_t> host;        // the bins as the last run left them (+ Init's generated, which no kernel counts)
         uint64_t init_generated = 0;
     } cov;
-    // ---- the state graph (mc_engine_graph; engine_graph.h): built on demand from the arena and the seen-set a search left, gone with
-    // the next search (run / step / simulate / restore) or with the engine
-    struct Graph {
-        bool built = false;
-        DevBuf<uint64_t> offsets;   // [states + 1]: row i of dst / act is [offsets[i], offsets[i + 1]); doubles as the out-degree table
-        DevBuf<uint32_t> dst;       // [edges] arena index of the successor
-        DevBuf<int16_t> act;        // [edges] action id (CovAction<S>::of: mc_action_name's)
-        mc_graph_info info{};
-        // what mc_engine_scc / mc_engine_liveness add (engine_live.h): lives and dies with the graph
-        struct Live {
-            bool scc_built = false, checked = false;
-            DevBuf<uint64_t> toff;      // [states + 1] rows of the transpose (self loops left out)
-            DevBuf<uint32_t> tsrc;      // [edges that are no self loops] the sources
-            DevBuf<uint32_t> scc;       // [states] the least arena index of the state's component
-            DevBuf<uint32_t> size;      // [states] at a component's id: its number of states
-            DevBuf<int8_t> proc;        // [edges] beside act: the process instance that takes the edge, LIVE_TERM for the terminating disjunct
-            DevBuf<unsigned long long> taken, disabled;   // [states] at a component's id: the unions over its states
-            DevBuf<unsigned> done;      // [states] at a component's id: it holds a Done state
-            mc_scc_info sinfo{};
-            mc_live_info linfo{};
-            uint64_t fair = 0;
-            void release() {
-                scc_built = checked = false;
-                toff.reset(); tsrc.reset(); scc.reset(); size.reset(); proc.reset(); taken.reset(); disabled.reset(); done.reset();
-            }
-        } lv;
-        void release() { built = false; offsets.reset(); dst.reset(); act.reset(); lv.release(); }
-    } gr;
 
     // slot slices of a generic-kernel launch (k_expand_insert): as many as it takes to give the device a few thousand wavefronts,
     // for specs whose slots all go through the loop (no unrolled prefix) and that have enough of them; TLAMC_NOSLICE=1 = A/B
@@ -387,6 +359,9 @@ struct Engine : EngineBase {
         use_matrix = (cfg.flags & MC_F_MATRIX) != 0;
         HIP_TRY(hipSetDevice(cfg.device));
         HIP_TRY(stream.create());
+        sharded = cfg.shard_count > 1;
+        graph_stream = stream;
+        graph_levels = &fr.level_start;
         {   // A/B knob (measured in DESIGN.md section 4): TLAMC_PRIO=1 gives the materialise stream the highest priority, =2 the lowest
             const char *pe = getenv("TLAMC_PRIO");
             int lo_p = 0, hi_p = 0;
@@ -456,16 +431,22 @@ struct Engine : EngineBase {
 
     // ------------------------------------------------------------------------------- coverage (engine_coverage.h)
     // All on `stream`, behind the expand kernels of the level they count: the arena rows and trace records they read are final by then.
-    // generated: the states [lo, hi) a level expanded, in the chunks the expand kernel saw.
-    void cov_generated(uint64_t lo, uint64_t hi) {
+    // The states [lo, hi) in the chunks the expand kernel saw: f(c0, c1, ncols), column 0 = the 64-aligned state at or below c0.
+    template <class F>
+    void each_chunk(uint64_t lo, uint64_t hi, F &&f) {
         for (uint64_t c0 = lo; c0 < hi;) {
             const uint64_t base = c0 & ~63ull;
             const uint64_t c1 = base + chunk < hi ? base + chunk : hi;
-            const uint64_t ncols = ((c1 - base) + 63) & ~63ull;
-            hipLaunchKernelGGL(k_coverage_generated<S>, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, stream, prm, (const uint64_t *)d_arena,
-                               c0, c1, ncols, cov.bins.p, cov.nbins);
+            f(c0, c1, ((c1 - base) + 63) & ~63ull);
             c0 = c1;
         }
+    }
+    // generated: the states [lo, hi) a level expanded
+    void cov_generated(uint64_t lo, uint64_t hi) {
+        each_chunk(lo, hi, [&](uint64_t c0, uint64_t c1, uint64_t ncols) {
+            hipLaunchKernelGGL(k_coverage_generated<S>, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, stream, prm, (const uint64_t *)d_arena,
+                               c0, c1, ncols, cov.bins.p, cov.nbins);
+        });
     }
     // distinct: the states [lo, hi) a level added (or Init stored), by their trace records
     void cov_distinct(uint64_t lo, uint64_t hi) {
@@ -512,23 +493,12 @@ struct Engine : EngineBase {
     // All on `stream`, after a search has ended: rows, fingerprints and counters are final and only read.  The states with out-edges
     // are [0, fr.lo): run() moves `lo` past a level exactly when it has expanded it — the same (lo, hi) it hands to cov_generated —
     // so the levels coverage counts and the levels that have rows here cannot differ.
-    template <class T>
-    int graph_alloc(DevBuf<T> &b, size_t count, const char *what, const char *call = "mc_engine_graph") {
-        if (b.alloc(count ? count : 1) == hipSuccess) return MC_OK;
-        (void)hipGetLastError();   // (the failed allocation is reported here, not by the next HIP call)
-        set_error(std::string(call) + ": cannot allocate " + std::to_string((unsigned long long)(count * sizeof(T))) + " bytes of device memory for " + what);
-        return MC_EARENA;
-    }
     template <class K, class... A>
     void graph_chunks(K kernel, uint64_t lo, uint64_t hi, A... args) {   // the chunks cov_generated launches
-        for (uint64_t c0 = lo; c0 < hi;) {
-            const uint64_t base = c0 & ~63ull;
-            const uint64_t c1 = base + chunk < hi ? base + chunk : hi;
-            const uint64_t ncols = ((c1 - base) + 63) & ~63ull;
+        each_chunk(lo, hi, [&](uint64_t c0, uint64_t c1, uint64_t ncols) {
             hipLaunchKernelGGL(kernel, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, stream, prm, (const uint64_t *)d_arena, c0, c1, ncols,
                                (const uint64_t *)d_table, seen_arg(), args...);
-            c0 = c1;
-        }
+        });
     }
     int graph(mc_graph_info *out) override {
         memset(out, 0, sizeof *out);
@@ -539,6 +509,7 @@ struct Engine : EngineBase {
             return MC_ESTATE;
         }
         gr.release();
+        gr.device = cfg.device;
         const uint64_t n = fr.last_distinct, expanded = fr.lo;
         if (n + 1 > 0x7fffffffull) { set_error("mc_engine_graph: at most 2^31 - 2 states (the scan's item count)"); return MC_EBADCFG; }
         HIP_TRY(hipSetDevice(cfg.device));
@@ -572,11 +543,7 @@ struct Engine : EngineBase {
                                   (const uint64_t *)d_table, seen_arg(), slot_index.p, table_cap, d_gc.p);
         graph_chunks(k_graph_degree<S>, 0, expanded, degree.p, d_gc.p);
         HIP_TRY(hipGetLastError());
-        hipcub::TransformInputIterator<uint64_t, GraphDegreeCast, const uint32_t *> in(degree.p, GraphDegreeCast());
-        size_t need = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, in, gr.offsets.p, (int)(n + 1), stream));
-        if (int rc = graph_alloc(scan_tmp, need, "the scan")) return rc;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp.p, need, in, gr.offsets.p, (int)(n + 1), stream));
+        if (int rc = scan_exclusive_u32_to_u64(degree.p, gr.offsets.p, n + 1, scan_tmp, stream, "mc_engine_graph")) return rc;
         uint64_t edges = 0;
         HIP_TRY(hipMemcpyAsync(&edges, gr.offsets.p + n, sizeof edges, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipMemcpyAsync(&gc, d_gc, sizeof gc, hipMemcpyDeviceToHost, stream));
@@ -604,146 +571,8 @@ struct Engine : EngineBase {
                   " (two different states with one 64-bit fingerprint are the only legitimate cause: the second is never stored); no graph was built");
         return MC_ESTATE;
     }
-    int graph_read(uint64_t first, uint64_t count, uint64_t *offsets_out, uint32_t *dst_out, int32_t *action_out, size_t *nedges_inout) override {
-        if (!gr.built) { set_error("mc_engine_graph_read: no graph (mc_engine_graph builds it; the next search releases it)"); return MC_ESTATE; }
-        if (first > gr.info.states || count > gr.info.states - first) { set_error("mc_engine_graph_read: range beyond the graph's states"); return MC_EBADCFG; }
-        HIP_TRY(hipSetDevice(cfg.device));
-        std::vector<uint64_t> off((size_t)count + 1);
-        HIP_TRY(hipMemcpy(off.data(), gr.offsets.p + first, off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        const uint64_t e0 = off[0], ne = off[count] - e0;
-        if (ne > *nedges_inout || !offsets_out || (ne && (!dst_out || !action_out))) {
-            *nedges_inout = (size_t)ne;
-            set_error("mc_engine_graph_read: buffer too small (" + std::to_string((unsigned long long)ne) + " edges)");
-            return MC_EBADCFG;
-        }
-        for (uint64_t k = 0; k <= count; k++) offsets_out[k] = off[k] - e0;
-        if (ne) {
-            std::vector<int16_t> a16((size_t)ne);
-            HIP_TRY(hipMemcpy(dst_out, gr.dst.p + e0, ne * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(a16.data(), gr.act.p + e0, ne * sizeof(int16_t), hipMemcpyDeviceToHost));
-            for (uint64_t k = 0; k < ne; k++) action_out[k] = a16[k];
-        }
-        *nedges_inout = (size_t)ne;
-        return MC_OK;
-    }
 
-    // ------------------------------------------------------------------------------- components and fairness (engine_live.h)
-    // One kernel over all states: the launches of this section differ in the kernel and its arguments only.
-    template <class K, class... A>
-    void live_launch(K kernel, uint64_t n, A... args) {
-        if (n) hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, args...);
-    }
-    // SCC_BATCH sweeps, then one read of the flag; until a whole batch changed nothing.  `rounds` counts the sweeps launched.
-    template <class F>
-    int live_fixed_point(unsigned *flag, uint32_t &rounds, F &&sweep) {
-        for (;;) {
-            HIP_TRY(hipMemsetAsync(flag, 0, sizeof(unsigned), stream));
-            for (int k = 0; k < SCC_BATCH; ++k) sweep();
-            rounds += SCC_BATCH;
-            unsigned h = 0;
-            HIP_TRY(hipMemcpyAsync(&h, flag, sizeof h, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (!h) return MC_OK;
-        }
-    }
-    int scc(mc_scc_info *out) override {
-        memset(out, 0, sizeof *out);
-        if (cfg.shard_count > 1) { set_error("mc_engine_scc: not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
-        if (!gr.built) { mc_graph_info gi; if (int rc = graph(&gi)) return rc; }
-        auto &lv = gr.lv;
-        lv.release();
-        const uint64_t n = gr.info.states;
-        HIP_TRY(hipSetDevice(cfg.device));
-        const auto t0 = std::chrono::steady_clock::now();
-        const int rc = scc_build(n);
-        if (rc) { lv.release(); return rc; }
-        lv.sinfo.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        lv.scc_built = true;
-        *out = lv.sinfo;
-        return MC_OK;
-    }
-    int scc_build(uint64_t n) {
-        auto &lv = gr.lv;
-        DevBuf<uint32_t> indeg;   // build-time only: the in-degrees, then the fill's cursors
-        DevBuf<unsigned> flag;
-        DevBuf<LiveCounters> d_lc;
-        DevBuf<char> scan_tmp;
-        int rc;
-        if ((rc = graph_alloc(indeg, n + 1, "the in-degrees", "mc_engine_scc"))) return rc;
-        if ((rc = graph_alloc(lv.toff, n + 1, "the transpose's row offsets", "mc_engine_scc"))) return rc;
-        if ((rc = graph_alloc(lv.scc, n, "the component ids", "mc_engine_scc"))) return rc;
-        if ((rc = graph_alloc(lv.size, n, "the colours", "mc_engine_scc"))) return rc;
-        if ((rc = graph_alloc(flag, 1, "the fixed-point flag", "mc_engine_scc"))) return rc;
-        if ((rc = graph_alloc(d_lc, 1, "the counters", "mc_engine_scc"))) return rc;
-        const uint64_t *off = gr.offsets.p;
-        const uint32_t *dst = gr.dst.p;
-        // ---- transpose
-        HIP_TRY(hipMemsetAsync(indeg, 0, (n + 1) * sizeof(uint32_t), stream));
-        live_launch(k_live_indegree, n, off, dst, indeg.p);
-        HIP_TRY(hipGetLastError());
-        hipcub::TransformInputIterator<uint64_t, GraphDegreeCast, const uint32_t *> in(indeg.p, GraphDegreeCast());
-        size_t need = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, in, lv.toff.p, (int)(n + 1), stream));
-        if ((rc = graph_alloc(scan_tmp, need, "the scan", "mc_engine_scc"))) return rc;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp.p, need, in, lv.toff.p, (int)(n + 1), stream));
-        uint64_t tedges = 0;
-        HIP_TRY(hipMemcpyAsync(&tedges, lv.toff.p + n, sizeof tedges, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if ((rc = graph_alloc(lv.tsrc, tedges, "the transpose's sources", "mc_engine_scc"))) return rc;
-        HIP_TRY(hipMemsetAsync(indeg, 0, (n + 1) * sizeof(uint32_t), stream));
-        live_launch(k_live_tfill, n, off, dst, (const uint64_t *)lv.toff.p, indeg.p, lv.tsrc.p);
-        HIP_TRY(hipGetLastError());
-        // ---- trim and colouring until no state is live
-        const uint64_t *toff = lv.toff.p;
-        const uint32_t *tsrc = lv.tsrc.p;
-        uint32_t *scc = lv.scc.p, *colour = lv.size.p;
-        HIP_TRY(hipMemsetAsync(scc, 0xff, n * sizeof(uint32_t), stream));
-        uint32_t trim_rounds = 0, colour_rounds = 0, back_rounds = 0, passes = 0;
-        for (; n;) {
-            if ((rc = live_fixed_point(flag.p, trim_rounds, [&] { live_launch(k_scc_trim, n, off, dst, toff, tsrc, scc, flag.p); }))) return rc;
-            unsigned live = 0;
-            HIP_TRY(hipMemsetAsync(flag, 0, sizeof(unsigned), stream));
-            live_launch(k_scc_colour_init, n, (const uint32_t *)scc, colour, flag.p);
-            HIP_TRY(hipMemcpyAsync(&live, flag, sizeof live, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (!live) break;
-            ++passes;
-            if ((rc = live_fixed_point(flag.p, colour_rounds, [&] { live_launch(k_scc_colour, n, toff, tsrc, (const uint32_t *)scc, colour, flag.p); }))) return rc;
-            live_launch(k_scc_roots, n, scc, (const uint32_t *)colour);
-            if ((rc = live_fixed_point(flag.p, back_rounds, [&] { live_launch(k_scc_back, n, off, dst, scc, (const uint32_t *)colour, flag.p); }))) return rc;
-        }
-        // ---- ids: the least index of the component; sizes; statistics (the colour array serves as `least`, then as `size`)
-        LiveCounters lc;
-        memset(&lc, 0, sizeof lc);
-        lc.first_root = ~0u;
-        HIP_TRY(hipMemcpyAsync(d_lc, &lc, sizeof lc, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemsetAsync(colour, 0xff, (n ? n : 1) * sizeof(uint32_t), stream));
-        live_launch(k_scc_least, n, (const uint32_t *)scc, colour);
-        live_launch(k_scc_renumber, n, scc, (const uint32_t *)colour);
-        HIP_TRY(hipMemsetAsync(colour, 0, (n ? n : 1) * sizeof(uint32_t), stream));
-        live_launch(k_scc_sizes, n, (const uint32_t *)scc, colour);
-        live_launch(k_scc_stats, n, (const uint32_t *)scc, (const uint32_t *)colour, d_lc.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&lc, d_lc, sizeof lc, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        memset(&lv.sinfo, 0, sizeof lv.sinfo);
-        lv.sinfo.states = n;
-        lv.sinfo.components = lc.components;
-        lv.sinfo.nontrivial = lc.nontrivial;
-        lv.sinfo.largest = lc.largest;
-        lv.sinfo.trim_rounds = trim_rounds;
-        lv.sinfo.colour_rounds = colour_rounds;
-        lv.sinfo.backward_rounds = back_rounds;
-        lv.sinfo.passes = passes;
-        return MC_OK;
-    }
-    int scc_read(uint64_t first, uint64_t count, uint32_t *scc_out) override {
-        if (!gr.built || !gr.lv.scc_built) { set_error("mc_engine_scc_read: no components (mc_engine_scc finds them; the next search releases them)"); return MC_ESTATE; }
-        if (first > gr.info.states || count > gr.info.states - first) { set_error("mc_engine_scc_read: range beyond the graph's states"); return MC_EBADCFG; }
-        HIP_TRY(hipSetDevice(cfg.device));
-        if (count) HIP_TRY(hipMemcpy(scc_out, gr.lv.scc.p + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        return MC_OK;
-    }
+    // ------------------------------------------------------------------------------- fairness: the lowering's part (LiveProc<S>, k_live_proc<S>)
     int liveness(uint64_t fair, mc_live_info *out) override {
         memset(out, 0, sizeof *out);
         if (cfg.shard_count > 1) { set_error("mc_engine_liveness: not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
@@ -762,144 +591,14 @@ struct Engine : EngineBase {
             if (!gr.built || !gr.lv.scc_built) { mc_scc_info si; if (int rc = scc(&si)) return rc; }
             auto &lv = gr.lv;
             lv.checked = false;
-            const uint64_t n = gr.info.states, edges = gr.info.edges;
+            const uint64_t edges = gr.info.edges;
             HIP_TRY(hipSetDevice(cfg.device));
             const auto t0 = std::chrono::steady_clock::now();
-            DevBuf<LiveCounters> d_lc;
-            int rc;
-            if ((rc = graph_alloc(lv.proc, edges, "the edges' processes", "mc_engine_liveness"))) return rc;
-            if ((rc = graph_alloc(lv.taken, n, "the components' taken masks", "mc_engine_liveness"))) return rc;
-            if ((rc = graph_alloc(lv.disabled, n, "the components' disabled masks", "mc_engine_liveness"))) return rc;
-            if ((rc = graph_alloc(lv.done, n, "the components' Done flags", "mc_engine_liveness"))) return rc;
-            if ((rc = graph_alloc(d_lc, 1, "the counters", "mc_engine_liveness"))) return rc;
-            LiveCounters lc;
-            memset(&lc, 0, sizeof lc);
-            lc.first_root = ~0u;
-            HIP_TRY(hipMemcpyAsync(d_lc, &lc, sizeof lc, hipMemcpyHostToDevice, stream));
+            if (int rc = graph_alloc(lv.proc, edges, "the edges' processes", "mc_engine_liveness")) return rc;
             HIP_TRY(hipMemsetAsync(lv.proc, 0xff, (edges ? edges : 1) * sizeof(int8_t), stream));
-            HIP_TRY(hipMemsetAsync(lv.taken, 0, (n ? n : 1) * sizeof(unsigned long long), stream));
-            HIP_TRY(hipMemsetAsync(lv.disabled, 0, (n ? n : 1) * sizeof(unsigned long long), stream));
-            HIP_TRY(hipMemsetAsync(lv.done, 0, (n ? n : 1) * sizeof(unsigned), stream));
             graph_chunks(k_live_proc<S>, 0, fr.lo, (const uint64_t *)gr.offsets.p, lv.proc.p);
-            live_launch(k_live_reduce, n, (const uint64_t *)gr.offsets.p, (const uint32_t *)gr.dst.p, (const int8_t *)lv.proc.p, (const uint32_t *)lv.scc.p,
-                        (const uint32_t *)lv.size.p, all, lv.taken.p, lv.disabled.p, lv.done.p);
-            live_launch(k_live_verdict, n, (const uint32_t *)lv.scc.p, (const uint32_t *)lv.size.p, (const unsigned long long *)lv.taken.p,
-                        (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p, all, fair, d_lc.p);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&lc, d_lc, sizeof lc, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            memset(&lv.linfo, 0, sizeof lv.linfo);
-            lv.linfo.violated = lc.fair_components ? 1 : 0;
-            lv.linfo.fair_components = lc.fair_components;
-            if (lc.fair_components) {
-                uint32_t sz = 0;
-                HIP_TRY(hipMemcpy(&sz, lv.size.p + lc.first_root, sizeof sz, hipMemcpyDeviceToHost));
-                lv.linfo.root = lc.first_root;
-                lv.linfo.root_size = sz;
-            }
-            lv.linfo.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            lv.fair = fair;
-            lv.checked = true;
-            *out = lv.linfo;
-            return MC_OK;
+            return gr.live_check(all, fair, stream, t0, out);
         }
-    }
-    // The counterexample of the last mc_engine_liveness, built on the host from the arrays (deterministic given them).
-    // prefix: from an initial state to the chosen component's id (its least state), one BFS level back per step along the transpose: the
-    // least source in the previous level (level boundaries: fr.level_start).  cycle: a closed walk inside the component that starts at
-    // that state and, for every weakly fair process, takes a real step of it or passes a state where it is disabled; the last entry has an
-    // edge back to the first.  Empty = the behaviour stutters in the prefix's last state for ever.
-    int liveness_trace(uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout) override {
-        auto &lv = gr.lv;
-        if (!gr.built || !lv.checked) { set_error("mc_engine_liveness_trace: no liveness check (mc_engine_liveness runs it; the next search releases it)"); return MC_ESTATE; }
-        if (!lv.linfo.violated) { set_error("mc_engine_liveness_trace: the property holds: there is no counterexample"); return MC_ESTATE; }
-        HIP_TRY(hipSetDevice(cfg.device));
-        const uint64_t n = gr.info.states, edges = gr.info.edges;
-        const uint32_t root = (uint32_t)lv.linfo.root;
-        // ---- prefix
-        std::vector<uint32_t> prefix{root};
-        auto level_of = [&](uint32_t x) { return (size_t)(std::upper_bound(fr.level_start.begin(), fr.level_start.end(), (uint64_t)x) - fr.level_start.begin()) - 1; };
-        for (uint32_t cur = root; level_of(cur) > 0;) {
-            const size_t L = level_of(cur);
-            uint64_t row[2];
-            HIP_TRY(hipMemcpy(row, lv.toff.p + cur, sizeof row, hipMemcpyDeviceToHost));
-            std::vector<uint32_t> src((size_t)(row[1] - row[0]));
-            if (!src.empty()) HIP_TRY(hipMemcpy(src.data(), lv.tsrc.p + row[0], src.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            uint32_t best = ~0u;
-            for (uint32_t u : src) if (u >= fr.level_start[L - 1] && u < fr.level_start[L] && u < best) best = u;
-            if (best == ~0u) { set_error("mc_engine_liveness_trace: state " + std::to_string(cur) + " has no in-edge from the level before its own"); return MC_ESTATE; }
-            prefix.push_back(best);
-            cur = best;
-        }
-        std::reverse(prefix.begin(), prefix.end());
-        // ---- cycle
-        std::vector<uint64_t> off((size_t)n + 1);
-        std::vector<uint32_t> dst((size_t)edges), scc((size_t)n);
-        std::vector<int8_t> proc((size_t)edges);
-        HIP_TRY(hipMemcpy(off.data(), gr.offsets.p, off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(scc.data(), lv.scc.p, scc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (edges) {
-            HIP_TRY(hipMemcpy(dst.data(), gr.dst.p, dst.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(proc.data(), lv.proc.p, proc.size() * sizeof(int8_t), hipMemcpyDeviceToHost));
-        }
-        std::vector<uint32_t> members;
-        for (uint64_t v = 0; v < n; ++v) if (scc[(size_t)v] == root) members.push_back((uint32_t)v);
-        std::vector<uint32_t> par((size_t)n, ~0u);
-        std::vector<uint32_t> cycle{root};   // the walk so far; its last entry is where it stands
-        // breadth-first inside the component, rows in index order; appends the states after `from` up to `to`
-        auto go = [&](uint32_t to) {
-            const uint32_t from = cycle.back();
-            if (from == to) return true;
-            for (uint32_t m : members) par[m] = ~0u;
-            std::vector<uint32_t> q{from};
-            par[from] = from;
-            for (size_t h = 0; h < q.size() && par[to] == ~0u; ++h)
-                for (uint64_t k = off[q[h]]; k < off[q[h] + 1]; ++k) {
-                    const uint32_t d = dst[(size_t)k];
-                    if (scc[d] == root && par[d] == ~0u) { par[d] = q[h]; q.push_back(d); }
-                }
-            if (par[to] == ~0u) return false;
-            std::vector<uint32_t> path;
-            for (uint32_t x = to; x != from; x = par[x]) path.push_back(x);
-            cycle.insert(cycle.end(), path.rbegin(), path.rend());
-            return true;
-        };
-        bool ok = true;
-        for (int p = 0; p < 64 && ok; ++p) {
-            if (!(lv.fair >> p & 1)) continue;
-            bool found = false;
-            for (size_t mi = 0; mi < members.size() && !found; ++mi) {   // a real step of p inside the component: the first in index order
-                const uint32_t u = members[mi];
-                for (uint64_t k = off[u]; k < off[u + 1] && !found; ++k)
-                    if (proc[(size_t)k] == p && live_real_step(p, u, dst[(size_t)k]) && scc[dst[(size_t)k]] == root) {
-                        found = true;
-                        ok = go(u);
-                        cycle.push_back(dst[(size_t)k]);
-                    }
-            }
-            for (size_t mi = 0; mi < members.size() && !found; ++mi) {   // else a state where p is disabled
-                const uint32_t u = members[mi];
-                uint64_t en = 0, tk = 0;
-                bool dn = false;
-                live_state(u, dst.data() + off[u], proc.data() + off[u], off[u + 1] - off[u], scc.data(), &en, &tk, &dn);
-                if (!(en >> p & 1)) { found = true; ok = go(u); }
-            }
-            if (!found) ok = false;
-        }
-        if (ok) ok = go(root);
-        if (!ok) { set_error("mc_engine_liveness_trace: the chosen component is not fair or not connected (the arrays disagree with the verdict)"); return MC_ESTATE; }
-        cycle.pop_back();   // (the walk ended on `root` again: the closing edge is implied; a walk that never moved leaves nothing)
-        if (prefix.size() > *nprefix_inout || cycle.size() > *ncycle_inout || !prefix_out || (!cycle.empty() && !cycle_out)) {
-            *nprefix_inout = prefix.size();
-            *ncycle_inout = cycle.size();
-            set_error("mc_engine_liveness_trace: buffers too small (" + std::to_string(prefix.size()) + " + " + std::to_string(cycle.size()) + " states)");
-            return MC_EBADCFG;
-        }
-        memcpy(prefix_out, prefix.data(), prefix.size() * sizeof(uint32_t));
-        if (!cycle.empty()) memcpy(cycle_out, cycle.data(), cycle.size() * sizeof(uint32_t));
-        *nprefix_inout = prefix.size();
-        *ncycle_inout = cycle.size();
-        return MC_OK;
     }
 
     template <class F>
@@ -1612,14 +1311,6 @@ struct Engine : EngineBase {
         HIP_TRY(sh.h_cur.reserve((size_t)8 * NSHARD));
         return MC_OK;
     }
-    int scan_answers(const uint8_t *answers_back, uint64_t n, hipStream_t on) {
-        hipcub::TransformInputIterator<uint32_t, AnswerCast, const uint8_t *> in(answers_back, AnswerCast());
-        size_t need = 0;
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, in, sh.d_incl.p, (int)n, on));
-        HIP_TRY(sh.d_scan_tmp.reserve(need));
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(sh.d_scan_tmp.p, need, in, sh.d_incl.p, (int)n, on));
-        return MC_OK;
-    }
     // generated code with packed rows serves one GPU: its rows cannot travel between ranks
     static int refuse_packed() {
         if constexpr (PackedRows<S>::value) { set_error("this engine of generated code stores rows packed to its program's cell ranges and serves ONE GPU: create a sharded engine with shard_count > 1 (or $TLAMC_JIT_PACK=0)"); return MC_EBADCFG; }
@@ -1886,7 +1577,7 @@ struct Engine : EngineBase {
         q.moved = 0;
         if (!q.pend_total) return MC_OK;
         const unsigned bx = (unsigned)((q.pend_total + 255) / 256);
-        int rc = scan_answers(answers_back, q.pend_total, side());
+        int rc = scan_answers_inclusive(answers_back, sh.d_incl.p, q.pend_total, sh.d_scan_tmp, side());
         if (rc) return rc;
         hipLaunchKernelGGL(k_gather_range_ends, dim3(1), dim3(64), 0, side(), sh.d_incl, q.pend_off, P, sh.d_ends);
         unsigned long long *ends = sh.h_ends;  // the per-owner counts go back to the host: the caller sizes its all-to-all with them
@@ -1938,7 +1629,7 @@ struct Engine : EngineBase {
             HIP_TRY(hipEventRecord(sh.ev_ans.get(), sh.ext_stream));
             HIP_TRY(hipStreamWaitEvent(ks, sh.ev_ans.get(), 0));
         }
-        int rc = scan_answers(answers_back, q.pend_total, ks);
+        int rc = scan_answers_inclusive(answers_back, sh.d_incl.p, q.pend_total, sh.d_scan_tmp, ks);
         if (rc) return rc;
         append_begin(ks);
         const uint32_t *d_total = sh.d_incl + (q.pend_total - 1);

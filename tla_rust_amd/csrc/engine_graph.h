@@ -8,11 +8,13 @@
 //                    4-byte read: no second hash table, no second placement rule.
 //   k_graph_degree   pass 1, one lane per expanded state: the slot loop to the wavefront's largest nslots, degree[i] = its edges
 //   k_graph_fill     pass 2, the same loop: dst[offsets[i] + k], act[offsets[i] + k] in slot order
+//   k_live_proc      the loop a third time, for mc_engine_liveness: proc[offsets[i] + k] beside act[] (LiveProc<S>, liveness.h)
 // Between the passes an exclusive scan turns degree into offsets.  Nothing here writes the arena, the seen-set or a counter of the search.
+// These are the kernels that know the lowering; whatever consumes the CSR arrays alone is compiled once, in state_graph.hip.
 #ifndef TLAMC_ENGINE_GRAPH_H
 #define TLAMC_ENGINE_GRAPH_H
 
-#include "graph.h"
+#include "liveness.h"   // (graph.h, and LiveProc<S>)
 
 namespace mc {
 
@@ -121,10 +123,35 @@ k_graph_fill(typename S::Params prm, const uint64_t *__restrict__ arena, uint64_
     graph_walk<S, true>(prm, arena, lo, hi, ncols, table, seen, slot_index, nslots_total, nullptr, offsets, dst, act, gc);
 }
 
-// degree (32 bits) as the scan's 64-bit input: the offsets of a graph of more than 2^32 edges do not wrap
-struct GraphDegreeCast {
-    __host__ __device__ __forceinline__ uint64_t operator()(const uint32_t &d) const { return (uint64_t)d; }
-};
+// proc[] beside act[]: graph_walk's loop once more (the chunks, the columns, the wavefront's largest nslots, graph_edge), writing the
+// process instance of every counted slot at the edge's place
+template <class S>
+__global__ void __launch_bounds__(256)
+k_live_proc(typename S::Params prm, const uint64_t *__restrict__ arena, uint64_t lo, uint64_t hi, uint64_t ncols,
+            const uint64_t *__restrict__ table, uint64_t seen, const uint64_t *__restrict__ offsets, int8_t *__restrict__ proc) {
+    const uint64_t col = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t idx = (lo & ~63ull) + col;
+    const bool active = col < ncols && idx >= lo && idx < hi;
+    const CWordRef s = arena_cref(arena, active ? idx : lo, S::words(prm));
+    typename S::Local loc;
+    int ns = 0;
+    uint64_t out = 0, end = 0;
+    if (active) {
+        S::load(prm, s, loc);
+        ns = S::nslots(prm, loc);
+        out = offsets[idx];
+        end = offsets[idx + 1];
+    }
+    const int wns = (int)wave_max_u32((unsigned)ns);
+    for (int slot = 0; slot < wns; ++slot) {
+        if (slot >= ns) continue;   // (no wavefront operation inside the loop)
+        uint64_t f = 0, pos;
+        const unsigned kind = graph_edge(S::eval(prm, loc, s, slot, f), f, table, seen, pos);
+        if (kind != GE_SELF && kind != GE_EDGE) continue;
+        if (out < end) proc[out] = (int8_t)LiveProc<S>::of(prm, slot);
+        ++out;
+    }
+}
 
 }  // namespace mc
 

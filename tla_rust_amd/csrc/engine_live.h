@@ -1,7 +1,8 @@
 // engine_live.h — the DEVICE half of the strongly-connected-components pass (mc_engine_scc) and of the fairness check built on it
-// (mc_engine_liveness).  Included by engine.hip only (inside namespace mc, after engine_graph.h).  Everything here is a consumer of the
-// CSR arrays of mc_engine_graph (offsets / dst) and of nothing else, except k_live_proc, which walks the arena once more to say which
-// process instance takes each edge.  The rule itself is liveness.h's, MC_HD code the host runs too.
+// (mc_engine_liveness), and the library's two device scans.  Included by state_graph.hip only: one copy in the library, whatever the
+// lowering of the engine that asks.  Everything here is a consumer of the CSR arrays of mc_engine_graph (offsets / dst / proc) and of
+// nothing else; k_live_proc<S>, which walks the arena once more to say which process instance takes each edge, is beside the other
+// spec-walking kernels in engine_graph.h.  The rule itself is liveness.h's, MC_HD code the host runs too.
 //
 //   transpose   k_live_indegree (atomics) -> hipcub exclusive scan in 64 bits -> k_live_tfill.  Edges that end where they start are left
 //               out: no consumer wants them.  A row of the transpose is in no particular order (the fill's atomics decide); every reader
@@ -19,9 +20,7 @@
 //               workgroup raises the device flag; the host reads the flag once per SCC_BATCH sweeps.  Sweeps update in place: a lane may
 //               see a value another lane wrote in the same sweep — every update is monotone (live -> assigned, colours only grow), so that
 //               only makes the fixed point come sooner.
-//   fairness    k_live_proc<S>   the walk of graph_walk (same slot loop, same graph_edge decisions: edge k of a row is the k-th counted
-//                                slot) writes proc[] beside act[]
-//               k_live_reduce    per state the en / taken masks and the Done flag (live_state), OR-ed into the component's entry at
+//   fairness    k_live_reduce    per state the en / taken masks and the Done flag (live_state), OR-ed into the component's entry at
 //                                scc[v]: plain stores for one-state components, else one atomic per set of lanes that agree on it
 //               k_live_verdict   per component root the rule (live_violates); the number of fair non-Done components and the least root
 //
@@ -31,11 +30,12 @@
 #ifndef TLAMC_ENGINE_LIVE_H
 #define TLAMC_ENGINE_LIVE_H
 
+#include <hipcub/hipcub.hpp>
+
 #include "liveness.h"
+#include "state_graph.h"
 
 namespace mc {
-
-// (the kernels that are no templates are `static`: engine.hip is compiled once per group of lowerings, and every copy has its own)
 
 constexpr uint32_t SCC_LIVE = 0xffffffffu;   // scc[v] of a state no component has been found for yet
 constexpr int SCC_BATCH = 8;                 // sweeps launched between two reads of the "changed" flag
@@ -44,6 +44,12 @@ struct LiveCounters {
     unsigned long long components, nontrivial, fair_components;
     unsigned largest, first_root;   // first_root: the least root among the fair non-Done components, ~0u = none
 };
+
+// (engine_kernels.h has the same reduction for the search kernels; that file is no part of this unit)
+__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
+    for (int o = 32; o > 0; o >>= 1) { unsigned t = __shfl_xor(v, o); v = t > v ? t : v; }
+    return v;
+}
 
 // the workgroup's "changed" bit: LDS, then one store to the device flag
 __device__ __forceinline__ void live_raise(bool changed, unsigned *flag) {
@@ -176,36 +182,6 @@ k_scc_stats(uint64_t n, const uint32_t *__restrict__ scc, const uint32_t *__rest
 }
 
 // ---- fairness
-// proc[] beside act[]: graph_walk's loop once more (the chunks, the columns, the wavefront's largest nslots, graph_edge), writing the
-// process instance of every counted slot at the edge's place
-template <class S>
-__global__ void __launch_bounds__(256)
-k_live_proc(typename S::Params prm, const uint64_t *__restrict__ arena, uint64_t lo, uint64_t hi, uint64_t ncols,
-            const uint64_t *__restrict__ table, uint64_t seen, const uint64_t *__restrict__ offsets, int8_t *__restrict__ proc) {
-    const uint64_t col = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t idx = (lo & ~63ull) + col;
-    const bool active = col < ncols && idx >= lo && idx < hi;
-    const CWordRef s = arena_cref(arena, active ? idx : lo, S::words(prm));
-    typename S::Local loc;
-    int ns = 0;
-    uint64_t out = 0, end = 0;
-    if (active) {
-        S::load(prm, s, loc);
-        ns = S::nslots(prm, loc);
-        out = offsets[idx];
-        end = offsets[idx + 1];
-    }
-    const int wns = (int)wave_max_u32((unsigned)ns);
-    for (int slot = 0; slot < wns; ++slot) {
-        if (slot >= ns) continue;   // (no wavefront operation inside the loop)
-        uint64_t f = 0, pos;
-        const unsigned kind = graph_edge(S::eval(prm, loc, s, slot, f), f, table, seen, pos);
-        if (kind != GE_SELF && kind != GE_EDGE) continue;
-        if (out < end) proc[out] = (int8_t)LiveProc<S>::of(prm, slot);
-        ++out;
-    }
-}
-
 __device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) {
     for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
     return v;
@@ -257,6 +233,32 @@ k_live_verdict(uint64_t n, const uint32_t *__restrict__ scc, const uint32_t *__r
         atomicAdd(&lc->fair_components, (unsigned long long)__popcll(b));
         atomicMin(&lc->first_root, (unsigned)v);
     }
+}
+
+// ---- the scans (state_graph.h declares them)
+// degree (32 bits) as the scan's 64-bit input: the offsets of a graph of more than 2^32 edges do not wrap
+struct ScanU32ToU64 {
+    __host__ __device__ __forceinline__ uint64_t operator()(const uint32_t &d) const { return (uint64_t)d; }
+};
+int scan_exclusive_u32_to_u64(const uint32_t *in, uint64_t *out, uint64_t n, DevBuf<char> &tmp, hipStream_t stream, const char *call) {
+    hipcub::TransformInputIterator<uint64_t, ScanU32ToU64, const uint32_t *> it(in, ScanU32ToU64());
+    size_t need = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, it, out, (int)n, stream));
+    if (int rc = graph_alloc(tmp, need, "the scan", call)) return rc;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, need, it, out, (int)n, stream));
+    return MC_OK;
+}
+// a rank's answers (one byte per candidate, non-zero = keep) as the 0 / 1 the sum counts
+struct ScanAnswerBit {
+    __host__ __device__ uint32_t operator()(const uint8_t &a) const { return a ? 1u : 0u; }
+};
+int scan_answers_inclusive(const uint8_t *answers, uint32_t *incl, uint64_t n, DevBuf<char> &tmp, hipStream_t stream) {
+    hipcub::TransformInputIterator<uint32_t, ScanAnswerBit, const uint8_t *> it(answers, ScanAnswerBit());
+    size_t need = 0;
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, it, incl, (int)n, stream));
+    HIP_TRY(tmp.reserve(need));
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp.p, need, it, incl, (int)n, stream));
+    return MC_OK;
 }
 
 }  // namespace mc

@@ -1,13 +1,28 @@
 // hip_owned.h — move-only owners of the HIP resources the engine's host half holds (engine.hip): device and pinned host buffers,
 // events, streams.  Each frees what it holds when it goes (or is assigned over), so no path — least of all an early return between two
 // allocations — can leak a resource or free one twice.  Kernels and HIP calls keep receiving the raw pointer / handle (implicit conversion).
+// Also how the host half reports a failed HIP call: HIP_TRY, over the C ABI's last-error text (set_error).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <string>
 #include <utility>
 
+extern "C" void mc_set_error_internal(const char *msg);   // engine.hip, translation unit 0: the C ABI's last-error text
+
 namespace mc {
+
+inline void set_error(const std::string &s) { mc_set_error_internal(s.c_str()); }
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess) {                                                                    \
+            mc::set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                      \
+            return MC_EHIP;                                                                        \
+        }                                                                                          \
+    } while (0)
 
 // n elements of T in device memory (PINNED: in page-locked host memory)
 template <class T, bool PINNED = false>

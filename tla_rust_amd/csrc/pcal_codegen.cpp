@@ -15,6 +15,7 @@
 #include "pcal.h"
 #include "spec_vm.h"
 #include "../../include/tlamc.h"
+#include <dirent.h>
 #include <dlfcn.h>
 #include <stdlib.h>
 #include <string.h>
@@ -789,9 +790,19 @@ extern "C" void *mc_jit_factory_opts(const void *program /* pcal::Program * */, 
     const std::string csrc = lib + "/../csrc", inc = lib + "/../../include";
     if (!exists(csrc + "/engine.hip")) { mc::set_error("jit: the engine sources are not beside the library (" + csrc + ")"); return nullptr; }
     uint64_t h = fnv(gen);
-    for (const char *f : {"/engine.hip", "/hip_owned.h", "/engine_kernels.h", "/engine_pairs.h", "/engine_sim.h", "/sim_walk.h", "/engine_coverage.h", "/coverage.h", "/engine_graph.h", "/graph.h", "/spec_gen.h", "/spec_vm.h", "/mc_common.h"}) {
+    // (every file the unit can include, by listing and not by a list kept by hand: the *.h and *.hip beside engine.hip, and the public header)
+    std::vector<std::string> sources{inc + "/tlamc.h"};
+    if (DIR *d = opendir(csrc.c_str())) {
+        while (const dirent *e = readdir(d)) {
+            const std::string n = e->d_name;
+            if ((n.size() > 2 && n.compare(n.size() - 2, 2, ".h") == 0) || (n.size() > 4 && n.compare(n.size() - 4, 4, ".hip") == 0)) sources.push_back(csrc + "/" + n);
+        }
+        closedir(d);
+    }
+    std::sort(sources.begin() + 1, sources.end());   // (readdir's order is the file system's)
+    for (const std::string &f : sources) {
         struct stat st;
-        if (stat((csrc + f).c_str(), &st) == 0) h = (h ^ (uint64_t)st.st_mtime ^ ((uint64_t)st.st_size << 20)) * 0x100000001b3ull;
+        if (stat(f.c_str(), &st) == 0) h = (h ^ fnv(f.substr(f.rfind('/'))) ^ (uint64_t)st.st_mtime ^ ((uint64_t)st.st_size << 20)) * 0x100000001b3ull;
     }
     // (A/B knob: $TLAMC_JIT_DEFS replaces the register / workgroup shape of the by-pairs kernel in the generated unit; part of the cache key)
     // (-fno-slp-vectorize below: clang 22's SLP vectorizer — of no use to per-lane scalar code — crashes on the shift-and-or chains of some

@@ -1,0 +1,285 @@
+// state_graph.hip — the HOST half of everything that consumes the state graph's CSR arrays (state_graph.h): the reads, the strongly
+// connected components, the fairness check and its counterexample.  One object in the library: no lowering is named below this line,
+// and the engines of all of them — the units of engine.hip, the unit of generated code built at load time — call in here.  The
+// kernels and the two device scans are engine_live.h's.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "state_graph.h"
+#include "engine_live.h"   // k_scc_* / k_live_*: the kernels; liveness.h: the rule the counterexample builder runs too
+
+namespace mc {
+
+// ------------------------------------------------------------------------------- the graph's rows
+int StateGraph::read(uint64_t first, uint64_t count, uint64_t *offsets_out, uint32_t *dst_out, int32_t *action_out, size_t *nedges_inout) {
+    if (!built) { set_error("mc_engine_graph_read: no graph (mc_engine_graph builds it; the next search releases it)"); return MC_ESTATE; }
+    if (first > info.states || count > info.states - first) { set_error("mc_engine_graph_read: range beyond the graph's states"); return MC_EBADCFG; }
+    HIP_TRY(hipSetDevice(device));
+    std::vector<uint64_t> off((size_t)count + 1);
+    HIP_TRY(hipMemcpy(off.data(), offsets.p + first, off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    const uint64_t e0 = off[0], ne = off[count] - e0;
+    if (ne > *nedges_inout || !offsets_out || (ne && (!dst_out || !action_out))) {
+        *nedges_inout = (size_t)ne;
+        set_error("mc_engine_graph_read: buffer too small (" + std::to_string((unsigned long long)ne) + " edges)");
+        return MC_EBADCFG;
+    }
+    for (uint64_t k = 0; k <= count; k++) offsets_out[k] = off[k] - e0;
+    if (ne) {
+        std::vector<int16_t> a16((size_t)ne);
+        HIP_TRY(hipMemcpy(dst_out, dst.p + e0, ne * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(a16.data(), act.p + e0, ne * sizeof(int16_t), hipMemcpyDeviceToHost));
+        for (uint64_t k = 0; k < ne; k++) action_out[k] = a16[k];
+    }
+    *nedges_inout = (size_t)ne;
+    return MC_OK;
+}
+
+// ------------------------------------------------------------------------------- components and fairness (engine_live.h)
+// One kernel over all states: the launches of this section differ in the kernel and its arguments only.
+template <class K, class... A>
+static void live_launch(hipStream_t stream, K kernel, uint64_t n, A... args) {
+    if (n) hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, args...);
+}
+// SCC_BATCH sweeps, then one read of the flag; until a whole batch changed nothing.  `rounds` counts the sweeps launched.
+template <class F>
+static int live_fixed_point(hipStream_t stream, unsigned *flag, uint32_t &rounds, F &&sweep) {
+    for (;;) {
+        HIP_TRY(hipMemsetAsync(flag, 0, sizeof(unsigned), stream));
+        for (int k = 0; k < SCC_BATCH; ++k) sweep();
+        rounds += SCC_BATCH;
+        unsigned h = 0;
+        HIP_TRY(hipMemcpyAsync(&h, flag, sizeof h, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (!h) return MC_OK;
+    }
+}
+int StateGraph::scc(hipStream_t stream, mc_scc_info *out) {
+    lv.release();
+    const uint64_t n = info.states;
+    HIP_TRY(hipSetDevice(device));
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = scc_build(n, stream);
+    if (rc) { lv.release(); return rc; }
+    lv.sinfo.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    lv.scc_built = true;
+    *out = lv.sinfo;
+    return MC_OK;
+}
+int StateGraph::scc_build(uint64_t n, hipStream_t stream) {
+    DevBuf<uint32_t> indeg;   // build-time only: the in-degrees, then the fill's cursors
+    DevBuf<unsigned> flag;
+    DevBuf<LiveCounters> d_lc;
+    DevBuf<char> scan_tmp;
+    int rc;
+    if ((rc = graph_alloc(indeg, n + 1, "the in-degrees", "mc_engine_scc"))) return rc;
+    if ((rc = graph_alloc(lv.toff, n + 1, "the transpose's row offsets", "mc_engine_scc"))) return rc;
+    if ((rc = graph_alloc(lv.scc, n, "the component ids", "mc_engine_scc"))) return rc;
+    if ((rc = graph_alloc(lv.size, n, "the colours", "mc_engine_scc"))) return rc;
+    if ((rc = graph_alloc(flag, 1, "the fixed-point flag", "mc_engine_scc"))) return rc;
+    if ((rc = graph_alloc(d_lc, 1, "the counters", "mc_engine_scc"))) return rc;
+    const uint64_t *off = offsets.p;
+    const uint32_t *dst = this->dst.p;
+    // ---- transpose
+    HIP_TRY(hipMemsetAsync(indeg, 0, (n + 1) * sizeof(uint32_t), stream));
+    live_launch(stream, k_live_indegree, n, off, dst, indeg.p);
+    HIP_TRY(hipGetLastError());
+    if ((rc = scan_exclusive_u32_to_u64(indeg.p, lv.toff.p, n + 1, scan_tmp, stream, "mc_engine_scc"))) return rc;
+    uint64_t tedges = 0;
+    HIP_TRY(hipMemcpyAsync(&tedges, lv.toff.p + n, sizeof tedges, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if ((rc = graph_alloc(lv.tsrc, tedges, "the transpose's sources", "mc_engine_scc"))) return rc;
+    HIP_TRY(hipMemsetAsync(indeg, 0, (n + 1) * sizeof(uint32_t), stream));
+    live_launch(stream, k_live_tfill, n, off, dst, (const uint64_t *)lv.toff.p, indeg.p, lv.tsrc.p);
+    HIP_TRY(hipGetLastError());
+    // ---- trim and colouring until no state is live
+    const uint64_t *toff = lv.toff.p;
+    const uint32_t *tsrc = lv.tsrc.p;
+    uint32_t *scc = lv.scc.p, *colour = lv.size.p;
+    HIP_TRY(hipMemsetAsync(scc, 0xff, n * sizeof(uint32_t), stream));
+    uint32_t trim_rounds = 0, colour_rounds = 0, back_rounds = 0, passes = 0;
+    for (; n;) {
+        if ((rc = live_fixed_point(stream, flag.p, trim_rounds, [&] { live_launch(stream, k_scc_trim, n, off, dst, toff, tsrc, scc, flag.p); }))) return rc;
+        unsigned live = 0;
+        HIP_TRY(hipMemsetAsync(flag, 0, sizeof(unsigned), stream));
+        live_launch(stream, k_scc_colour_init, n, (const uint32_t *)scc, colour, flag.p);
+        HIP_TRY(hipMemcpyAsync(&live, flag, sizeof live, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (!live) break;
+        ++passes;
+        if ((rc = live_fixed_point(stream, flag.p, colour_rounds, [&] { live_launch(stream, k_scc_colour, n, toff, tsrc, (const uint32_t *)scc, colour, flag.p); }))) return rc;
+        live_launch(stream, k_scc_roots, n, scc, (const uint32_t *)colour);
+        if ((rc = live_fixed_point(stream, flag.p, back_rounds, [&] { live_launch(stream, k_scc_back, n, off, dst, scc, (const uint32_t *)colour, flag.p); }))) return rc;
+    }
+    // ---- ids: the least index of the component; sizes; statistics (the colour array serves as `least`, then as `size`)
+    LiveCounters lc;
+    memset(&lc, 0, sizeof lc);
+    lc.first_root = ~0u;
+    HIP_TRY(hipMemcpyAsync(d_lc, &lc, sizeof lc, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(colour, 0xff, (n ? n : 1) * sizeof(uint32_t), stream));
+    live_launch(stream, k_scc_least, n, (const uint32_t *)scc, colour);
+    live_launch(stream, k_scc_renumber, n, scc, (const uint32_t *)colour);
+    HIP_TRY(hipMemsetAsync(colour, 0, (n ? n : 1) * sizeof(uint32_t), stream));
+    live_launch(stream, k_scc_sizes, n, (const uint32_t *)scc, colour);
+    live_launch(stream, k_scc_stats, n, (const uint32_t *)scc, (const uint32_t *)colour, d_lc.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&lc, d_lc, sizeof lc, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    memset(&lv.sinfo, 0, sizeof lv.sinfo);
+    lv.sinfo.states = n;
+    lv.sinfo.components = lc.components;
+    lv.sinfo.nontrivial = lc.nontrivial;
+    lv.sinfo.largest = lc.largest;
+    lv.sinfo.trim_rounds = trim_rounds;
+    lv.sinfo.colour_rounds = colour_rounds;
+    lv.sinfo.backward_rounds = back_rounds;
+    lv.sinfo.passes = passes;
+    return MC_OK;
+}
+int StateGraph::scc_read(uint64_t first, uint64_t count, uint32_t *scc_out) {
+    if (!built || !lv.scc_built) { set_error("mc_engine_scc_read: no components (mc_engine_scc finds them; the next search releases them)"); return MC_ESTATE; }
+    if (first > info.states || count > info.states - first) { set_error("mc_engine_scc_read: range beyond the graph's states"); return MC_EBADCFG; }
+    HIP_TRY(hipSetDevice(device));
+    if (count) HIP_TRY(hipMemcpy(scc_out, lv.scc.p + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+// After the engine's k_live_proc<S> (enqueued on `stream`, proc[] filled): per state the masks, per component the rule.
+int StateGraph::live_check(uint64_t all, uint64_t fair, hipStream_t stream, std::chrono::steady_clock::time_point started, mc_live_info *out) {
+    const uint64_t n = info.states;
+    DevBuf<LiveCounters> d_lc;
+    int rc;
+    if ((rc = graph_alloc(lv.taken, n, "the components' taken masks", "mc_engine_liveness"))) return rc;
+    if ((rc = graph_alloc(lv.disabled, n, "the components' disabled masks", "mc_engine_liveness"))) return rc;
+    if ((rc = graph_alloc(lv.done, n, "the components' Done flags", "mc_engine_liveness"))) return rc;
+    if ((rc = graph_alloc(d_lc, 1, "the counters", "mc_engine_liveness"))) return rc;
+    LiveCounters lc;
+    memset(&lc, 0, sizeof lc);
+    lc.first_root = ~0u;
+    HIP_TRY(hipMemcpyAsync(d_lc, &lc, sizeof lc, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(lv.taken, 0, (n ? n : 1) * sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(lv.disabled, 0, (n ? n : 1) * sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(lv.done, 0, (n ? n : 1) * sizeof(unsigned), stream));
+    live_launch(stream, k_live_reduce, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, (const int8_t *)lv.proc.p, (const uint32_t *)lv.scc.p,
+                (const uint32_t *)lv.size.p, all, lv.taken.p, lv.disabled.p, lv.done.p);
+    live_launch(stream, k_live_verdict, n, (const uint32_t *)lv.scc.p, (const uint32_t *)lv.size.p, (const unsigned long long *)lv.taken.p,
+                (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p, all, fair, d_lc.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&lc, d_lc, sizeof lc, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    memset(&lv.linfo, 0, sizeof lv.linfo);
+    lv.linfo.violated = lc.fair_components ? 1 : 0;
+    lv.linfo.fair_components = lc.fair_components;
+    if (lc.fair_components) {
+        uint32_t sz = 0;
+        HIP_TRY(hipMemcpy(&sz, lv.size.p + lc.first_root, sizeof sz, hipMemcpyDeviceToHost));
+        lv.linfo.root = lc.first_root;
+        lv.linfo.root_size = sz;
+    }
+    lv.linfo.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count();
+    lv.fair = fair;
+    lv.checked = true;
+    *out = lv.linfo;
+    return MC_OK;
+}
+// The counterexample of the last mc_engine_liveness, built on the host from the arrays (deterministic given them).
+// prefix: from an initial state to the chosen component's id (its least state), one BFS level back per step along the transpose: the
+// least source in the previous level (level boundaries: level_start).  cycle: a closed walk inside the component that starts at
+// that state and, for every weakly fair process, takes a real step of it or passes a state where it is disabled; the last entry has an
+// edge back to the first.  Empty = the behaviour stutters in the prefix's last state for ever.
+int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout) {
+    if (!built || !lv.checked) { set_error("mc_engine_liveness_trace: no liveness check (mc_engine_liveness runs it; the next search releases it)"); return MC_ESTATE; }
+    if (!lv.linfo.violated) { set_error("mc_engine_liveness_trace: the property holds: there is no counterexample"); return MC_ESTATE; }
+    HIP_TRY(hipSetDevice(device));
+    const uint64_t n = info.states, edges = info.edges;
+    const uint32_t root = (uint32_t)lv.linfo.root;
+    // ---- prefix
+    std::vector<uint32_t> prefix{root};
+    auto level_of = [&](uint32_t x) { return (size_t)(std::upper_bound(level_start.begin(), level_start.end(), (uint64_t)x) - level_start.begin()) - 1; };
+    for (uint32_t cur = root; level_of(cur) > 0;) {
+        const size_t L = level_of(cur);
+        uint64_t row[2];
+        HIP_TRY(hipMemcpy(row, lv.toff.p + cur, sizeof row, hipMemcpyDeviceToHost));
+        std::vector<uint32_t> src((size_t)(row[1] - row[0]));
+        if (!src.empty()) HIP_TRY(hipMemcpy(src.data(), lv.tsrc.p + row[0], src.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        uint32_t best = ~0u;
+        for (uint32_t u : src) if (u >= level_start[L - 1] && u < level_start[L] && u < best) best = u;
+        if (best == ~0u) { set_error("mc_engine_liveness_trace: state " + std::to_string(cur) + " has no in-edge from the level before its own"); return MC_ESTATE; }
+        prefix.push_back(best);
+        cur = best;
+    }
+    std::reverse(prefix.begin(), prefix.end());
+    // ---- cycle
+    std::vector<uint64_t> off((size_t)n + 1);
+    std::vector<uint32_t> dst((size_t)edges), scc((size_t)n);
+    std::vector<int8_t> proc((size_t)edges);
+    HIP_TRY(hipMemcpy(off.data(), offsets.p, off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(scc.data(), lv.scc.p, scc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (edges) {
+        HIP_TRY(hipMemcpy(dst.data(), this->dst.p, dst.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(proc.data(), lv.proc.p, proc.size() * sizeof(int8_t), hipMemcpyDeviceToHost));
+    }
+    std::vector<uint32_t> members;
+    for (uint64_t v = 0; v < n; ++v) if (scc[(size_t)v] == root) members.push_back((uint32_t)v);
+    std::vector<uint32_t> par((size_t)n, ~0u);
+    std::vector<uint32_t> cycle{root};   // the walk so far; its last entry is where it stands
+    // breadth-first inside the component, rows in index order; appends the states after `from` up to `to`
+    auto go = [&](uint32_t to) {
+        const uint32_t from = cycle.back();
+        if (from == to) return true;
+        for (uint32_t m : members) par[m] = ~0u;
+        std::vector<uint32_t> q{from};
+        par[from] = from;
+        for (size_t h = 0; h < q.size() && par[to] == ~0u; ++h)
+            for (uint64_t k = off[q[h]]; k < off[q[h] + 1]; ++k) {
+                const uint32_t d = dst[(size_t)k];
+                if (scc[d] == root && par[d] == ~0u) { par[d] = q[h]; q.push_back(d); }
+            }
+        if (par[to] == ~0u) return false;
+        std::vector<uint32_t> path;
+        for (uint32_t x = to; x != from; x = par[x]) path.push_back(x);
+        cycle.insert(cycle.end(), path.rbegin(), path.rend());
+        return true;
+    };
+    bool ok = true;
+    for (int p = 0; p < 64 && ok; ++p) {
+        if (!(lv.fair >> p & 1)) continue;
+        bool found = false;
+        for (size_t mi = 0; mi < members.size() && !found; ++mi) {   // a real step of p inside the component: the first in index order
+            const uint32_t u = members[mi];
+            for (uint64_t k = off[u]; k < off[u + 1] && !found; ++k)
+                if (proc[(size_t)k] == p && live_real_step(p, u, dst[(size_t)k]) && scc[dst[(size_t)k]] == root) {
+                    found = true;
+                    ok = go(u);
+                    cycle.push_back(dst[(size_t)k]);
+                }
+        }
+        for (size_t mi = 0; mi < members.size() && !found; ++mi) {   // else a state where p is disabled
+            const uint32_t u = members[mi];
+            uint64_t en = 0, tk = 0;
+            bool dn = false;
+            live_state(u, dst.data() + off[u], proc.data() + off[u], off[u + 1] - off[u], scc.data(), &en, &tk, &dn);
+            if (!(en >> p & 1)) { found = true; ok = go(u); }
+        }
+        if (!found) ok = false;
+    }
+    if (ok) ok = go(root);
+    if (!ok) { set_error("mc_engine_liveness_trace: the chosen component is not fair or not connected (the arrays disagree with the verdict)"); return MC_ESTATE; }
+    cycle.pop_back();   // (the walk ended on `root` again: the closing edge is implied; a walk that never moved leaves nothing)
+    if (prefix.size() > *nprefix_inout || cycle.size() > *ncycle_inout || !prefix_out || (!cycle.empty() && !cycle_out)) {
+        *nprefix_inout = prefix.size();
+        *ncycle_inout = cycle.size();
+        set_error("mc_engine_liveness_trace: buffers too small (" + std::to_string(prefix.size()) + " + " + std::to_string(cycle.size()) + " states)");
+        return MC_EBADCFG;
+    }
+    memcpy(prefix_out, prefix.data(), prefix.size() * sizeof(uint32_t));
+    if (!cycle.empty()) memcpy(cycle_out, cycle.data(), cycle.size() * sizeof(uint32_t));
+    *nprefix_inout = prefix.size();
+    *ncycle_inout = cycle.size();
+    return MC_OK;
+}
+
+}  // namespace mc
