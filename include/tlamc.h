@@ -303,6 +303,57 @@ int mc_engine_scc(mc_engine *e, mc_scc_info *out);
 int mc_engine_scc_read(mc_engine *e, uint64_t first, uint64_t count, uint32_t *scc_out);
 int mc_engine_liveness(mc_engine *e, uint64_t weak_fair_mask, mc_live_info *out);
 int mc_engine_liveness_trace(mc_engine *e, uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout);
+
+/* ------------------------------------------------------------------ <>Q, []<>Q, <>[]P and P ~> Q under weak fairness
+ * A cfg PROPERTY of a compiled PlusCal program other than `Termination` names a definition of one of these four shapes over state
+ * predicates, under bounded `\A`s and conjunctions; mc_program_live_property lists the checks it becomes (one per quantifier instance)
+ * and the names the front end refused, with the reason.  The distinct predicates are compiled with the program and evaluated on demand:
+ * mc_engine_predicates: bit k of bits_out[i] = predicate k in arena state first + i (built, with the graph, on first use; 4 bytes per
+ * state; MC_ESTATE with the predicate and the least state where evaluating one fails).
+ * mc_engine_liveness_check: one check, as a triple of state sets — M, where a violating suffix may stay; S, where it may be entered;
+ * T, of which a state must recur:
+ *     kind                          M        S                        T
+ *     MC_LIVE_LEADS_TO    P ~> Q    ~Q       P /\ ~Q                  all
+ *     MC_LIVE_INF_OFTEN   []<>Q     ~Q       ~Q                       all
+ *     MC_LIVE_EVENTUALLY  <>Q       ~Q       initial states with ~Q   all
+ *     MC_LIVE_STABLE      <>[]P     all      all                      ~P
+ * violated iff some strongly connected component C of the graph induced by M (one-state components included) is fair — every fair
+ * process takes a step u -> v, u # v, inside C or is disabled, IN THE FULL GRAPH, in some state of C —, holds a state of T and is
+ * reachable inside M from a state of S that lies in M.  One component build per distinct M, kept while the graph lives; mc_engine_scc's
+ * components are untouched.  witness: the least arena index among the S states from which such a component is reached; root: the
+ * component the counterexample ends in (from the witness along strictly decreasing distance, the least successor each time).
+ * mc_engine_liveness_trace then gives that counterexample: the prefix runs from an initial state through the witness to the first
+ * state of the component, the cycle is a closed walk from there that meets the fairness condition by itself and, for MC_LIVE_STABLE,
+ * passes the component's least ~P state.  Device memory beside mc_engine_liveness's: 4 bytes per state for the predicate bits, 4 for
+ * the distances, 8 per distinct mask.  Errors: mc_engine_liveness's, and MC_EBADCFG for a predicate index the program does not
+ * have, a refused property or an unknown kind. */
+enum { MC_LIVE_LEADS_TO = 0, MC_LIVE_INF_OFTEN = 1, MC_LIVE_EVENTUALLY = 2, MC_LIVE_STABLE = 3 };
+typedef struct mc_live_property {
+    char    origin[64];        /* the cfg's PROPERTY name                                            */
+    char    name[128];         /* of this check: origin, `.k` for conjunct k of several, `[i = v]`   */
+    int32_t kind;              /* MC_LIVE_*; -1 when refused                                         */
+    int32_t p, q;              /* predicate indices (P / Q of the table above), -1 = none            */
+    int32_t refused;           /* 1: the front end does not check this name                          */
+    char    reason[256];       /* why (refused)                                                      */
+} mc_live_property;
+typedef struct mc_live_check_info {
+    int32_t  violated;
+    uint32_t sweeps;           /* of the reach pass, in batches of 8                                 */
+    uint64_t fair_components;  /* fair components of the masked graph that hold a T state            */
+    uint64_t witness;          /* valid when violated: see above                                     */
+    uint64_t root;
+    uint64_t root_size;
+    uint64_t mask_states;      /* states in M                                                        */
+    uint64_t bad_starts;       /* S states from which a violating component is reached               */
+    uint32_t scc_builds;       /* component builds this call needed (0: the mask's were kept)        */
+    uint32_t pad;
+    double   seconds;          /* everything the call did, component builds included                 */
+} mc_live_check_info;
+int mc_engine_predicates(mc_engine *e, uint64_t first, uint64_t count, uint32_t *bits_out);
+int mc_engine_liveness_check(mc_engine *e, uint64_t weak_fair_mask, const mc_live_property *prop, mc_live_check_info *out);
+/* the component ids the last mc_engine_liveness_check judged: those of the graph induced by its M (the least arena index of the state's
+ * component; a state outside M is its own) — mc_engine_scc_read's array for MC_LIVE_STABLE.  MC_ESTATE without such a check. */
+int mc_engine_liveness_components(mc_engine *e, uint64_t first, uint64_t count, uint32_t *scc_out);
 /* copy `count` resident states starting at arena index `first` (discovery order: level by level)
  * to the host, mc_state_bytes() bytes each — TLC's "states/" dump, for tests and tooling */
 int mc_engine_read_states(mc_engine *e, uint64_t first, uint64_t count, uint8_t *out);
@@ -637,6 +688,10 @@ int mc_program_fairness(const mc_program *p, uint64_t *weak_fair_mask, const cha
 /* the cfg's PROPERTY / PROPERTIES names, in cfg order; NULL past the last (what a caller that runs the search itself — `mc -gpus` —
  * must name as NOT checked) */
 const char *mc_program_property(const mc_program *p, int index);
+/* the checks (and refusals) the cfg's PROPERTY names other than Termination become, in cfg order: MC_OK, or MC_EBADCFG past the last.
+ * mc_program_live_predicate: the text of predicate number index (with the quantifier values it was compiled for), NULL past the last */
+int mc_program_live_property(const mc_program *p, int index, mc_live_property *out);
+const char *mc_program_live_predicate(const mc_program *p, int index);
 void mc_program_free(mc_program *p);
 
 /* ------------------------------------------------------------------ helpers (host only) */

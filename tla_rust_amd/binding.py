@@ -112,6 +112,20 @@ class LiveInfo(C.Structure):
                 ("root_size", C.c_uint64), ("seconds", C.c_double)]
 
 
+class LiveProperty(C.Structure):
+    """mc_live_property"""
+    _fields_ = [("origin", C.c_char * 64), ("name", C.c_char * 128), ("kind", C.c_int32), ("p", C.c_int32), ("q", C.c_int32),
+                ("refused", C.c_int32), ("reason", C.c_char * 256)]
+
+
+class LiveCheckInfo(C.Structure):
+    """mc_live_check_info"""
+    _fields_ = [("violated", C.c_int32), ("sweeps", C.c_uint32), ("fair_components", C.c_uint64), ("witness", C.c_uint64), ("root", C.c_uint64),
+                ("root_size", C.c_uint64), ("mask_states", C.c_uint64), ("bad_starts", C.c_uint64), ("scc_builds", C.c_uint32), ("pad", C.c_uint32),
+                ("seconds", C.c_double)]
+
+
+LIVE_KINDS = ["leads-to", "always-eventually", "eventually", "eventually-always"]   # MC_LIVE_*: P ~> Q, []<>Q, <>Q, <>[]P
 MC_DOT_ACTIONLABELS, MC_DOT_COLORIZE = 1, 2   # mc_check_files_dot
 
 
@@ -249,6 +263,12 @@ def lib():
         L.mc_program_invariant.argtypes = [C.c_void_p, C.c_int]
         L.mc_program_invariant.restype = C.c_char_p
         L.mc_program_fairness.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_char_p)]
+        L.mc_program_live_property.argtypes = [C.c_void_p, C.c_int, C.POINTER(LiveProperty)]
+        L.mc_program_live_predicate.argtypes = [C.c_void_p, C.c_int]
+        L.mc_program_live_predicate.restype = C.c_char_p
+        L.mc_engine_predicates.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.mc_engine_liveness_components.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.mc_engine_liveness_check.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(LiveProperty), C.POINTER(LiveCheckInfo)]
         L.mc_program_property.argtypes = [C.c_void_p, C.c_int]
         L.mc_program_property.restype = C.c_char_p
         L.mc_program_free.argtypes = [C.c_void_p]
@@ -428,6 +448,34 @@ class Engine:
         li = LiveInfo()
         _check(lib().mc_engine_liveness(self._h, weak_fair_mask, C.byref(li)), "mc_engine_liveness")
         return Result((k, getattr(li, k)) for k, _ in LiveInfo._fields_ if k != "pad")
+
+    def predicates(self, count=None):
+        """mc_engine_predicates: numpy uint32, one entry per arena state of the last search (the first `count`; None: all of them, which
+        builds the state graph anew): bit k = predicate k of the program's temporal properties (Program.live_predicates) holds in
+        the state."""
+        import numpy as np
+        n = self.graph_info().states if count is None else count
+        out = np.zeros(max(1, n), dtype=np.uint32)
+        _check(lib().mc_engine_predicates(self._h, 0, n, out.ctypes.data), "mc_engine_predicates")
+        return out[:n]
+
+    def check_property(self, weak_fair_mask, prop):
+        """mc_engine_liveness_check: one entry of Program.live_properties under weak fairness of the process instances in the mask,
+        decided on the complete state graph of the last search: a dict with violated, sweeps, fair_components, witness, root, root_size,
+        mask_states, bad_starts, scc_builds, seconds.  liveness_trace() then gives the counterexample of a violated check."""
+        lp = LiveProperty(prop["origin"].encode(), prop["name"].encode(), prop["kind"], prop["p"], prop["q"], 1 if prop["refused"] else 0,
+                          (prop["reason"] or "").encode())
+        ci = LiveCheckInfo()
+        _check(lib().mc_engine_liveness_check(self._h, weak_fair_mask, C.byref(lp), C.byref(ci)), "mc_engine_liveness_check")
+        return Result((k, getattr(ci, k)) for k, _ in LiveCheckInfo._fields_ if k != "pad")
+
+    def check_components(self, count):
+        """mc_engine_liveness_components: numpy uint32, the component ids of the first `count` states in the graph the last
+        check_property looked at (the subgraph induced by its mask: a state outside it is a component of its own)"""
+        import numpy as np
+        out = np.zeros(max(1, count), dtype=np.uint32)
+        _check(lib().mc_engine_liveness_components(self._h, 0, count, out.ctypes.data), "mc_engine_liveness_components")
+        return out[:count]
 
     def liveness_trace(self):
         """mc_engine_liveness_trace: (prefix, cycle) of the last violated liveness check, as lists of arena indices: a path from an
@@ -718,6 +766,15 @@ class Program:
         self.ninst = _check(lib().mc_program_fairness(h, C.byref(mask), C.byref(why)), "mc_program_fairness")
         self.fair_mask = int(mask.value)             # bit k: process instance k (slot order) is weakly fair
         self.live_refusal = why.value.decode() if why.value else None   # why Engine.liveness cannot decide Termination for it (None: it can)
+        # the cfg's PROPERTY names other than Termination: one dict per check (a quantifier instance of a conjunct) or per refused name —
+        # origin, name, kind (MC_LIVE_*, LIVE_KINDS), p, q (indices into live_predicates, -1 = none), refused, reason
+        self.live_properties, self.live_predicates = [], []
+        lp = LiveProperty()
+        while lib().mc_program_live_property(h, len(self.live_properties), C.byref(lp)) == 0:
+            self.live_properties.append(Result(origin=lp.origin.decode(), name=lp.name.decode(), kind=int(lp.kind), p=int(lp.p), q=int(lp.q),
+                                               refused=bool(lp.refused), reason=lp.reason.decode() or None))
+        while lib().mc_program_live_predicate(h, len(self.live_predicates)):
+            self.live_predicates.append(lib().mc_program_live_predicate(h, len(self.live_predicates)).decode())
 
     def translated(self):
         return lib().mc_program_translated(self._h).decode()

@@ -117,6 +117,8 @@ struct EngineBase {
     const std::vector<uint64_t> *graph_levels = nullptr;   // the level table of the last search
     virtual int graph(mc_graph_info *out) = 0;
     virtual int liveness(uint64_t weak_fair_mask, mc_live_info *out) = 0;
+    virtual int predicates(uint64_t first, uint64_t count, uint32_t *bits_out) = 0;
+    virtual int liveness_check(uint64_t weak_fair_mask, const mc_live_property *prop, mc_live_check_info *out) = 0;
     int graph_read(uint64_t first, uint64_t count, uint64_t *offsets_out, uint32_t *dst_out, int32_t *action_out, size_t *nedges_inout) {
         return gr.read(first, count, offsets_out, dst_out, action_out, nedges_inout);
     }
@@ -127,6 +129,7 @@ struct EngineBase {
         return gr.scc(graph_stream, out);
     }
     int scc_read(uint64_t first, uint64_t count, uint32_t *scc_out) { return gr.scc_read(first, count, scc_out); }
+    int liveness_components(uint64_t first, uint64_t count, uint32_t *scc_out) { return gr.live_scc_read(first, count, scc_out); }
     int liveness_trace(uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout) {
         return gr.live_trace(*graph_levels, prefix_out, nprefix_inout, cycle_out, ncycle_inout);
     }
@@ -597,7 +600,93 @@ struct Engine : EngineBase {
             if (int rc = graph_alloc(lv.proc, edges, "the edges' processes", "mc_engine_liveness")) return rc;
             HIP_TRY(hipMemsetAsync(lv.proc, 0xff, (edges ? edges : 1) * sizeof(int8_t), stream));
             graph_chunks(k_live_proc<S>, 0, fr.lo, (const uint64_t *)gr.offsets.p, lv.proc.p);
+            lv.proc_built = true;
             return gr.live_check(all, fair, stream, t0, out);
+        }
+    }
+    // ------------------------------------------------------------------------------- the predicates of the cfg's temporal properties
+    // (LivePred<S>, k_live_pred<S>) and one (M, S, T) check over them
+    int predicates_build(const char *call) {
+        if constexpr (!LivePred<S>::HAS) {
+            return MC_ENOSPEC;
+        } else {
+            auto &lv = gr.lv;
+            if (lv.pred_built) return MC_OK;
+            LivePredTab tab;
+            memset(&tab, 0, sizeof tab);
+            tab.n = vm_live_preds(prm.host, tab.entry, LIVE_MAX_PREDS);
+            if (tab.n > LIVE_MAX_PREDS) { set_error(std::string(call) + ": at most 32 predicates"); return MC_EBADCFG; }
+            const uint64_t n = gr.info.states;
+            HIP_TRY(hipSetDevice(cfg.device));
+            DevBuf<unsigned long long> d_bad;
+            if (int rc = graph_alloc(lv.pred, n, "the predicate bits", call)) return rc;
+            if (int rc = graph_alloc(d_bad, 1, "the counters", call)) return rc;
+            unsigned long long bad = ~0ull;
+            HIP_TRY(hipMemcpyAsync(d_bad, &bad, sizeof bad, hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemsetAsync(lv.pred, 0, (n ? n : 1) * sizeof(uint32_t), stream));
+            if (tab.n) graph_chunks(k_live_pred<S>, 0, n, tab, lv.pred.p, d_bad.p);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (bad != ~0ull) {
+                lv.pred.reset();
+                set_error(std::string(call) + ": evaluating the predicate `" + vm_live_pred_text(prm.host, (int)(bad & 0xff)) + "` fails in state " +
+                          std::to_string(bad >> 8) + " (an evaluation error: a function applied outside its domain, an overflow, ...)");
+                return MC_ESTATE;
+            }
+            lv.pred_built = true;
+            return MC_OK;
+        }
+    }
+    int predicates(uint64_t first, uint64_t count, uint32_t *bits_out) override {
+        if (cfg.shard_count > 1) { set_error("mc_engine_predicates: not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
+        if constexpr (!LivePred<S>::HAS) {
+            set_error("mc_engine_predicates: this lowering has no compiled predicates (compiled PlusCal programs only)");
+            return MC_ENOSPEC;
+        } else {
+            if (!gr.built) { mc_graph_info gi; if (int rc = graph(&gi)) return rc; }
+            if (int rc = predicates_build("mc_engine_predicates")) return rc;
+            return gr.pred_read(first, count, bits_out);
+        }
+    }
+    int liveness_check(uint64_t fair, const mc_live_property *prop, mc_live_check_info *out) override {
+        memset(out, 0, sizeof *out);
+        if (cfg.shard_count > 1) { set_error("mc_engine_liveness_check: not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
+        if constexpr (!LiveProc<S>::HAS || !LivePred<S>::HAS) {
+            set_error("mc_engine_liveness_check: this lowering has no process instances (compiled PlusCal programs only)");
+            return MC_ENOSPEC;
+        } else {
+            if (!fr.have_run || ck.pending || fr.have_viol || fr.hi != fr.lo) {
+                set_error("mc_engine_liveness_check: needs a search of this engine that finished without a violation and with an empty queue (the complete state graph)");
+                return MC_ESTATE;
+            }
+            const int np = LiveProc<S>::count(prm);
+            if (np > LIVE_MAX_PROCS) { set_error("mc_engine_liveness_check: at most 64 process instances"); return MC_EBADCFG; }
+            const uint64_t all = np >= 64 ? ~0ull : (1ull << np) - 1;
+            if (fair & ~all) { set_error("mc_engine_liveness_check: the fairness mask names a process instance the program does not have"); return MC_EBADCFG; }
+            if (prop->refused) { set_error(std::string("mc_engine_liveness_check: the front end refused ") + prop->name); return MC_EBADCFG; }
+            const int npred = vm_live_preds(prm.host, nullptr, 0);
+            const int kind = prop->kind;
+            if (kind < LIVE_LEADS_TO || kind > LIVE_STABLE) { set_error("mc_engine_liveness_check: unknown kind " + std::to_string(kind)); return MC_EBADCFG; }
+            const bool need_p = kind == LIVE_LEADS_TO || kind == LIVE_STABLE, need_q = kind != LIVE_STABLE;
+            if ((need_p && (prop->p < 0 || prop->p >= npred)) || (need_q && (prop->q < 0 || prop->q >= npred)) || npred > LIVE_MAX_PREDS) {
+                set_error("mc_engine_liveness_check: a predicate index the program does not have (it has " + std::to_string(npred) + " predicates)");
+                return MC_EBADCFG;
+            }
+            const auto t0 = std::chrono::steady_clock::now();
+            if (!gr.built || !gr.lv.scc_built) { mc_scc_info si; if (int rc = scc(&si)) return rc; }
+            auto &lv = gr.lv;
+            lv.checked = false;
+            HIP_TRY(hipSetDevice(cfg.device));
+            if (!lv.proc_built) {
+                const uint64_t edges = gr.info.edges;
+                if (int rc = graph_alloc(lv.proc, edges, "the edges' processes", "mc_engine_liveness_check")) return rc;
+                HIP_TRY(hipMemsetAsync(lv.proc, 0xff, (edges ? edges : 1) * sizeof(int8_t), stream));
+                graph_chunks(k_live_proc<S>, 0, fr.lo, (const uint64_t *)gr.offsets.p, lv.proc.p);
+                lv.proc_built = true;
+            }
+            if (int rc = predicates_build("mc_engine_liveness_check")) return rc;
+            return gr.live_check_masked(all, fair, kind, need_p ? prop->p : -1, need_q ? prop->q : -1, stream, t0, out);
         }
     }
 
@@ -2169,6 +2258,15 @@ int mc_engine_scc_read(mc_engine *e, uint64_t first, uint64_t count, uint32_t *s
     return e && (scc_out || !count) ? e->impl->scc_read(first, count, scc_out) : MC_EBADCFG;
 }
 int mc_engine_liveness(mc_engine *e, uint64_t weak_fair_mask, mc_live_info *out) { return e && out ? e->impl->liveness(weak_fair_mask, out) : MC_EBADCFG; }
+int mc_engine_predicates(mc_engine *e, uint64_t first, uint64_t count, uint32_t *bits_out) {
+    return e && (bits_out || !count) ? e->impl->predicates(first, count, bits_out) : MC_EBADCFG;
+}
+int mc_engine_liveness_check(mc_engine *e, uint64_t weak_fair_mask, const mc_live_property *prop, mc_live_check_info *out) {
+    return e && prop && out ? e->impl->liveness_check(weak_fair_mask, prop, out) : MC_EBADCFG;
+}
+int mc_engine_liveness_components(mc_engine *e, uint64_t first, uint64_t count, uint32_t *scc_out) {
+    return e && (scc_out || !count) ? e->impl->liveness_components(first, count, scc_out) : MC_EBADCFG;
+}
 int mc_engine_liveness_trace(mc_engine *e, uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout) {
     return e && nprefix_inout && ncycle_inout ? e->impl->liveness_trace(prefix_out, nprefix_inout, cycle_out, ncycle_inout) : MC_EBADCFG;
 }

@@ -9,6 +9,8 @@
 //   k_graph_degree   pass 1, one lane per expanded state: the slot loop to the wavefront's largest nslots, degree[i] = its edges
 //   k_graph_fill     pass 2, the same loop: dst[offsets[i] + k], act[offsets[i] + k] in slot order
 //   k_live_proc      the loop a third time, for mc_engine_liveness: proc[offsets[i] + k] beside act[] (LiveProc<S>, liveness.h)
+//   k_live_pred      one lane per stored state, the same chunks: pred[i] = the state predicates of the cfg's temporal properties that hold
+//                    in it, one bit each (LivePred<S>, liveness.h)
 // Between the passes an exclusive scan turns degree into offsets.  Nothing here writes the arena, the seen-set or a counter of the search.
 // These are the kernels that know the lowering; whatever consumes the CSR arrays alone is compiled once, in state_graph.hip.
 #ifndef TLAMC_ENGINE_GRAPH_H
@@ -151,6 +153,26 @@ k_live_proc(typename S::Params prm, const uint64_t *__restrict__ arena, uint64_t
         if (out < end) proc[out] = (int8_t)LiveProc<S>::of(prm, slot);
         ++out;
     }
+}
+
+// pred[] for mc_engine_predicates / mc_engine_liveness_check: the arena row loaded as the walk loads it, every predicate of `tab` run on
+// it.  An evaluation error is no value: the least (state << 8 | predicate) of them is left in *first_bad (~0 = none).
+template <class S>
+__global__ void __launch_bounds__(256)
+k_live_pred(typename S::Params prm, const uint64_t *__restrict__ arena, uint64_t lo, uint64_t hi, uint64_t ncols,
+            const uint64_t *__restrict__, uint64_t, LivePredTab tab, uint32_t *__restrict__ pred, unsigned long long *first_bad) {
+    const uint64_t col = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t idx = (lo & ~63ull) + col;
+    if (!(col < ncols && idx >= lo && idx < hi)) return;
+    typename S::Local loc;
+    S::load(prm, arena_cref(arena, idx, S::words(prm)), loc);
+    uint32_t bits = 0;
+    for (int k = 0; k < tab.n && k < LIVE_MAX_PREDS; ++k) {
+        int32_t res = 0;
+        if (!LivePred<S>::eval(prm, loc, tab, k, res)) { atomicMin(first_bad, (unsigned long long)idx << 8 | (unsigned)k); continue; }
+        if (res) bits |= 1u << k;
+    }
+    pred[idx] = bits;
 }
 
 }  // namespace mc

@@ -23,6 +23,12 @@
 //   fairness    k_live_reduce    per state the en / taken masks and the Done flag (live_state), OR-ed into the component's entry at
 //                                scc[v]: plain stores for one-state components, else one atomic per set of lanes that agree on it
 //               k_live_verdict   per component root the rule (live_violates); the number of fair non-Done components and the least root
+//   properties  (mc_engine_liveness_check) the same over the subgraph induced by a mask M of predicate bits:
+//               k_scc_mask       before the first trim: a state outside M is a component of its own, and live to nobody
+//               k_live_reduce<true> / k_live_verdict<true>   only states of M are merged and judged, "holds a T state" in the Done
+//                                flag's place; en comes from the full row, taken from edges whose two ends share the component
+//               k_live_reach     dist[v], to a fixed point: 0 in a violating component, else 1 + the least dist of a successor in M
+//               k_live_witness   the states of M, the S states with a dist, and the least of those
 //
 // Memory, beside the graph's 8 bytes per state and 6 per edge: 16 bytes per state (transpose offsets 8, scc 4, colour / size 4) and 4 per
 // edge (transpose) for mc_engine_scc, 4 more per state while the transpose is built; mc_engine_liveness adds 1 byte per edge (proc) and 20
@@ -100,6 +106,12 @@ k_scc_trim(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__r
         if (!out || !in) { scc[v] = (uint32_t)v; changed = true; }
     }
     live_raise(changed, flag);
+}
+// the masked build: scc[] is all SCC_LIVE when this runs
+static __global__ void __launch_bounds__(256)
+k_scc_mask(uint64_t n, const uint32_t *__restrict__ pred, LiveCheck ck, uint32_t *__restrict__ scc) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v < n && live_own_component(ck, pred[v])) scc[v] = (uint32_t)v;
 }
 static __global__ void __launch_bounds__(256)
 k_scc_colour_init(uint64_t n, const uint32_t *__restrict__ scc, uint32_t *__restrict__ colour, unsigned *flag) {
@@ -187,18 +199,25 @@ __device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) 
     return v;
 }
 
+// MASKED: scc / size are those of G[M]; only the states of M are merged, and `done` says "the component holds a T state"
+template <bool MASKED>
 static __global__ void __launch_bounds__(256)
 k_live_reduce(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ proc,
               const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, uint64_t all, unsigned long long *taken,
-              unsigned long long *disabled, unsigned *done) {
+              unsigned long long *disabled, unsigned *done, const uint32_t *__restrict__ pred, LiveCheck ck) {
     const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = v < n;
+    const bool active = v < n && (!MASKED || live_in_mask(ck, pred[v]));
     uint64_t en = 0, tk = 0;
     bool dn = false;
     uint32_t comp = 0;
     if (active) {
         const uint64_t o = offsets[v];
-        live_state((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc, &en, &tk, &dn);
+        if constexpr (MASKED) {
+            live_state_masked((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc, [&](uint32_t d) { return d < n && live_in_mask(ck, pred[d]); }, &en, &tk);
+            dn = live_in_target(ck, pred[v]);
+        } else {
+            live_state((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc, &en, &tk, &dn);
+        }
         comp = scc[v];
     }
     const uint64_t dis = active ? live_disabled(all, en) : 0;
@@ -223,15 +242,67 @@ k_live_reduce(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *
     }
 }
 
+// MASKED: only the components of states in M are judged, by live_violates_masked; dist[v] = 0 at a violating root, LIVE_FAR elsewhere
+template <bool MASKED>
 static __global__ void __launch_bounds__(256)
 k_live_verdict(uint64_t n, const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, const unsigned long long *__restrict__ taken,
-               const unsigned long long *__restrict__ disabled, const unsigned *__restrict__ done, uint64_t all, uint64_t fair, LiveCounters *lc) {
+               const unsigned long long *__restrict__ disabled, const unsigned *__restrict__ done, uint64_t all, uint64_t fair, LiveCounters *lc,
+               const uint32_t *__restrict__ pred, LiveCheck ck, uint32_t *__restrict__ dist) {
     const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool bad = v < n && scc[v] == (uint32_t)v && live_violates(all, fair, taken[v], disabled[v], done[v] != 0, size[v]);
+    const bool root = v < n && scc[v] == (uint32_t)v;
+    const bool bad = root && (MASKED ? live_in_mask(ck, pred[v]) && live_violates_masked(all, fair, taken[v], disabled[v], done[v] != 0, size[v])
+                                     : live_violates(all, fair, taken[v], disabled[v], done[v] != 0, size[v]));
+    if (MASKED && v < n) dist[v] = bad ? 0u : LIVE_FAR;
     const unsigned long long b = __ballot(bad);
     if (b && (int)(threadIdx.x & 63) == __ffsll((long long)b) - 1) {   // (the first bad lane of a wavefront holds its least root)
         atomicAdd(&lc->fair_components, (unsigned long long)__popcll(b));
         atomicMin(&lc->first_root, (unsigned)v);
+    }
+}
+
+// ---- reach (mc_engine_liveness_check): from which states of M is a violating component reached inside M, and how far is it
+struct LiveCheckCounters {
+    unsigned long long mask_states, bad_starts;
+    unsigned witness, pad;   // the least S state with a dist, ~0u = none
+};
+// the other states of the violating components (k_live_verdict<true> marked their roots; a root keeps its value: no lane writes what
+// another reads)
+static __global__ void __launch_bounds__(256)
+k_live_reach_init(uint64_t n, const uint32_t *__restrict__ scc, const uint32_t *__restrict__ pred, LiveCheck ck, uint32_t *dist) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n || !live_passable(ck, pred[v])) return;
+    const uint32_t r = scc[v];
+    if (r != (uint32_t)v && r < n && dist[r] == 0u) dist[v] = 0u;
+}
+// one sweep, in place: a lane may read a dist another lane lowered in the same sweep — values only fall, towards the one fixed point
+static __global__ void __launch_bounds__(256)
+k_live_reach(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const uint32_t *__restrict__ pred, LiveCheck ck,
+             uint32_t *dist, unsigned *flag) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool changed = false;
+    if (v < n && live_passable(ck, pred[v])) {
+        const uint32_t mine = dist[v];
+        if (mine != 0u) {
+            const uint64_t o = offsets[v];
+            const uint32_t best = live_reach_step((uint32_t)v, mine, dst + o, offsets[v + 1] - o, dist,
+                                                  [&](uint32_t d) { return d < n && live_passable(ck, pred[d]); });
+            if (best < mine) { dist[v] = best; changed = true; }
+        }
+    }
+    live_raise(changed, flag);
+}
+static __global__ void __launch_bounds__(256)
+k_live_witness(uint64_t n, const uint32_t *__restrict__ pred, LiveCheck ck, const uint32_t *__restrict__ dist, uint64_t init_states,
+               LiveCheckCounters *cc) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t bits = v < n ? pred[v] : 0u;
+    const bool in_m = v < n && live_in_mask(ck, bits);
+    const bool bad = in_m && dist[v] != LIVE_FAR && live_in_start(ck, bits, v < init_states);
+    const unsigned long long m = __ballot(in_m), b = __ballot(bad);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&cc->mask_states, (unsigned long long)__popcll(m));
+    if (b && (int)(threadIdx.x & 63) == __ffsll((long long)b) - 1) {   // (the first bad lane of a wavefront holds its least state)
+        atomicAdd(&cc->bad_starts, (unsigned long long)__popcll(b));
+        atomicMin(&cc->witness, (unsigned)v);
     }
 }
 

@@ -27,6 +27,7 @@
 #include <fstream>
 #include <sstream>
 #include <string>
+#include <set>
 #include <vector>
 
 #include "../../include/tlamc.h"
@@ -48,6 +49,22 @@ int mc_program_fairness(const mc_program *p, uint64_t *weak_fair_mask, const cha
     if (weak_fair_mask) *weak_fair_mask = p->prog.fair_mask;
     if (refusal) *refusal = p->prog.live_refusal.empty() ? nullptr : p->prog.live_refusal.c_str();
     return p->prog.ninst;
+}
+int mc_program_live_property(const mc_program *p, int index, mc_live_property *out) {
+    if (!p || !out || index < 0 || (size_t)index >= p->prog.live_props.size()) return MC_EBADCFG;
+    const auto &lp = p->prog.live_props[(size_t)index];
+    memset(out, 0, sizeof *out);
+    snprintf(out->origin, sizeof out->origin, "%s", lp.origin.c_str());
+    snprintf(out->name, sizeof out->name, "%s", lp.name.c_str());
+    snprintf(out->reason, sizeof out->reason, "%s", lp.refusal.c_str());
+    out->kind = lp.kind;
+    out->p = lp.p;
+    out->q = lp.q;
+    out->refused = lp.refusal.empty() ? 0 : 1;
+    return MC_OK;
+}
+const char *mc_program_live_predicate(const mc_program *p, int index) {
+    return p && index >= 0 && (size_t)index < p->prog.live_preds.size() ? p->prog.live_preds[(size_t)index].text.c_str() : nullptr;
 }
 extern "C" long pcal_codegen_text(const pcal::Program *p, char *buf, size_t cap);   // pcal_codegen.cpp
 
@@ -641,6 +658,7 @@ int mc_program_compile(const char *tla_text, const char *cfg_text, mc_program **
         cf.invariants = c->invariants;
         cf.constraints = c->constraints;
         properties = c->properties;
+        for (const auto &n : properties) if (n != "Termination" && std::find(cf.properties.begin(), cf.properties.end(), n) == cf.properties.end()) cf.properties.push_back(n);
         for (const auto &k : c->constants) {
             if (k.replacement) { mc_cfg_free(c); return fe_fail(MC_ENOSPEC, "CONSTANT %s <- ...: definition overrides are not supported for PlusCal programs", k.name.c_str()); }
             cf.constants.push_back({k.name, to_const(k.value)});
@@ -1569,14 +1587,51 @@ static int check_files_impl(const char *tla_path, const char *cfg_path, const mc
         mc_program_fairness(prog, &fair, &refusal);
         const bool complete = res->verdict == MC_V_OK && res->queue_left == 0;
         bool checked = false;   // Termination was decided (a cfg that names it twice is checked once)
+        std::set<std::string> seen_names;
+        auto take_trace = [&]() -> int {
+            size_t np = 0, nc = 0;
+            int r = mc_engine_liveness_trace(e, nullptr, &np, nullptr, &nc);   // (MC_EBADCFG with the counts is the answer to no buffers)
+            if (r != MC_EBADCFG || !np) return r ? r : MC_ESTATE;
+            live_prefix.resize(np);
+            live_cycle.resize(nc ? nc : 1);
+            if ((r = mc_engine_liveness_trace(e, live_prefix.data(), &np, live_cycle.data(), &nc))) return r;
+            live_prefix.resize(np);
+            live_cycle.resize(nc);
+            live_violated = true;
+            return MC_OK;
+        };
         for (const auto &name : R.properties) {
+            const bool term = name == "Termination";
+            if (!term && !seen_names.insert(name).second) continue;
+            // the checks a name other than Termination became, or the front end's reason for refusing it
+            std::vector<mc_live_property> checks;
             std::string why;
-            if (name != "Termination") why = "only the translation's Termination is supported";
-            else if (refusal) why = refusal;
-            else if (!complete) why = "the search did not finish (a violation or a budget): liveness needs the complete state graph";
+            if (!term) {
+                mc_live_property lp;
+                for (int k = 0; mc_program_live_property(prog, k, &lp) == MC_OK; k++) {
+                    if (name != lp.origin) continue;
+                    if (lp.refused) why = lp.reason; else checks.push_back(lp);
+                }
+                if (name.size() >= sizeof lp.origin) why = "its name is longer than 63 characters";   // (what mc_live_property.origin holds)
+                if (why.empty() && checks.empty()) why = "it is not a definition of the module this front-end can read";
+            }
+            if (why.empty() && refusal) why = refusal;
+            if (why.empty() && !complete) why = "the search did not finish (a violation or a budget): liveness needs the complete state graph";
             if (!why.empty()) {   // refused: named and counted
                 res->unchecked_properties++;
                 o.put("Warning: temporal property %s NOT checked: %s.\n", name.c_str(), why.c_str());
+                continue;
+            }
+            if (live_violated) continue;   // (the first violated property is the one reported)
+            if (!term) {
+                if (cfg->flags & (MC_F_COVERAGE | MC_F_PROGRESS)) o.put("Checking temporal property %s\n", name.c_str());
+                for (const auto &lp : checks) {
+                    mc_live_check_info ci;
+                    if ((rc = mc_engine_liveness_check(e, fair, &lp, &ci))) { mc_engine_destroy(e); return rc; }
+                    if (!ci.violated) continue;
+                    if ((rc = take_trace())) { mc_engine_destroy(e); return rc; }
+                    break;
+                }
                 continue;
             }
             if (checked) continue;
@@ -1584,15 +1639,7 @@ static int check_files_impl(const char *tla_path, const char *cfg_path, const mc
             mc_live_info li;
             if ((rc = mc_engine_liveness(e, fair, &li))) { mc_engine_destroy(e); return rc; }
             if (!li.violated) continue;
-            size_t np = 0, nc = 0;
-            rc = mc_engine_liveness_trace(e, nullptr, &np, nullptr, &nc);   // (MC_EBADCFG with the counts is the answer to no buffers)
-            if (rc != MC_EBADCFG || !np) { mc_engine_destroy(e); return rc ? rc : MC_ESTATE; }
-            live_prefix.resize(np);
-            live_cycle.resize(nc ? nc : 1);
-            if ((rc = mc_engine_liveness_trace(e, live_prefix.data(), &np, live_cycle.data(), &nc))) { mc_engine_destroy(e); return rc; }
-            live_prefix.resize(np);
-            live_cycle.resize(nc);
-            live_violated = true;
+            if ((rc = take_trace())) { mc_engine_destroy(e); return rc; }
         }
     }
     if (live_violated) {

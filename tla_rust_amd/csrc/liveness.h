@@ -91,4 +91,117 @@ MC_HD bool live_violates(uint64_t all, uint64_t fair, uint64_t taken, uint64_t d
     return size >= 1 && !has_done && live_fair(all, fair, taken, disabled);
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// <>Q, []<>Q, <>[]P and P ~> Q (mc_engine_liveness_check): the same rule over the subgraph G[M] induced by a mask.
+// A check is a triple of state sets, each a function of the state's predicate bits (bit k = predicate k; k_live_pred<S>) and of whether
+// the state is initial:
+//
+//     kind                 M (a violating suffix stays in)   S (it may be entered at)     T (a state of it must recur)
+//     LIVE_LEADS_TO  P~>Q  ~Q                                P /\ ~Q                      all
+//     LIVE_INF_OFTEN []<>Q ~Q                                ~Q                           all
+//     LIVE_EVENTUALLY <>Q  ~Q                                initial states with ~Q       all
+//     LIVE_STABLE    <>[]P all                               all                          ~P
+//
+//   violated  iff  some strongly connected component C of G[M] (one-state components included) is fair, holds a T state and is
+//   reachable along edges of G[M] from an S state that is itself in M.  taken(C) counts edges with both ends in C; en(s, p) — and so
+//   disabled(C) — is taken in the FULL graph: an edge that leaves M still makes its process enabled.  That is live_state over the
+//   component ids of G[M], in which every state outside M is a component of its own: scc[dst] == scc[self] never holds across the mask.
+//
+//   * LivePred<S>: the state predicates of a compiled program, evaluated on a loaded row.
+//   * live_in_mask / live_in_start / live_in_target: the three sets.  live_own_component: which states the component search leaves out.
+//     live_state_masked (then live_merge, as above, with "is a T state" in the Done flag's place) and live_violates_masked: the rule.
+//     live_passable, live_reach_step: the reach pass.
+constexpr int LIVE_LEADS_TO = 0, LIVE_INF_OFTEN = 1, LIVE_EVENTUALLY = 2, LIVE_STABLE = 3;
+constexpr int LIVE_MAX_PREDS = 32;
+constexpr uint32_t LIVE_FAR = 0xffffffffu;   // dist[] of a state from which no violating component is reached inside M
+
+struct LiveCheck { int kind, p, q; };        // p / q: predicate indices, -1 = none
+
+// what the host keeps about the predicates of a compiled program (defined in pcal_compile.cpp, beside vm_format): their number, with
+// entries[k] = where predicate k's code starts in the image (at most cap of them); predicate k's text
+int vm_live_preds(const void *host, int *entries, int cap);
+const char *vm_live_pred_text(const void *host, int k);
+
+// where the predicates' code is: entry[k] is the interpreter's code offset; generated code numbers them after its invariants
+struct LivePredTab { int n; int entry[LIVE_MAX_PREDS]; };
+
+template <class S>
+struct LivePred {
+    static constexpr bool HAS = false;
+    MC_HD static int eval(const typename S::Params &, typename S::Local &, const LivePredTab &, int, int32_t &) { return 0; }
+};
+// eval: 1 = evaluated (res), 0 = an evaluation error inside the predicate
+template <int MAXV>
+struct LivePred<SpecVmT<MAXV>> {
+    static constexpr bool HAS = true;
+    MC_HD static int eval(const VmParams &p, typename SpecVmT<MAXV>::Local &l, const LivePredTab &tab, int k, int32_t &res) {
+        int aux;
+        return SpecVmT<MAXV>::run(p, tab.entry[k], 0, 0, 0, l.v, res, aux) == SpecVmT<MAXV>::R_OK;
+    }
+};
+template <class G>
+struct LivePred<SpecGenT<G>> {
+    static constexpr bool HAS = true;
+    MC_HD static int eval(const VmParams &, typename SpecGenT<G>::Local &l, const LivePredTab &, int k, int32_t &res) {
+        return G::run_inv(G::NINV + G::NCON + k, l.v, res) == SpecGenT<G>::R_OK;
+    }
+};
+
+MC_HD bool live_bit(uint32_t bits, int k) { return k >= 0 && (bits >> k & 1u); }
+MC_HD bool live_in_mask(const LiveCheck &c, uint32_t bits) {
+    return c.kind == LIVE_STABLE || !live_bit(bits, c.q);
+}
+MC_HD bool live_in_start(const LiveCheck &c, uint32_t bits, bool initial) {
+    if (!live_in_mask(c, bits)) return false;   // (the S state itself must be in M)
+    if (c.kind == LIVE_LEADS_TO) return live_bit(bits, c.p);
+    if (c.kind == LIVE_EVENTUALLY) return initial;
+    return true;
+}
+MC_HD bool live_in_target(const LiveCheck &c, uint32_t bits) {
+    return c.kind == LIVE_STABLE ? !live_bit(bits, c.p) : true;
+}
+// the components of G[M]: a state outside M takes no part in the search, it is a component of its own
+MC_HD bool live_own_component(const LiveCheck &c, uint32_t bits) {
+    return !live_in_mask(c, bits);
+}
+// live_state for a state of M: *en from the whole row, *taken from the edges that stay in the state's component of G[M].  in_m(d): is
+// state d in M; scc: the component ids of G[M].
+template <class InM>
+MC_HD void live_state_masked(uint32_t self, const uint32_t *dst, const int8_t *proc, uint64_t n, const uint32_t *scc, InM &&in_m, uint64_t *en, uint64_t *taken) {
+    uint64_t en_ = 0, tk_ = 0;
+    const uint32_t mine = scc[self];
+    for (uint64_t k = 0; k < n; ++k) {
+        const int p = proc[k];
+        if (!live_real_step(p, self, dst[k])) continue;
+        en_ |= 1ull << p;   // (the FULL graph's: an edge that leaves M still makes its process enabled)
+        if (in_m(dst[k]) && scc[dst[k]] == mine) tk_ |= 1ull << p;
+    }
+    *en = en_;
+    *taken = tk_;
+}
+// the component of G[M] with these unions over its states: a weakly fair suffix that stays in M and passes a T state for ever?
+MC_HD bool live_violates_masked(uint64_t all, uint64_t fair, uint64_t taken, uint64_t disabled, bool has_target, uint32_t size) {
+    return size >= 1 && has_target && live_fair(all, fair, taken, disabled);
+}
+// may a path from an S state to a violating component pass this state?  Only inside M.
+MC_HD bool live_passable(const LiveCheck &c, uint32_t bits) {
+    return live_in_mask(c, bits);
+}
+// The reach pass: dist[v] = 0 for the states of the violating components, else 1 + the least dist among the successors inside M
+// (LIVE_FAR: none reaches one).  One update of a passable state `self` from its row; returns the new value (never larger than `mine`).
+// in_m(d): is state d passable.  The fixed point is the length of the shortest path inside M to a violating component: unique, whatever
+// the order of the updates.
+template <class InM>
+MC_HD uint32_t live_reach_step(uint32_t self, uint32_t mine, const uint32_t *dst, uint64_t n, const uint32_t *dist, InM &&in_m) {
+    uint32_t best = mine;
+    for (uint64_t k = 0; k < n; ++k) {
+        const uint32_t d = dst[k];
+        if (d == self || !in_m(d)) continue;
+        const uint32_t dd = dist[d];
+        if (dd != LIVE_FAR && dd + 1 < best) best = dd + 1;
+    }
+    return best;
+}
+
 }  // namespace mc

@@ -467,10 +467,12 @@ int main(int argc, char **argv) {
                 "                [-checkpoint FILE] [-recover FILE] [-gpus P [-torch]]                    check X.tla like `tlc X.tla`\n"
                 "                [-coverage [MINUTES]]                                                    ... and list every action's distinct:generated counts\n"
                 "                a PlusCal X.tla whose X.cfg says PROPERTY Termination: checked under the algorithm's weak fairness (`fair process`,\n"
-                "                `--fair algorithm`) on the complete state graph\n"
+                "                `--fair algorithm`) on the complete state graph; so is a PROPERTY that names a definition of the shape <>A, []<>A,\n"
+                "                <>[]A or A ~> B over state predicates (under \\A over constant sets, and conjunctions of these); any other temporal\n"
+                "                property is named as NOT checked, with the reason\n"
                 "       mc X.tla -simulate [num=N] [-depth D] [-seed S] [...]                             random walks like `tlc -simulate`\n"
                 "       mc --transpile X.tla [Y.tla ...]                                                  translate like `pcal2tla`\n"
-                "exit status: 0 no error, 12 invariant / assertion violated, 11 deadlock, 13 liveness (Termination) violated, 1 anything else\n");
+                "exit status: 0 no error, 12 invariant / assertion violated, 11 deadlock, 13 a temporal property violated, 1 anything else\n");
         return 1;
     }
     if (!simulate && (have_depth || have_seed)) { fprintf(stderr, "mc: %s needs -simulate\n", have_depth ? "-depth" : "-seed"); return 1; }

@@ -988,6 +988,167 @@ size_t find_line_start(const std::string &text, int line) {  // offset of 1-base
 }
 int line_of(const std::string &text, size_t off) { return 1 + (int)std::count(text.begin(), text.begin() + (long)off, '\n'); }
 
+// ------------------------------------------------------------------------------------------ temporal formulas (cfg PROPERTY)
+// The body of a definition that is no expression: one of  <>A, []<>A, <>[]A, A ~> B  (A, B state predicates of the expression subset),
+// optionally parenthesised, under bounded `\A x \in S :`, and conjunctions of these.  The lexer has no token for the temporal operators:
+// `<>`, `[]` and `~>` are two adjacent symbols each.  Anything else leaves the reason in out.refusal.
+struct TemporalParser {
+    const std::vector<Tok> &t;
+    TemporalDef &out;
+    using Quants = std::vector<std::pair<std::string, EP>>;
+    bool sym(size_t i, const char *s) const { return i < t.size() && t[i].t == Tok::SYM && t[i].s == s; }
+    bool pair(size_t i, size_t e, const char *a, const char *b) const {
+        return i + 1 < e && sym(i, a) && sym(i + 1, b) && t[i].line == t[i + 1].line && t[i + 1].col == t[i].col + (int)t[i].s.size();
+    }
+    bool dia(size_t i, size_t e) const { return pair(i, e, "<", ">"); }
+    bool box(size_t i, size_t e) const { return pair(i, e, "[", "]"); }
+    bool leads(size_t i, size_t e) const { return pair(i, e, "~", ">"); }
+    static int nest(const Tok &k) {
+        if (k.t != Tok::SYM) return 0;
+        if (k.s == "(" || k.s == "[" || k.s == "{" || k.s == "<<") return 1;
+        if (k.s == ")" || k.s == "]" || k.s == "}" || k.s == ">>") return -1;
+        return 0;
+    }
+    void refuse(const std::string &why) { if (out.refusal.empty()) out.refusal = why; }
+    std::string text(size_t b, size_t e) const {
+        std::string s;
+        for (size_t i = b; i < e; i++) s += (i > b ? " " : "") + (t[i].t == Tok::STR ? "\"" + t[i].s + "\"" : t[i].s);
+        return s;
+    }
+    // a state predicate: no temporal operator, no fairness formula, no primed variable, and an expression of the subset
+    EP state(size_t b, size_t e) {
+        for (size_t i = b; i < e; i++) {
+            if (dia(i, e) || box(i, e) || leads(i, e)) { refuse("nested temporal operators"); return nullptr; }
+            if (t[i].t == Tok::IDENT && (t[i].s.rfind("WF_", 0) == 0 || t[i].s.rfind("SF_", 0) == 0)) { refuse("a WF_ / SF_ fairness formula inside the property"); return nullptr; }
+            if (sym(i, "'")) { refuse("a primed variable (an action formula)"); return nullptr; }
+        }
+        if (b >= e) { refuse("an operand is missing"); return nullptr; }
+        std::vector<Tok> body(t.begin() + (long)b, t.begin() + (long)e);
+        Tok end;
+        end.line = body.back().line;
+        end.col = body.back().col + 1;
+        body.push_back(end);
+        Parser bp(body);
+        try {
+            EP x = bp.expr(0);
+            if (bp.cur().t == Tok::END) return x;
+        } catch (const ParseError &) {
+        }
+        refuse("a predicate outside the expression subset (`" + text(b, e) + "`)");
+        return nullptr;
+    }
+    // The operand of a temporal PREFIX operator: `<>` binds tighter than every infix operator, so `<>A \/ B` is `(<>A) \/ B` and
+    // `<>x = 1` is `(<>x) = 1`.  What is accepted as "the rest of the body" is therefore one primary only: a parenthesised expression,
+    // or a name / literal with applications (`Done`, `flag[i]`, `Held(i)`, `r.f`), either under `~`.
+    bool primary(size_t b, size_t e) const {
+        while (b < e && (sym(b, "~") || sym(b, "\\lnot") || sym(b, "\\neg"))) ++b;
+        if (b >= e) return false;
+        size_t i = b;
+        if (t[i].t == Tok::IDENT || t[i].t == Tok::NUM || t[i].t == Tok::STR) ++i;
+        else if (!sym(i, "(")) return false;
+        while (i < e) {
+            if (sym(i, ".") && i + 1 < e && t[i + 1].t == Tok::IDENT) { i += 2; continue; }
+            if (!sym(i, "(") && !sym(i, "[")) return false;
+            int d = 0;
+            for (; i < e; i++) { d += nest(t[i]); if (d == 0) break; }
+            if (i >= e) return false;
+            ++i;
+        }
+        return true;
+    }
+    // an operator at nesting depth 0 of [b, e) that binds looser than `~>` (=>, <=>, \equiv): `A => B ~> C` is `A => (B ~> C)`
+    bool looser_than_leads(size_t b, size_t e) const {
+        int d = 0;
+        for (size_t i = b; i < e; i++) {
+            if (d == 0 && (sym(i, "=>") || sym(i, "<=>") || sym(i, "\\equiv"))) return true;
+            d += nest(t[i]);
+        }
+        return false;
+    }
+    void item(int kind, size_t ab, size_t ae, size_t bb, size_t be, const Quants &q) {
+        if (kind == 0 && (looser_than_leads(ab, ae) || looser_than_leads(bb, be)))
+            return refuse("`=>` / `<=>` beside `~>` without parentheses (they bind looser than `~>`: the formula is not of the shape A ~> B)");
+        if (kind != 0) state(kind == 3 ? ab : bb, kind == 3 ? ae : be);   // (a nested temporal operator is named as that)
+        if (!out.refusal.empty()) return;
+        if (kind != 0 && !primary(kind == 3 ? ab : bb, kind == 3 ? ae : be))
+            return refuse("the operand of `<>` / `[]` must be parenthesised (a temporal prefix operator binds tighter than every infix operator: `<>A \\/ B` is `(<>A) \\/ B`)");
+        LiveItem it;
+        it.kind = kind;
+        it.quants = q;
+        if (kind == 0 || kind == 3) { it.a = state(ab, ae); it.a_text = text(ab, ae); }
+        if (kind != 3) { it.b = state(bb, be); it.b_text = text(bb, be); }
+        if (out.refusal.empty()) out.items.push_back(it);
+    }
+    void formula(size_t b, size_t e, Quants q) {
+        if (!out.refusal.empty()) return;
+        if (b >= e) return refuse("an operand is missing");
+        if (sym(b, "(")) {   // ( F )
+            int d = 0;
+            size_t i = b;
+            for (; i < e; i++) { d += nest(t[i]); if (d == 0) break; }
+            if (i == e - 1) return formula(b + 1, e - 1, q);
+        }
+        if (sym(b, "\\E")) return refuse("`\\E` over a temporal formula");
+        if (sym(b, "\\A")) {
+            if (!(b + 2 < e && t[b + 1].t == Tok::IDENT && sym(b + 2, "\\in"))) return refuse("a quantifier that is not `\\A x \\in S :`");
+            int d = 0;
+            size_t colon = b + 3;
+            for (; colon < e; colon++) { if (d == 0 && sym(colon, ":")) break; d += nest(t[colon]); }
+            if (colon >= e) return refuse("a quantifier without `:`");
+            EP dom = state(b + 3, colon);
+            if (!dom) { out.refusal = "a quantifier whose domain is outside the expression subset"; return; }
+            q.push_back({t[b + 1].s, dom});
+            return formula(colon + 1, e, q);
+        }
+        if (sym(b, "/\\")) {   // a bulleted conjunction: the items are what stands between the bullets of the first one's column
+            std::vector<size_t> bullets{b};
+            int d = 0;
+            for (size_t i = b + 1; i < e; i++) {
+                if (d == 0 && sym(i, "/\\") && t[i].col == t[b].col && t[i].line != t[b].line) bullets.push_back(i);
+                if (!box(i, e) && !(i > b && box(i - 1, e))) d += nest(t[i]);
+            }
+            bullets.push_back(e);
+            if (bullets.size() > 2) {
+                for (size_t k = 0; k + 1 < bullets.size(); k++) formula(bullets[k] + 1, bullets[k + 1], q);
+                return;
+            }
+            ++b;
+        }
+        // IF / LET / CASE / CHOOSE and a quantifier inside a larger expression reach as far right as they can: `IF c THEN p ELSE q ~> r` is
+        // IF .. ELSE (q ~> r), `a /\ \A j \in S : p ~> r` is a /\ \A j : (p ~> r), and after `\A i \in S : <>p /\ <>q` both conjuncts are the
+        // quantifier's.  `open`: the first such token at nesting depth 0 (a `\A` / `\E` that STARTS the piece was taken above)
+        std::vector<size_t> arrows, ands;
+        size_t open = e;
+        int d = 0;
+        for (size_t i = b; i < e; i++) {
+            if (d == 0 && open == e && ((t[i].t == Tok::IDENT && (t[i].s == "IF" || t[i].s == "LET" || t[i].s == "CASE" || t[i].s == "CHOOSE")) || sym(i, "\\A") || sym(i, "\\E")))
+                open = i;
+            if (d == 0 && leads(i, e)) arrows.push_back(i);
+            if (d == 0 && (sym(i, "/\\") || sym(i, "\\land"))) ands.push_back(i);
+            if (!box(i, e) && !(i > b && box(i - 1, e))) d += nest(t[i]);   // (`[]` opens nothing)
+        }
+        if (arrows.size() > 1) return refuse("nested temporal operators (more than one `~>`)");
+        if (arrows.size() == 1 && open < arrows[0])
+            return refuse("`" + t[open].s + "` on the left of `~>` without parentheses (its scope reaches as far right as it can: it takes the `~>` in, and the formula is not of the shape A ~> B)");
+        if (arrows.size() == 1) return item(0, b, arrows[0], arrows[0] + 2, e, q);
+        if (!ands.empty() && open < ands.back())
+            return refuse("`" + t[open].s + "` before a `/\\` without parentheses (its scope reaches as far right as it can: the conjuncts after it are its own)");
+        if (!ands.empty()) {
+            ands.push_back(e);
+            size_t from = b;
+            for (size_t at : ands) { formula(from, at, q); from = at + 1; }
+            return;
+        }
+        if (box(b, e) && dia(b + 2, e)) return item(1, 0, 0, b + 4, e, q);
+        if (dia(b, e) && box(b + 2, e)) return item(3, b + 4, e, 0, 0, q);
+        if (dia(b, e)) return item(2, 0, 0, b + 2, e, q);
+        if (box(b, e)) return refuse("`[]` without `<>` is a safety property (`[]A` is an INVARIANT, `[][A]_v` an action formula)");
+        for (size_t i = b; i < e; i++)
+            if (t[i].t == Tok::IDENT && (t[i].s.rfind("WF_", 0) == 0 || t[i].s.rfind("SF_", 0) == 0)) return refuse("a WF_ / SF_ fairness formula inside the property");
+        refuse("not one of <>A, []<>A, <>[]A, A ~> B (under `\\A` over constant sets, and conjunctions of these)");
+    }
+};
+
 }  // namespace
 
 // An algorithm written without any label gets the labels it needs, named Lbl_1, Lbl_2, ... like pcal2tla's (p-manual section 2.3
@@ -2373,10 +2534,20 @@ std::string parse_module(const std::string &text, Module &m) {
                 end.col = d.t[j].col;
                 body.push_back(end);
                 Parser bp(body);
+                bool is_expr = false;
                 try {
                     def.body = bp.expr(0);
-                    if (bp.cur().t == Tok::END) m.defs.push_back(def);  // otherwise: beyond the expression subset, ignored unless used
+                    if (bp.cur().t == Tok::END) { m.defs.push_back(def); is_expr = true; }  // otherwise: beyond the expression subset, ignored unless used
                 } catch (const ParseError &) {
+                }
+                if (!is_expr && params.empty()) {   // ... as a cfg PROPERTY: a temporal formula, classified here and kept
+                    TemporalDef td;
+                    td.name = def.name;
+                    td.line = def.line;
+                    body.pop_back();
+                    TemporalParser{body, td}.formula(0, body.size(), {});
+                    if (!td.refusal.empty()) td.items.clear();
+                    m.temporal.push_back(td);
                 }
                 d.i = j;
             } else {

@@ -99,6 +99,20 @@ struct Definition {
     int line = 0;
     bool in_define = false;   // from the algorithm's `define` block (printed in the translation)
 };
+// A definition of the module that is no state-level expression but a temporal formula: kept so that a cfg PROPERTY
+// that names it can be classified.  items: the conjuncts of an accepted body, each one of the four shapes under its bounded `\A`s.
+struct LiveItem {
+    int kind = 0;                                       // 0 `A ~> B`, 1 `[]<>B`, 2 `<>B`, 3 `<>[]A` (MC_LIVE_* of tlamc.h)
+    std::vector<std::pair<std::string, EP>> quants;     // the `\A x \in S :` around it, outermost first: (x, S)
+    EP a, b;                                            // the state predicates (null where the shape has none)
+    std::string a_text, b_text;                         // their tokens, joined by one blank: what predicates are deduplicated by
+};
+struct TemporalDef {
+    std::string name;
+    int line = 0;
+    std::vector<LiveItem> items;
+    std::string refusal;                                // "" = accepted; else why the body is none of the accepted shapes
+};
 struct Macro {
     std::string name;
     std::vector<std::string> params;
@@ -113,6 +127,7 @@ struct Module {
     std::vector<VarDecl> globals;
     std::vector<Proc> procs;                // a uniprocess algorithm is one Proc with an empty name
     std::vector<Definition> defs;           // definitions of the `define` block and of the module around the algorithm
+    std::vector<TemporalDef> temporal;      // the definitions beyond the expression subset: temporal formulas, accepted or refused
     std::vector<Macro> macros;
     std::vector<Procedure> procedures;      // as written; expand_procedures() has inlined them into the processes' bodies
     bool had_procedures = false;
@@ -173,6 +188,7 @@ struct Config {
     std::vector<std::string> invariants;                       // INVARIANT names, in cfg order
     std::vector<std::string> constraints;                      // CONSTRAINT names
     std::vector<std::pair<std::string, ConstVal>> constants;   // CONSTANT name = value
+    std::vector<std::string> properties;                       // PROPERTY names other than Termination, in cfg order (Program::live_props)
 };
 
 struct VarInfo {
@@ -205,6 +221,13 @@ struct Program {
     // fairness (liveness.h): bit k = process instance k (the slot order: slot / maxch) is weakly fair
     unsigned long long fair_mask = 0;
     std::string live_refusal;             // "" = `Termination` can be checked on the state graph; else why not
+    // the cfg's other temporal properties.  live_preds: the distinct state predicates they are made of, compiled after the
+    // INVARIANTs and CONSTRAINTs into the same image but never run by the search (a table of their own: the entries are not in the header).
+    // live_props: one entry per check — a quantifier instance of a conjunct of a named definition — or per refused name.
+    struct LivePred { std::string text; int entry = 0; };
+    struct LiveProp { std::string origin, name; int kind = -1, p = -1, q = -1; std::string refusal; };
+    std::vector<LivePred> live_preds;
+    std::vector<LiveProp> live_props;
 };
 
 // Returns "" or an error message.

@@ -695,8 +695,15 @@ std::string codegen(const Program &P, bool pack) {
         o << "    MC_HD static int inv" << k << "(Cells &v, int32_t &result) {\n        constexpr int32_t SELF_ = 0; constexpr int INST = 0; const Cells &old = v; int aux = 0; uint64_t ch = 0;\n        (void)SELF_; (void)INST;\n"
           << g.body(c[(size_t)mc::VMH_INV0 + (size_t)k]) << "    }\n";
     }
+    // the predicates of the cfg's temporal properties (Program::live_preds): further entries of the same kind, after the CONSTRAINTs; the
+    // search never asks for them (spec_gen.h inv_status stops at NINV + NCON), k_live_pred does (liveness.h LivePred)
+    const int npred = (int)P.live_preds.size();
+    for (int k = 0; k < npred; ++k) {
+        o << "    MC_HD static int inv" << ninv + ncon + k << "(Cells &v, int32_t &result) {\n        constexpr int32_t SELF_ = 0; constexpr int INST = 0; const Cells &old = v; int aux = 0; uint64_t ch = 0;\n        (void)SELF_; (void)INST;\n"
+          << g.body(P.live_preds[(size_t)k].entry) << "    }\n";
+    }
     o << "    MC_HD static int run_inv(int k, Cells &v, int32_t &result) {\n        switch (k) {\n";
-    for (int k = 0; k < ninv + ncon; ++k) o << "        case " << k << ": return inv" << k << "(v, result);\n";
+    for (int k = 0; k < ninv + ncon + npred; ++k) o << "        case " << k << ": return inv" << k << "(v, result);\n";
     o << "        default: return R_ERROR;\n        }\n    }\n";
     for (int l : used) {
         o << "    template <int INST, int SELF_>\n    MC_HD static int label" << l << "(uint64_t &ch, Cells &v, const Cells &old, int32_t &result, int &aux) {\n"

@@ -1567,6 +1567,119 @@ struct Compiler {
         if (ninit > (1ull << 40)) cfail("too many initial states", d.pos);
     }
 
+    // ---- the cfg's temporal properties other than Termination: every named definition becomes checks over compiled
+    // state predicates, or one refused entry with the reason.  A name is accepted or refused as a whole.
+    std::map<std::string, int> live_pred_of;
+    std::vector<std::pair<std::string, std::string>> live_bound;   // the `\\A` variables around the predicate being compiled: (name, value as written)
+    bool dom_of_strings(const EP &dom) {
+        if (dom->k == Expr::SETENUM) return !dom->a.empty() && dom->a[0]->k == Expr::STR;
+        if (dom->k == Expr::ID) {
+            auto it = consts.find(dom->s);
+            if (it != consts.end()) return it->second.k == ConstVal::SET && !it->second.elems.empty() && it->second.elems[0].k == ConstVal::STR;
+            for (const auto &d : m.defs) if (d.name == dom->s && d.params.empty()) return d.body.get() != dom.get() && dom_of_strings(d.body);
+        }
+        return false;
+    }
+    int live_pred(const EP &e, const std::string &text) {
+        std::string key = text;
+        for (const auto &b : live_bound) {   // the bound variables the text mentions: one predicate per value of those alone
+            bool used = false;
+            for (size_t at = text.find(b.first); at != std::string::npos && !used; at = text.find(b.first, at + 1))
+                used = (at == 0 || text[at - 1] == ' ') && (at + b.first.size() == text.size() || text[at + b.first.size()] == ' ');
+            if (used) key += " | " + b.first + " = " + b.second;
+        }
+        auto it = live_pred_of.find(key);
+        if (it != live_pred_of.end()) return it->second;
+        const int k = (int)P.live_preds.size();
+        Program::LivePred lp;
+        lp.text = key;
+        lp.entry = (int)c.size();
+        next_temp = 0;
+        depth = 0;
+        fallthrough = true;
+        ex(e);
+        emit(mc::VM_HALT);
+        if (max_depth > mc::SpecVm::STACK) cfail("`" + text + "` is too deeply nested for the interpreter's stack");
+        P.live_preds.push_back(lp);
+        live_pred_of[key] = k;
+        return k;
+    }
+    void live_expand(const LiveItem &it, size_t qi, const std::string &base, const std::string &label, std::vector<Program::LiveProp> &got) {
+        if (qi == it.quants.size()) {
+            Program::LiveProp lp;
+            lp.name = base + (label.empty() ? "" : "[" + label + "]");
+            lp.kind = it.kind;
+            lp.p = it.a ? live_pred(it.a, it.a_text) : -1;
+            lp.q = it.b ? live_pred(it.b, it.b_text) : -1;
+            got.push_back(lp);
+            return;
+        }
+        std::vector<long long> elems;
+        const EP &dom = it.quants[qi].second;
+        if (!const_set(dom, elems)) cfail("the domain of `\\A " + it.quants[qi].first + "` is no constant set");
+        const bool str = dom_of_strings(dom);
+        for (long long v : elems) {
+            binds.push_back({it.quants[qi].first, 0, true, v});
+            const std::string val = str && v >= 0 && (size_t)v < P.strings.size() ? "\"" + P.strings[(size_t)v] + "\"" : std::to_string(v);
+            live_bound.push_back({it.quants[qi].first, val});
+            live_expand(it, qi + 1, base, label + (label.empty() ? "" : ", ") + it.quants[qi].first + " = " + val, got);
+            live_bound.pop_back();
+            binds.pop_back();
+        }
+    }
+    void live_properties() {
+        size_t checks = 0;
+        for (const auto &name : cfg.properties) {
+            Program::LiveProp refused;
+            refused.origin = refused.name = name;
+            const TemporalDef *td = nullptr;
+            for (const auto &d : m.temporal) if (d.name == name) td = &d;
+            if (name.size() > 63) {
+                refused.refusal = "its name is longer than 63 characters";
+            } else if (!td) {
+                bool is_def = false;
+                for (const auto &d : m.defs) is_def |= d.name == name;
+                refused.refusal = is_def ? "it is a state-level formula, not one of <>A, []<>A, <>[]A, A ~> B" : "it is not a definition of the module this front-end can read";
+            } else if (!td->refusal.empty()) {
+                refused.refusal = td->refusal;
+            }
+            if (!refused.refusal.empty()) { P.live_props.push_back(refused); continue; }
+            std::vector<Program::LiveProp> got;
+            const size_t code0 = c.size(), preds0 = P.live_preds.size(), binds0 = binds.size();
+            const auto pred_of0 = live_pred_of;
+            const auto str_id0 = str_id;
+            const size_t strings0 = P.strings.size();
+            const int depth0 = max_depth;
+            std::string why;
+            try {
+                for (size_t k = 0; k < td->items.size(); k++)
+                    live_expand(td->items[k], 0, td->items.size() > 1 ? name + "." + std::to_string(k + 1) : name, "", got);
+            } catch (const CompileError &e) {
+                why = "a predicate outside the expression subset: " + e.msg;
+            }
+            if (why.empty() && got.empty()) why = "it expands to no check (a quantifier over an empty set: vacuously true)";
+            if (why.empty() && checks + got.size() > 16) why = "more than 16 checks per cfg";
+            if (why.empty() && P.live_preds.size() > 32) why = "more than 32 distinct predicates per cfg";
+            if (!why.empty()) {   // as if the name had never been compiled
+                c.resize(code0);
+                P.live_preds.resize(preds0);
+                binds.resize(binds0);
+                live_bound.clear();
+                live_pred_of = pred_of0;
+                str_id = str_id0;              // (a string literal only the refused predicates mention is no string of the program)
+                P.strings.resize(strings0);
+                max_depth = depth0;
+                depth = 0;
+                fallthrough = true;
+                refused.refusal = why;
+                P.live_props.push_back(refused);
+                continue;
+            }
+            checks += got.size();
+            for (auto &g : got) { g.origin = name; P.live_props.push_back(g); }
+        }
+    }
+
     void run() {
         P.module = m.name;
         P.multi = !(m.procs.size() == 1 && m.procs[0].name.empty());
@@ -1815,6 +1928,8 @@ struct Compiler {
                 emit(mc::VM_HALT);
                 if (pass == 0) P.invariants.push_back(name);
             }
+        // ---- the predicates of the cfg's other temporal properties: code after the invariants', entries in a table of the program's own
+        live_properties();
         // ---- header
         c[mc::VMH_MAGIC] = mc::VM_MAGIC;
         c[mc::VMH_NV] = nv;
@@ -1965,6 +2080,17 @@ int vm_format(const void *host, const int32_t *vals, char *buf, size_t cap) {
     const size_t n = s.size() < cap ? s.size() : (cap ? cap - 1 : 0);
     if (cap) { memcpy(buf, s.data(), n); buf[n] = 0; }
     return (int)n;
+}
+
+// the predicates of the program's temporal properties: their number; entries[k] = where predicate k's code starts (at most cap of them)
+int vm_live_preds(const void *host, int *entries, int cap) {
+    const pcal::Program &P = *(const pcal::Program *)host;
+    for (int k = 0; entries && k < cap && (size_t)k < P.live_preds.size(); k++) entries[k] = P.live_preds[(size_t)k].entry;
+    return (int)P.live_preds.size();
+}
+const char *vm_live_pred_text(const void *host, int k) {
+    const pcal::Program &P = *(const pcal::Program *)host;
+    return k >= 0 && (size_t)k < P.live_preds.size() ? P.live_preds[(size_t)k].text.c_str() : "?";
 }
 
 // action id = label id of the instance that moves; nlabels = the terminating disjunct

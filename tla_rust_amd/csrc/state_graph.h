@@ -8,6 +8,7 @@
 
 #include <chrono>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -53,9 +54,21 @@ struct StateGraph {
         mc_scc_info sinfo{};
         mc_live_info linfo{};
         uint64_t fair = 0;
+        // what mc_engine_predicates / mc_engine_liveness_check add
+        bool pred_built = false, proc_built = false;
+        DevBuf<uint32_t> pred;      // [states] bit k = predicate k of the program's temporal properties holds in the state
+        DevBuf<uint32_t> dist;      // [states] the reach pass of the last check
+        struct Masked { int q; DevBuf<uint32_t> scc, size; };   // the components of the subgraph induced by ~predicate q: one build per mask
+        std::vector<std::unique_ptr<Masked>> masks;
+        // the last check, for the counterexample: -1 = Termination (mc_engine_liveness), else the kind of a property check
+        int last_kind = -1, last_p = -1, last_q = -1;
+        const Masked *last_mask = nullptr;     // its components (null: the full graph's)
+        std::vector<uint32_t> descent;         // from the witness along falling dist to the first state of the component
         void release() {
-            scc_built = checked = false;
+            scc_built = checked = pred_built = proc_built = false;
             toff.reset(); tsrc.reset(); scc.reset(); size.reset(); proc.reset(); taken.reset(); disabled.reset(); done.reset();
+            pred.reset(); dist.reset(); masks.clear(); descent.clear();
+            last_kind = -1; last_mask = nullptr;
         }
     } lv;
     void release() { built = false; offsets.reset(); dst.reset(); act.reset(); lv.release(); }
@@ -69,10 +82,19 @@ struct StateGraph {
     // over `all` process instances, `fair` of them weakly fair.  started: when the call began (mc_live_info.seconds).
     int live_check(uint64_t all, uint64_t fair, hipStream_t stream, std::chrono::steady_clock::time_point started, mc_live_info *out);
     // mc_engine_liveness_trace; level_start: the search's level table (arena index of each BFS level's first state)
+    // mc_engine_predicates once the engine's k_live_pred<S> has filled lv.pred
+    int pred_read(uint64_t first, uint64_t count, uint32_t *bits_out);
+    // mc_engine_liveness_check once the components, lv.proc and lv.pred are there: kind / p / q as in mc_live_property (validated by
+    // the caller against the program's predicates)
+    int live_check_masked(uint64_t all, uint64_t fair, int kind, int p, int q, hipStream_t stream, std::chrono::steady_clock::time_point started,
+                          mc_live_check_info *out);
+    int live_scc_read(uint64_t first, uint64_t count, uint32_t *scc_out);   // mc_engine_liveness_components
     int live_trace(const std::vector<uint64_t> &level_start, uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout);
 
 private:
     int scc_build(uint64_t n, hipStream_t stream);
+    // trim + colouring over the transpose that is there; mask: the predicate whose states are left out (a component of their own each), -1 = none
+    int scc_components(uint64_t n, hipStream_t stream, int mask_q, DevBuf<uint32_t> &scc_buf, DevBuf<uint32_t> &size_buf, mc_scc_info &info);
 };
 
 }  // namespace mc

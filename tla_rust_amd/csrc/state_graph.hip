@@ -46,9 +46,11 @@ static void live_launch(hipStream_t stream, K kernel, uint64_t n, A... args) {
     if (n) hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, args...);
 }
 // SCC_BATCH sweeps, then one read of the flag; until a whole batch changed nothing.  `rounds` counts the sweeps launched.
+// max_rounds: a fixed point that needs more sweeps than that "did not converge" (MC_ESTATE); 0 = no bound
 template <class F>
-static int live_fixed_point(hipStream_t stream, unsigned *flag, uint32_t &rounds, F &&sweep) {
+static int live_fixed_point(hipStream_t stream, unsigned *flag, uint32_t &rounds, F &&sweep, uint64_t max_rounds = 0, const char *what = "") {
     for (;;) {
+        if (max_rounds && rounds > max_rounds) { set_error(std::string(what) + " did not converge after " + std::to_string(rounds) + " sweeps"); return MC_ESTATE; }
         HIP_TRY(hipMemsetAsync(flag, 0, sizeof(unsigned), stream));
         for (int k = 0; k < SCC_BATCH; ++k) sweep();
         rounds += SCC_BATCH;
@@ -72,16 +74,10 @@ int StateGraph::scc(hipStream_t stream, mc_scc_info *out) {
 }
 int StateGraph::scc_build(uint64_t n, hipStream_t stream) {
     DevBuf<uint32_t> indeg;   // build-time only: the in-degrees, then the fill's cursors
-    DevBuf<unsigned> flag;
-    DevBuf<LiveCounters> d_lc;
     DevBuf<char> scan_tmp;
     int rc;
     if ((rc = graph_alloc(indeg, n + 1, "the in-degrees", "mc_engine_scc"))) return rc;
     if ((rc = graph_alloc(lv.toff, n + 1, "the transpose's row offsets", "mc_engine_scc"))) return rc;
-    if ((rc = graph_alloc(lv.scc, n, "the component ids", "mc_engine_scc"))) return rc;
-    if ((rc = graph_alloc(lv.size, n, "the colours", "mc_engine_scc"))) return rc;
-    if ((rc = graph_alloc(flag, 1, "the fixed-point flag", "mc_engine_scc"))) return rc;
-    if ((rc = graph_alloc(d_lc, 1, "the counters", "mc_engine_scc"))) return rc;
     const uint64_t *off = offsets.p;
     const uint32_t *dst = this->dst.p;
     // ---- transpose
@@ -96,11 +92,24 @@ int StateGraph::scc_build(uint64_t n, hipStream_t stream) {
     HIP_TRY(hipMemsetAsync(indeg, 0, (n + 1) * sizeof(uint32_t), stream));
     live_launch(stream, k_live_tfill, n, off, dst, (const uint64_t *)lv.toff.p, indeg.p, lv.tsrc.p);
     HIP_TRY(hipGetLastError());
+    return scc_components(n, stream, -1, lv.scc, lv.size, lv.sinfo);
+}
+int StateGraph::scc_components(uint64_t n, hipStream_t stream, int mask_q, DevBuf<uint32_t> &scc_buf, DevBuf<uint32_t> &size_buf, mc_scc_info &info) {
+    DevBuf<unsigned> flag;
+    DevBuf<LiveCounters> d_lc;
+    int rc;
+    if ((rc = graph_alloc(scc_buf, n, "the component ids", "mc_engine_scc"))) return rc;
+    if ((rc = graph_alloc(size_buf, n, "the colours", "mc_engine_scc"))) return rc;
+    if ((rc = graph_alloc(flag, 1, "the fixed-point flag", "mc_engine_scc"))) return rc;
+    if ((rc = graph_alloc(d_lc, 1, "the counters", "mc_engine_scc"))) return rc;
+    const uint64_t *off = offsets.p;
+    const uint32_t *dst = this->dst.p;
     // ---- trim and colouring until no state is live
     const uint64_t *toff = lv.toff.p;
     const uint32_t *tsrc = lv.tsrc.p;
-    uint32_t *scc = lv.scc.p, *colour = lv.size.p;
+    uint32_t *scc = scc_buf.p, *colour = size_buf.p;
     HIP_TRY(hipMemsetAsync(scc, 0xff, n * sizeof(uint32_t), stream));
+    if (mask_q >= 0) live_launch(stream, k_scc_mask, n, (const uint32_t *)lv.pred.p, LiveCheck{LIVE_INF_OFTEN, -1, mask_q}, scc);
     uint32_t trim_rounds = 0, colour_rounds = 0, back_rounds = 0, passes = 0;
     for (; n;) {
         if ((rc = live_fixed_point(stream, flag.p, trim_rounds, [&] { live_launch(stream, k_scc_trim, n, off, dst, toff, tsrc, scc, flag.p); }))) return rc;
@@ -129,15 +138,15 @@ int StateGraph::scc_build(uint64_t n, hipStream_t stream) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&lc, d_lc, sizeof lc, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    memset(&lv.sinfo, 0, sizeof lv.sinfo);
-    lv.sinfo.states = n;
-    lv.sinfo.components = lc.components;
-    lv.sinfo.nontrivial = lc.nontrivial;
-    lv.sinfo.largest = lc.largest;
-    lv.sinfo.trim_rounds = trim_rounds;
-    lv.sinfo.colour_rounds = colour_rounds;
-    lv.sinfo.backward_rounds = back_rounds;
-    lv.sinfo.passes = passes;
+    memset(&info, 0, sizeof info);
+    info.states = n;
+    info.components = lc.components;
+    info.nontrivial = lc.nontrivial;
+    info.largest = lc.largest;
+    info.trim_rounds = trim_rounds;
+    info.colour_rounds = colour_rounds;
+    info.backward_rounds = back_rounds;
+    info.passes = passes;
     return MC_OK;
 }
 int StateGraph::scc_read(uint64_t first, uint64_t count, uint32_t *scc_out) {
@@ -163,10 +172,11 @@ int StateGraph::live_check(uint64_t all, uint64_t fair, hipStream_t stream, std:
     HIP_TRY(hipMemsetAsync(lv.taken, 0, (n ? n : 1) * sizeof(unsigned long long), stream));
     HIP_TRY(hipMemsetAsync(lv.disabled, 0, (n ? n : 1) * sizeof(unsigned long long), stream));
     HIP_TRY(hipMemsetAsync(lv.done, 0, (n ? n : 1) * sizeof(unsigned), stream));
-    live_launch(stream, k_live_reduce, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, (const int8_t *)lv.proc.p, (const uint32_t *)lv.scc.p,
-                (const uint32_t *)lv.size.p, all, lv.taken.p, lv.disabled.p, lv.done.p);
-    live_launch(stream, k_live_verdict, n, (const uint32_t *)lv.scc.p, (const uint32_t *)lv.size.p, (const unsigned long long *)lv.taken.p,
-                (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p, all, fair, d_lc.p);
+    live_launch(stream, k_live_reduce<false>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, (const int8_t *)lv.proc.p, (const uint32_t *)lv.scc.p,
+                (const uint32_t *)lv.size.p, all, lv.taken.p, lv.disabled.p, lv.done.p, (const uint32_t *)nullptr, LiveCheck{});
+    live_launch(stream, k_live_verdict<false>, n, (const uint32_t *)lv.scc.p, (const uint32_t *)lv.size.p, (const unsigned long long *)lv.taken.p,
+                (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p, all, fair, d_lc.p, (const uint32_t *)nullptr, LiveCheck{},
+                (uint32_t *)nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&lc, d_lc, sizeof lc, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -182,11 +192,139 @@ int StateGraph::live_check(uint64_t all, uint64_t fair, hipStream_t stream, std:
     lv.linfo.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count();
     lv.fair = fair;
     lv.checked = true;
+    lv.last_kind = -1;
+    lv.last_mask = nullptr;
+    lv.descent.clear();
     *out = lv.linfo;
     return MC_OK;
 }
+int StateGraph::live_scc_read(uint64_t first, uint64_t count, uint32_t *scc_out) {
+    if (!built || !lv.checked || lv.last_kind < 0) { set_error("mc_engine_liveness_components: no property check (mc_engine_liveness_check runs one; the next search releases it)"); return MC_ESTATE; }
+    if (first > info.states || count > info.states - first) { set_error("mc_engine_liveness_components: range beyond the graph's states"); return MC_EBADCFG; }
+    HIP_TRY(hipSetDevice(device));
+    if (count) HIP_TRY(hipMemcpy(scc_out, (lv.last_mask ? lv.last_mask->scc.p : lv.scc.p) + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+int StateGraph::pred_read(uint64_t first, uint64_t count, uint32_t *bits_out) {
+    if (!built || !lv.pred_built) { set_error("mc_engine_predicates: no predicate bits"); return MC_ESTATE; }
+    if (first > info.states || count > info.states - first) { set_error("mc_engine_predicates: range beyond the graph's states"); return MC_EBADCFG; }
+    HIP_TRY(hipSetDevice(device));
+    if (count) HIP_TRY(hipMemcpy(bits_out, lv.pred.p + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+// One (M, S, T) check over lv.pred: the components of G[M] (kept per mask), the rule per component, the reach pass, the witness; then,
+// on the host and only when violated, the way from the witness into a component (lv.descent), which fixes the component reported.
+int StateGraph::live_check_masked(uint64_t all, uint64_t fair, int kind, int p, int q, hipStream_t stream, std::chrono::steady_clock::time_point started,
+                                  mc_live_check_info *out) {
+    const uint64_t n = info.states;
+    const LiveCheck ck{kind, p, q};
+    const char *call = "mc_engine_liveness_check";
+    int rc;
+    uint32_t builds = 0;
+    lv.checked = false;
+    // ---- the components of G[M]: the full graph's for <>[]P, else one build per predicate that masks
+    const Live::Masked *mask = nullptr;
+    if (kind != LIVE_STABLE) {
+        for (const auto &m : lv.masks) if (m->q == q) mask = m.get();
+        if (!mask) {
+            auto m = std::make_unique<Live::Masked>();
+            m->q = q;
+            mc_scc_info si;
+            if ((rc = scc_components(n, stream, q, m->scc, m->size, si))) return rc;
+            ++builds;
+            mask = m.get();
+            lv.masks.push_back(std::move(m));
+        }
+    }
+    const uint32_t *scc = mask ? mask->scc.p : lv.scc.p, *size = mask ? mask->size.p : lv.size.p, *pred = lv.pred.p;
+    DevBuf<LiveCounters> d_lc;
+    DevBuf<LiveCheckCounters> d_cc;
+    DevBuf<unsigned> flag;
+    if ((rc = graph_alloc(lv.taken, n, "the components' taken masks", call))) return rc;
+    if ((rc = graph_alloc(lv.disabled, n, "the components' disabled masks", call))) return rc;
+    if ((rc = graph_alloc(lv.done, n, "the components' target flags", call))) return rc;
+    if ((rc = graph_alloc(lv.dist, n, "the distances", call))) return rc;
+    if ((rc = graph_alloc(d_lc, 1, "the counters", call))) return rc;
+    if ((rc = graph_alloc(d_cc, 1, "the counters", call))) return rc;
+    if ((rc = graph_alloc(flag, 1, "the fixed-point flag", call))) return rc;
+    LiveCounters lc;
+    memset(&lc, 0, sizeof lc);
+    lc.first_root = ~0u;
+    LiveCheckCounters cc;
+    memset(&cc, 0, sizeof cc);
+    cc.witness = ~0u;
+    HIP_TRY(hipMemcpyAsync(d_lc, &lc, sizeof lc, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_cc, &cc, sizeof cc, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(lv.taken, 0, (n ? n : 1) * sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(lv.disabled, 0, (n ? n : 1) * sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(lv.done, 0, (n ? n : 1) * sizeof(unsigned), stream));
+    live_launch(stream, k_live_reduce<true>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, (const int8_t *)lv.proc.p, scc, size, all, lv.taken.p,
+                lv.disabled.p, lv.done.p, pred, ck);
+    live_launch(stream, k_live_verdict<true>, n, scc, size, (const unsigned long long *)lv.taken.p, (const unsigned long long *)lv.disabled.p,
+                (const unsigned *)lv.done.p, all, fair, d_lc.p, pred, ck, lv.dist.p);
+    live_launch(stream, k_live_reach_init, n, scc, pred, ck, lv.dist.p);
+    HIP_TRY(hipGetLastError());
+    uint32_t sweeps = 0;
+    if (n && (rc = live_fixed_point(stream, flag.p, sweeps, [&] { live_launch(stream, k_live_reach, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, pred, ck, lv.dist.p, flag.p); },
+                                    n + SCC_BATCH, "mc_engine_liveness_check: the reach pass")))
+        return rc;
+    live_launch(stream, k_live_witness, n, pred, ck, (const uint32_t *)lv.dist.p, (uint64_t)info.init_states, d_cc.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&lc, d_lc, sizeof lc, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&cc, d_cc, sizeof cc, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    memset(out, 0, sizeof *out);
+    out->violated = cc.bad_starts ? 1 : 0;
+    out->sweeps = sweeps;
+    out->fair_components = lc.fair_components;
+    out->mask_states = cc.mask_states;
+    out->bad_starts = cc.bad_starts;
+    out->scc_builds = builds;
+    lv.descent.clear();
+    if (out->violated) {
+        // from the witness along strictly falling dist inside M, the least such successor each time
+        std::vector<uint64_t> off((size_t)n + 1);
+        std::vector<uint32_t> d((size_t)info.edges), dist((size_t)n);
+        HIP_TRY(hipMemcpy(off.data(), offsets.p, off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(dist.data(), lv.dist.p, dist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (info.edges) HIP_TRY(hipMemcpy(d.data(), dst.p, d.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        uint32_t cur = cc.witness;
+        lv.descent.push_back(cur);
+        while (dist[cur] != 0) {
+            uint32_t best = ~0u;
+            for (uint64_t k = off[cur]; k < off[cur + 1]; ++k) {
+                const uint32_t t = d[(size_t)k];
+                if (t < n && t != cur && dist[t] != LIVE_FAR && dist[t] + 1 == dist[cur] && t < best) best = t;   // (a dist at all: the state is in M)
+            }
+            if (best == ~0u) { set_error("mc_engine_liveness_check: state " + std::to_string(cur) + " has a distance and no successor one step nearer"); return MC_ESTATE; }
+            lv.descent.push_back(best);
+            cur = best;
+        }
+        uint32_t root = 0, sz = 0;
+        HIP_TRY(hipMemcpy(&root, scc + cur, sizeof root, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&sz, size + root, sizeof sz, hipMemcpyDeviceToHost));
+        out->witness = cc.witness;
+        out->root = root;
+        out->root_size = sz;
+    }
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count();
+    memset(&lv.linfo, 0, sizeof lv.linfo);
+    lv.linfo.violated = out->violated;
+    lv.linfo.fair_components = out->fair_components;
+    lv.linfo.root = out->root;
+    lv.linfo.root_size = out->root_size;
+    lv.linfo.seconds = out->seconds;
+    lv.fair = fair;
+    lv.last_kind = kind;
+    lv.last_p = p;
+    lv.last_q = q;
+    lv.last_mask = mask;
+    lv.checked = true;
+    return MC_OK;
+}
 // The counterexample of the last mc_engine_liveness, built on the host from the arrays (deterministic given them).
-// prefix: from an initial state to the chosen component's id (its least state), one BFS level back per step along the transpose: the
+// prefix: from an initial state to the chosen component's id (its least state) — after a property check: to the witness, and on along
+// lv.descent to the first state of the component —, one BFS level back per step along the transpose: the
 // least source in the previous level (level boundaries: level_start).  cycle: a closed walk inside the component that starts at
 // that state and, for every weakly fair process, takes a real step of it or passes a state where it is disabled; the last entry has an
 // edge back to the first.  Empty = the behaviour stutters in the prefix's last state for ever.
@@ -196,10 +334,12 @@ int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *p
     HIP_TRY(hipSetDevice(device));
     const uint64_t n = info.states, edges = info.edges;
     const uint32_t root = (uint32_t)lv.linfo.root;
+    const bool prop = lv.last_kind >= 0 && !lv.descent.empty();
+    const uint32_t target = prop ? lv.descent.front() : root;   // where the way back to an initial state starts
     // ---- prefix
-    std::vector<uint32_t> prefix{root};
+    std::vector<uint32_t> prefix{target};
     auto level_of = [&](uint32_t x) { return (size_t)(std::upper_bound(level_start.begin(), level_start.end(), (uint64_t)x) - level_start.begin()) - 1; };
-    for (uint32_t cur = root; level_of(cur) > 0;) {
+    for (uint32_t cur = target; level_of(cur) > 0;) {
         const size_t L = level_of(cur);
         uint64_t row[2];
         HIP_TRY(hipMemcpy(row, lv.toff.p + cur, sizeof row, hipMemcpyDeviceToHost));
@@ -212,12 +352,14 @@ int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *p
         cur = best;
     }
     std::reverse(prefix.begin(), prefix.end());
+    if (prop) prefix.insert(prefix.end(), lv.descent.begin() + 1, lv.descent.end());
+    const uint32_t entry = prefix.back();   // where the behaviour enters the component: the cycle starts and ends here
     // ---- cycle
     std::vector<uint64_t> off((size_t)n + 1);
     std::vector<uint32_t> dst((size_t)edges), scc((size_t)n);
     std::vector<int8_t> proc((size_t)edges);
     HIP_TRY(hipMemcpy(off.data(), offsets.p, off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(scc.data(), lv.scc.p, scc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(scc.data(), prop && lv.last_mask ? lv.last_mask->scc.p : lv.scc.p, scc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (edges) {
         HIP_TRY(hipMemcpy(dst.data(), this->dst.p, dst.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(proc.data(), lv.proc.p, proc.size() * sizeof(int8_t), hipMemcpyDeviceToHost));
@@ -225,7 +367,7 @@ int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *p
     std::vector<uint32_t> members;
     for (uint64_t v = 0; v < n; ++v) if (scc[(size_t)v] == root) members.push_back((uint32_t)v);
     std::vector<uint32_t> par((size_t)n, ~0u);
-    std::vector<uint32_t> cycle{root};   // the walk so far; its last entry is where it stands
+    std::vector<uint32_t> cycle{entry};   // the walk so far; its last entry is where it stands
     // breadth-first inside the component, rows in index order; appends the states after `from` up to `to`
     auto go = [&](uint32_t to) {
         const uint32_t from = cycle.back();
@@ -266,9 +408,18 @@ int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *p
         }
         if (!found) ok = false;
     }
-    if (ok) ok = go(root);
+    if (ok && prop && lv.last_kind == LIVE_STABLE) {   // <>[]P: the walk passes a ~P state, the component's least
+        std::vector<uint32_t> bits((size_t)n);
+        HIP_TRY(hipMemcpy(bits.data(), lv.pred.p, bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        const LiveCheck ck{lv.last_kind, lv.last_p, lv.last_q};
+        bool found = false;
+        for (size_t mi = 0; mi < members.size() && !found; ++mi)
+            if (live_in_target(ck, bits[members[mi]])) { found = true; ok = go(members[mi]); }
+        if (!found) ok = false;
+    }
+    if (ok) ok = go(entry);
     if (!ok) { set_error("mc_engine_liveness_trace: the chosen component is not fair or not connected (the arrays disagree with the verdict)"); return MC_ESTATE; }
-    cycle.pop_back();   // (the walk ended on `root` again: the closing edge is implied; a walk that never moved leaves nothing)
+    cycle.pop_back();   // (the walk ended on `entry` again: the closing edge is implied; a walk that never moved leaves nothing)
     if (prefix.size() > *nprefix_inout || cycle.size() > *ncycle_inout || !prefix_out || (!cycle.empty() && !cycle_out)) {
         *nprefix_inout = prefix.size();
         *ncycle_inout = cycle.size();
