@@ -127,6 +127,9 @@ extern "C" {
     // null; returns the number of instances) and the cfg's PROPERTY names (null past the last)
     pub fn mc_program_fairness(p: *const mc_program, weak_fair_mask: *mut u64, refusal: *mut *const c_char) -> c_int;
     pub fn mc_program_property(p: *const mc_program, index: c_int) -> *const c_char;
+    // the cfg's VIEW (the text of its definition, null without one) and ACTION_CONSTRAINT names (null past the last)
+    pub fn mc_program_view(p: *const mc_program) -> *const c_char;
+    pub fn mc_program_action_constraint(p: *const mc_program, index: c_int) -> *const c_char;
     pub fn mc_program_free(p: *mut mc_program);
     pub fn mc_state_bytes(spec: *const mc_spec_desc) -> usize;
     pub fn mc_state_format(spec: *const mc_spec_desc, state: *const u8, buf: *mut c_char, cap: usize) -> c_int;

@@ -692,6 +692,11 @@ const char *mc_program_property(const mc_program *p, int index);
  * mc_program_live_predicate: the text of predicate number index (with the quantifier values it was compiled for), NULL past the last */
 int mc_program_live_property(const mc_program *p, int index, mc_live_property *out);
 const char *mc_program_live_predicate(const mc_program *p, int index);
+/* the cfg's VIEW and ACTION_CONSTRAINTs as the program honours them: the text of the view's definition ("<<x, pc>>"), NULL without a VIEW;
+ * the name of action constraint number index (cfg order), NULL past the last.  With a view the fingerprint of a state is that of its view
+ * values; which state represents a view value is the one that arrived first — reproducible exactly when equal views imply equal futures. */
+const char *mc_program_view(const mc_program *p);
+const char *mc_program_action_constraint(const mc_program *p, int index);
 void mc_program_free(mc_program *p);
 
 /* ------------------------------------------------------------------ helpers (host only) */

@@ -1,0 +1,33 @@
+------------------------------ MODULE refuse_primed_seq ------------------------------
+(* Refused, by a message that names the form: a primed sequence compared with a tuple that is no constant. *)
+EXTENDS Naturals, Sequences, TLC
+
+(* --algorithm refuse_primed_seq
+variables q = <<>>, msgs = {}, r = [cnt |-> 0, flag |-> FALSE];
+
+process P \in 1..2
+variable c = 0;
+begin
+  s: while c < 2 do
+       either
+         q := Append(q, self);
+       or
+         await Len(q) > 0;
+         q := Tail(q);
+       or
+         msgs := msgs \cup {[type |-> "m", from |-> self]};
+       or
+         msgs := msgs \ {[type |-> "m", from |-> self]};
+       or
+         r := [cnt |-> r.cnt + 1, flag |-> TRUE];
+       or
+         r := [cnt |-> 0, flag |-> r.flag];
+       end either;
+       c := c + 1;
+     end while;
+end process
+
+end algorithm *)
+
+Bad == q' # <<r.cnt>>
+=============================================================================

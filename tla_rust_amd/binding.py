@@ -269,6 +269,10 @@ def lib():
         L.mc_engine_predicates.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         L.mc_engine_liveness_components.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         L.mc_engine_liveness_check.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(LiveProperty), C.POINTER(LiveCheckInfo)]
+        L.mc_program_view.argtypes = [C.c_void_p]
+        L.mc_program_view.restype = C.c_char_p
+        L.mc_program_action_constraint.argtypes = [C.c_void_p, C.c_int]
+        L.mc_program_action_constraint.restype = C.c_char_p
         L.mc_program_property.argtypes = [C.c_void_p, C.c_int]
         L.mc_program_property.restype = C.c_char_p
         L.mc_program_free.argtypes = [C.c_void_p]
@@ -775,6 +779,12 @@ class Program:
                                                refused=bool(lp.refused), reason=lp.reason.decode() or None))
         while lib().mc_program_live_predicate(h, len(self.live_predicates)):
             self.live_predicates.append(lib().mc_program_live_predicate(h, len(self.live_predicates)).decode())
+        # the cfg's VIEW (the text of its definition, None without one) and ACTION_CONSTRAINT names, as the program honours them
+        v = lib().mc_program_view(h)
+        self.view = v.decode() if v else None
+        self.action_constraints = []
+        while lib().mc_program_action_constraint(h, len(self.action_constraints)):
+            self.action_constraints.append(lib().mc_program_action_constraint(h, len(self.action_constraints)).decode())
 
     def translated(self):
         return lib().mc_program_translated(self._h).decode()

@@ -95,6 +95,8 @@ struct CovAction<SpecVmT<MAXV>> {
         return slot < 0 ? -1 : l.v[p.pc_base + slot / p.maxch];
     }
 };
+template <int MAXV>
+struct CovAction<SpecVmCfgT<MAXV>> : CovAction<SpecVmT<MAXV>> {};   // (spec_vm_cfg.h: the same rows and slots)
 // ... as generated code: the pc cell from the stored (possibly packed) row
 template <class G>
 struct CovAction<SpecGenT<G>> {

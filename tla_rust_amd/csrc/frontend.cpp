@@ -66,6 +66,10 @@ int mc_program_live_property(const mc_program *p, int index, mc_live_property *o
 const char *mc_program_live_predicate(const mc_program *p, int index) {
     return p && index >= 0 && (size_t)index < p->prog.live_preds.size() ? p->prog.live_preds[(size_t)index].text.c_str() : nullptr;
 }
+const char *mc_program_view(const mc_program *p) { return p && !p->prog.view_text.empty() ? p->prog.view_text.c_str() : nullptr; }
+const char *mc_program_action_constraint(const mc_program *p, int index) {
+    return p && index >= 0 && (size_t)index < p->prog.action_constraints.size() ? p->prog.action_constraints[(size_t)index].c_str() : nullptr;
+}
 extern "C" long pcal_codegen_text(const pcal::Program *p, char *buf, size_t cap);   // pcal_codegen.cpp
 
 namespace {
@@ -143,6 +147,8 @@ struct Lexer {
                 std::string tail(p + 1, q);
                 if (tail == "CONSTRAINT" || tail == "CONSTRAINTS") { t.s += "-" + tail; p = q; }
             }
+            // (TLC's own spelling, ACTION_CONSTRAINT(S) — ModelConfig.java — is the same statement)
+            if (t.s == "ACTION_CONSTRAINT" || t.s == "ACTION_CONSTRAINTS") t.s[6] = '-';
             bool letter = false;
             for (char ch : t.s) letter |= !(ch >= '0' && ch <= '9');
             t.t = letter ? Tok::IDENT : Tok::NUMBER;
@@ -663,9 +669,11 @@ int mc_program_compile(const char *tla_text, const char *cfg_text, mc_program **
             if (k.replacement) { mc_cfg_free(c); return fe_fail(MC_ENOSPEC, "CONSTANT %s <- ...: definition overrides are not supported for PlusCal programs", k.name.c_str()); }
             cf.constants.push_back({k.name, to_const(k.value)});
         }
-        const bool other = !c->action_constraints.empty() || !c->symmetry.empty() || !c->view.empty();
+        cf.action_constraints = c->action_constraints;
+        cf.view = c->view;
+        const bool other = !c->symmetry.empty();
         mc_cfg_free(c);
-        if (other) return fe_fail(MC_ENOSPEC, "ACTION-CONSTRAINT / SYMMETRY / VIEW are not supported for PlusCal programs");
+        if (other) return fe_fail(MC_ENOSPEC, "SYMMETRY is not supported for PlusCal programs");
     }
     const std::string text(tla_text);
     pcal::Module m;

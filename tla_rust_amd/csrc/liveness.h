@@ -33,6 +33,9 @@ struct LiveProc<SpecVmT<MAXV>> {
     MC_HD static int count(const VmParams &p) { return p.ninst; }
     MC_HD static int of(const VmParams &p, int slot) { return slot >= p.ninst * p.maxch ? LIVE_TERM : slot / p.maxch; }
 };
+template <int MAXV> struct SpecVmCfgT;   // (spec_vm_cfg.h: the interpreter with the cfg's ACTION_CONSTRAINTs / VIEW — the same slots and processes)
+template <int MAXV>
+struct LiveProc<SpecVmCfgT<MAXV>> : LiveProc<SpecVmT<MAXV>> {};
 template <class G>
 struct LiveProc<SpecGenT<G>> {
     static constexpr bool HAS = true;
@@ -140,6 +143,8 @@ struct LivePred<SpecVmT<MAXV>> {
         return SpecVmT<MAXV>::run(p, tab.entry[k], 0, 0, 0, l.v, res, aux) == SpecVmT<MAXV>::R_OK;
     }
 };
+template <int MAXV>
+struct LivePred<SpecVmCfgT<MAXV>> : LivePred<SpecVmT<MAXV>> {};
 template <class G>
 struct LivePred<SpecGenT<G>> {
     static constexpr bool HAS = true;

@@ -470,6 +470,11 @@ int main(int argc, char **argv) {
                 "                `--fair algorithm`) on the complete state graph; so is a PROPERTY that names a definition of the shape <>A, []<>A,\n"
                 "                <>[]A or A ~> B over state predicates (under \\A over constant sets, and conjunctions of these); any other temporal\n"
                 "                property is named as NOT checked, with the reason\n"
+                "                a PlusCal X.tla whose X.cfg says ACTION_CONSTRAINT A: a step that violates A is generated and its successor checked,\n"
+                "                but not stored; VIEW V (a tuple of variables and scalar expressions): a state is fingerprinted by its view, the\n"
+                "                first state to arrive stands for its view value.  As with TLC: unless equal views imply equal futures, WHICH state\n"
+                "                that is depends on the order of arrival within a level, and the counts may differ from run to run; a temporal\n"
+                "                property under a VIEW is named as NOT checked\n"
                 "       mc X.tla -simulate [num=N] [-depth D] [-seed S] [...]                             random walks like `tlc -simulate`\n"
                 "       mc --transpile X.tla [Y.tla ...]                                                  translate like `pcal2tla`\n"
                 "exit status: 0 no error, 12 invariant / assertion violated, 11 deadlock, 13 a temporal property violated, 1 anything else\n");

@@ -318,6 +318,15 @@ struct Parser {
                 body->paren = true;
                 return body;
             }
+            if (k.s == "UNCHANGED") {  // UNCHANGED v / UNCHANGED <<v, w>> (an ACTION_CONSTRAINT): kept as the operator UNCHANGED(v, w)
+                i++;
+                auto e = mk(Expr::CALL, k);
+                e->s = "UNCHANGED";
+                EP what = postfix();
+                if (what->k == Expr::TUPLE) e->a = what->a;
+                else e->a.push_back(what);
+                return e;
+            }
             if (k.s == "CHOOSE") {  // bounded CHOOSE x \in S : P (examples/p-manual.pdf section 2.4: the definition of gcd)
                 i++;
                 auto e = mk(Expr::QUANT, k);
@@ -336,6 +345,13 @@ struct Parser {
                 e->s = k.s;
                 if (!is_sym(")")) for (;;) { e->a.push_back(expr(0)); if (is_sym(",")) { i++; continue; } break; }
                 expect_sym(")");
+                if ((e->s == "Len" || e->s == "Head" || e->s == "Cardinality") && e->a.size() == 1 && e->a[0]->k == Expr::PRIME) {
+                    // Len(q'): kept as (Len(q))' — a PRIME node says "the VARIABLE at the root of my operand is the successor's" (see postfix)
+                    auto x = mk(Expr::PRIME, k);
+                    e->a[0] = e->a[0]->a[0];
+                    x->a = {e};
+                    return x;
+                }
                 return e;
             }
             auto e = mk(Expr::ID, k);
@@ -442,16 +458,20 @@ struct Parser {
                 const Tok at = cur();
                 i++;
                 auto x = mk(Expr::INDEX, at);
-                x->a = {e, expr(0)};
+                const bool primed = e->k == Expr::PRIME;   // f'[i]: kept as PRIME(f[i]) — the prime is the root variable's, the index is read as written
+                x->a = {primed ? e->a[0] : e, expr(0)};
                 expect_sym("]");
-                e = x;
+                if (primed) { auto pr = mk(Expr::PRIME, at); pr->a = {x}; e = pr; }
+                else e = x;
             } else if (is_sym(".") && peek().t == Tok::IDENT) {  // r.f
                 const Tok at = cur();
                 i++;
                 auto x = mk(Expr::DOT, at);
                 x->s = t[i++].s;
-                x->a = {e};
-                e = x;
+                const bool primed = e->k == Expr::PRIME;   // r'.f: PRIME(r.f)
+                x->a = {primed ? e->a[0] : e};
+                if (primed) { auto pr = mk(Expr::PRIME, at); pr->a = {x}; e = pr; }
+                else e = x;
             } else if (is_sym("'")) {
                 const Tok at = cur();
                 i++;
@@ -1966,8 +1986,62 @@ struct RecordFlattener {
         c->a[(size_t)(1 - side)] = t;
         return c;
     }
+    // <<r, pc>> / UNCHANGED <<r, x>> with a record variable r of this pass: r stands for the variables of its fields (the next pass
+    // expands a field that is a record itself)
+    EP expand_records(const EP &e) const {
+        auto c = std::make_shared<Expr>(*e);
+        c->a.clear();
+        for (const auto &x : e->a) {
+            if (x->k == Expr::ID && recs.count(x->s) && !bound_shape(x)) for (const auto &f : recs.at(x->s).fields) c->a.push_back(id(x->s + "_" + f, x->pos));
+            else c->a.push_back(rw(x));
+        }
+        return c;
+    }
+    static EP primed(const EP &e) { auto p = node(Expr::PRIME, e->pos); p->a = {e}; return p; }
     EP rw(const EP &e) const {
         if (!e) return e;
+        if (e->k == Expr::CALL && e->s == "UNCHANGED") return expand_records(e);
+        if (e->k == Expr::QUANT && e->a[0]->k == Expr::PRIME && e->a[0]->a[0]->k == Expr::ID && rsets.count(e->a[0]->a[0]->s))
+            fail(e->pos, "a quantifier over the primed set of records `" + e->a[0]->a[0]->s + "'` is not supported (supported on a primed set of records: r \\in " +
+                             e->a[0]->a[0]->s + "', " + e->a[0]->a[0]->s + "' = {}, Cardinality(" + e->a[0]->a[0]->s + "'))");
+        if (e->k == Expr::BINOP && (e->s == "\\in" || e->s == "\\notin") && e->a[1]->k == Expr::PRIME && e->a[1]->a[0]->k == Expr::ID && rsets.count(e->a[1]->a[0]->s)) {
+            auto c = std::make_shared<Expr>(*e);   // r \in msgs': the element in the set's own field order, the prime kept
+            c->a[0] = rset_elem(e->a[0], rsets.at(e->a[1]->a[0]->s), e->a[1]->a[0]->s);
+            return c;
+        }
+        if (e->k == Expr::BINOP && (e->s == "=" || e->s == "#") && (e->a[0]->k == Expr::PRIME || e->a[1]->k == Expr::PRIME)) {
+            // r' = r, r' = [f |-> e, ...] (an ACTION_CONSTRAINT): field by field, the prime on the field's variable
+            const bool p0 = e->a[0]->k == Expr::PRIME, p1 = e->a[1]->k == Expr::PRIME;
+            const EP x0 = p0 ? e->a[0]->a[0] : e->a[0], x1 = p1 ? e->a[1]->a[0] : e->a[1];
+            if (x0->k == Expr::ID && x1->k == Expr::ID && x0->s == x1->s && rsets.count(x0->s) && !bound_shape(x0)) return e;   // msgs' = msgs: cell by cell (pcal_compile.cpp)
+            if ((x0->k == Expr::ID && rsets.count(x0->s) && p0 && x1->k == Expr::SETENUM && x1->a.empty()) ||
+                (x1->k == Expr::ID && rsets.count(x1->s) && p1 && x0->k == Expr::SETENUM && x0->a.empty())) return e;   // msgs' = {}
+            if (record_valued(x0) || record_valued(x1)) {
+                if (!record_valued(x0) || !record_valued(x1)) fail(e->pos, "a record can only be compared with a record variable, an element of a record array or a record constructor");
+                const auto fs = fields_of(x0);
+                if (!same_fields(fs, fields_of(x1))) fail(e->pos, "comparison of records with different fields");
+                EP acc;
+                for (const auto &f : fs) {
+                    const EP f0 = field_of(x0, f), f1 = field_of(x1, f);
+                    if ((p0 && record_valued(f0)) || (p1 && record_valued(f1))) fail(e->pos, "a primed record whose field `" + f + "` is a record itself cannot be compared as a whole: compare its fields");
+                    auto eq = node(Expr::BINOP, e->pos);
+                    eq->s = "=";
+                    eq->a = {p0 ? primed(f0) : f0, p1 ? primed(f1) : f1};
+                    if (!acc) { acc = eq; continue; }
+                    auto both = node(Expr::BINOP, e->pos);
+                    both->s = "/\\";
+                    both->a = {acc, eq};
+                    acc = both;
+                }
+                acc->paren = true;
+                if (e->s == "=") return acc;
+                auto no = node(Expr::UNOP, e->pos);
+                no->s = "~";
+                no->a = {acc};
+                no->paren = true;
+                return no;
+            }
+        }
         switch (e->k) {
         case Expr::DOT: {
             EP b = e->a[0];
@@ -2390,9 +2464,16 @@ struct RecordFlattener {
             }
             for (auto &d : m.defs) {
                 try {
-                    d.body = rw(d.body);
-                } catch (const FlattenError &) {
+                    // a definition that IS a tuple of variables, or one variable (a cfg VIEW): a record variable in it stands for its fields' variables
+                    if (d.params.empty() && d.body->k == Expr::ID && recs.count(d.body->s) && !bound_shape(d.body)) {
+                        auto t = node(Expr::TUPLE, d.body->pos);
+                        t->a = {d.body};
+                        d.body = t;
+                    }
+                    d.body = d.params.empty() && d.body->k == Expr::TUPLE ? expand_records(d.body) : rw(d.body);
+                } catch (const FlattenError &e) {
                     if (d.in_define) throw;
+                    m.dropped_defs.push_back({d.name, e.msg});
                     d.body = nullptr;  // a definition of the module text beyond the subset: unusable as an invariant, like an unparsed one
                 }
             }
@@ -2600,7 +2681,14 @@ std::string pe_inner(const EP &e, const Ctx &c, const std::set<std::string> &pri
         return l + " " + e->s + " " + r;
     }
     case Expr::INDEX: return pe(e->a[0], c, primed, shadow) + "[" + pe(e->a[1], c, primed, shadow) + "]";
-    case Expr::PRIME: return pe(e->a[0], c, primed, shadow) + "'";
+    case Expr::PRIME: {   // the prime belongs to the root variable of the operand (the parser keeps f'[i] as PRIME(f[i])): printed where it was written
+        const EP &x = e->a[0];
+        auto pr = [&](const EP &y) { auto p2 = std::make_shared<Expr>(*e); p2->a = {y}; return pe(p2, c, primed, shadow); };
+        if (x->k == Expr::INDEX) return pr(x->a[0]) + "[" + pe(x->a[1], c, primed, shadow) + "]";
+        if (x->k == Expr::DOT) return pr(x->a[0]) + "." + x->s;
+        if (x->k == Expr::CALL && x->a.size() == 1) return x->s + "(" + pr(x->a[0]) + ")";
+        return pe(x, c, primed, shadow) + "'";
+    }
     case Expr::CALL: {
         std::string r = e->s + "(";
         for (size_t i = 0; i < e->a.size(); i++) r += (i ? ", " : "") + pe(e->a[i], c, primed, shadow);

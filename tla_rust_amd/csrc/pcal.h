@@ -127,6 +127,8 @@ struct Module {
     std::vector<VarDecl> globals;
     std::vector<Proc> procs;                // a uniprocess algorithm is one Proc with an empty name
     std::vector<Definition> defs;           // definitions of the `define` block and of the module around the algorithm
+    std::vector<std::pair<std::string, std::string>> dropped_defs;   // definitions of the module text beyond the record subset: (name, why), for the
+                                            // message of a cfg statement that names one (VIEW, ACTION_CONSTRAINT)
     std::vector<TemporalDef> temporal;      // the definitions beyond the expression subset: temporal formulas, accepted or refused
     std::vector<Macro> macros;
     std::vector<Procedure> procedures;      // as written; expand_procedures() has inlined them into the processes' bodies
@@ -189,6 +191,8 @@ struct Config {
     std::vector<std::string> constraints;                      // CONSTRAINT names
     std::vector<std::pair<std::string, ConstVal>> constants;   // CONSTANT name = value
     std::vector<std::string> properties;                       // PROPERTY names other than Termination, in cfg order (Program::live_props)
+    std::vector<std::string> action_constraints;               // ACTION_CONSTRAINT names, in cfg order
+    std::string view;                                          // VIEW name, or ""
 };
 
 struct VarInfo {
@@ -228,6 +232,12 @@ struct Program {
     struct LiveProp { std::string origin, name; int kind = -1, p = -1, q = -1; std::string refusal; };
     std::vector<LivePred> live_preds;
     std::vector<LiveProp> live_props;
+    // the cfg's ACTION_CONSTRAINTs and VIEW: code after the live predicates', entries in tables of the program's own
+    std::vector<std::string> action_constraints;   // the names, in cfg order
+    std::vector<int> acon_entry;                   // one entry per name
+    struct ViewComp { int a = 0, n = 0; std::string text; };   // n > 0: the cells a .. a + n - 1 of a variable; n == 0: the code at a (one value)
+    std::vector<ViewComp> view;
+    std::string view_text;                         // the body of the definition the cfg's VIEW names ("<<c1, ..., ck>>"), or ""
 };
 
 // Returns "" or an error message.

@@ -705,6 +705,39 @@ std::string codegen(const Program &P, bool pack) {
     o << "    MC_HD static int run_inv(int k, Cells &v, int32_t &result) {\n        switch (k) {\n";
     for (int k = 0; k < ninv + ncon + npred; ++k) o << "        case " << k << ": return inv" << k << "(v, result);\n";
     o << "        default: return R_ERROR;\n        }\n    }\n";
+ // ---- the cfg's ACTION_CONSTRAINTs and VIEW: emitted only for a program that has them — the header of any other
+    // program is the text it was before they existed
+    if (!P.acon_entry.empty()) {
+        const int nacon = (int)P.acon_entry.size();
+        for (int k = 0; k < nacon; ++k) {
+            // (the interpreter's convention, spec_vm_cfg.h: the code reads unprimed variables from v — here the state being expanded — and primed ones from `old`)
+            o << "    MC_HD static int acon" << k << "(const Cells &v, const Cells &old, int32_t &result) {\n        constexpr int32_t SELF_ = 0; constexpr int INST = 0; int aux = 0; uint64_t ch = 0;\n        (void)SELF_; (void)INST;\n"
+              << g.body(P.acon_entry[(size_t)k]) << "    }\n";
+        }
+        o << "    static constexpr int NACON = " << nacon << ";\n    // action constraint k on the transition cur -> succ\n    MC_HD static int run_acon(int k, const Cells &cur, const Cells &succ, int32_t &result) {\n        switch (k) {\n";
+        for (int k = 0; k < nacon; ++k) o << "        case " << k << ": return acon" << k << "(cur, succ, result);\n";
+        o << "        default: return R_ERROR;\n        }\n    }\n";
+    }
+    if (!P.view.empty()) {
+        int nvals = 0, ne = 0;
+        std::ostringstream fill;
+        auto put = [&](const std::string &val) {
+            fill << "        w[" << nvals / 2 << "] " << (nvals % 2 ? "|= (uint64_t)(uint32_t)(" + val + ") << 32" : "= (uint64_t)(uint32_t)(" + val + ")") << ";\n";
+            nvals++;
+        };
+        for (const auto &vc : P.view) {
+            if (vc.n > 0) { for (int i = 0; i < vc.n; ++i) put("v.c" + std::to_string(vc.a + i)); continue; }
+            o << "    MC_HD static int viewe" << ne << "(Cells &v, int32_t &result) {\n        constexpr int32_t SELF_ = 0; constexpr int INST = 0; const Cells &old = v; int aux = 0; uint64_t ch = 0;\n        (void)SELF_; (void)INST;\n"
+              << g.body(vc.a) << "    }\n";
+            fill << "        { int32_t r_ = 0; if (viewe" << ne << "(v, r_) != R_OK) { ok = false; r_ = " << mc::VM_DEFAULT_INIT << "; }\n    ";
+            put("r_");
+            fill << "        }\n";
+            ne++;
+        }
+        o << "    // cfg VIEW " << P.view_text << ": the values a state is fingerprinted by, two per word; false = an evaluation error inside a component\n"
+          << "    static constexpr int VIEW = " << nvals << ", VIEW_WORDS = " << (nvals + 1) / 2 << ";\n    MC_HD static bool view_words(Cells &v, uint64_t *w) {\n        bool ok = true;\n"
+          << fill.str() << "        return ok;\n    }\n";
+    }
     for (int l : used) {
         o << "    template <int INST, int SELF_>\n    MC_HD static int label" << l << "(uint64_t &ch, Cells &v, const Cells &old, int32_t &result, int &aux) {\n"
           << g.body(c[(size_t)(label_tab + l)]) << "    }\n";

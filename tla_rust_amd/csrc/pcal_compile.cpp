@@ -5,6 +5,7 @@
 // disjunct (p.63) is the engine's last slot.  INVARIANTs are the zero-argument definitions the cfg names.
 #include "pcal.h"
 #include "spec_vm.h"
+#include "spec_vm_cfg.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -605,6 +606,7 @@ struct Compiler {
         const EP e = resolve_domain(e0);
         if (e->k == Expr::SETOF) return true;
         if (set_var(e)) return true;
+        if (e->k == Expr::PRIME && set_var(e->a[0])) return true;
         if (e->k == Expr::BINOP && (e->s == "\\cup" || e->s == "\\union" || e->s == "\\cap" || e->s == "\\intersect" || e->s == "\\"))
             return dynamic_set(e->a[0]) || dynamic_set(e->a[1]);
         if (e->k == Expr::SETENUM) { for (const auto &x : e->a) { long long v; if (!const_scalar(x, v)) return true; } }
@@ -613,6 +615,7 @@ struct Compiler {
     // leave the 32-bit mask of a set expression on the stack
     void ex_set(const EP &e0) {
         const EP e = resolve_domain(e0);
+        if (e->k == Expr::PRIME && set_var(e->a[0])) { primed(e, [&](const EP &x) { ex_set(x); }); return; }
         if (e->k == Expr::SETOF) {   // {x \\in S : P}: the members of S for which P holds; {f : x \\in S}: the values f takes (all within 0..31)
             const bool filter = e->s == "filter";
             const EP dom = resolve_domain(e->a[0]);
@@ -714,6 +717,166 @@ struct Compiler {
         for (auto &x : c->a) x = subst_ids(x, m);
         return c;
     }
+    // ---- primed variables (cfg ACTION_CONSTRAINT).  The parser keeps f'[i], r'.f, Len(q') as PRIME(f[i]), PRIME(r.f),
+    // PRIME(Len(q)): the prime belongs to the variable at the root of the operand.  The indices on the way are evaluated first, as written
+    // (into temporaries); then the access itself runs between VM_OLD_ON / VM_OLD_OFF.  The code of an action constraint is run with v = the
+    // state being expanded and `old` = the successor (spec_vm_cfg.h), and its body is emitted at "old" depth 0 — definitions are inlined
+    // WITHOUT the VM_OLD_ON they get elsewhere — so exactly the primed accesses read the successor
+    bool in_acon = false;
+    static std::string expr_text(const EP &e) {
+        if (!e) return "?";
+        switch (e->k) {
+        case Expr::NUM: return std::to_string(e->num);
+        case Expr::BOOL: return e->num ? "TRUE" : "FALSE";
+        case Expr::STR: return "\"" + e->s + "\"";
+        case Expr::ID: return e->s;
+        case Expr::PRIME: return expr_text(e->a[0]) + "'";
+        case Expr::INDEX: return expr_text(e->a[0]) + "[" + expr_text(e->a[1]) + "]";
+        case Expr::DOT: return expr_text(e->a[0]) + "." + e->s;
+        case Expr::UNOP: return e->s + " " + expr_text(e->a[0]);
+        case Expr::BINOP: return "(" + expr_text(e->a[0]) + " " + e->s + " " + expr_text(e->a[1]) + ")";
+        case Expr::TUPLE: case Expr::SETENUM: case Expr::CALL: {
+            std::string r = e->k == Expr::TUPLE ? "<<" : e->k == Expr::SETENUM ? "{" : e->s + "(";
+            for (size_t k = 0; k < e->a.size(); k++) r += (k ? ", " : "") + expr_text(e->a[k]);
+            return r + (e->k == Expr::TUPLE ? ">>" : e->k == Expr::SETENUM ? "}" : ")");
+        }
+        default: return "(...)";
+        }
+    }
+    bool is_variable(const EP &e) {
+        if (e->k != Expr::ID) return false;
+        for (const auto &b : binds) if (b.name == e->s) return false;
+        return var_index.count(e->s) != 0;
+    }
+    template <class F>
+    void primed(const EP &e, F &&emit_access) {
+        if (!in_acon) cfail("a primed variable (`" + expr_text(e) + "`) outside an ACTION_CONSTRAINT", e->pos);
+        const int temp0 = next_temp;
+        const size_t binds0 = binds.size();
+        // rebuild the access path with every index that reads anything replaced by a temporary
+        std::function<EP(const EP &)> path = [&](const EP &x) -> EP {
+            if (x->k == Expr::ID) {
+                if (!is_variable(x)) cfail("a prime (') on `" + expr_text(x) + "`, which is no variable: only variable names can be primed", e->pos);
+                return x;
+            }
+            if (x->k == Expr::CALL && x->a.size() == 1 && (x->s == "Len" || x->s == "Head" || x->s == "Cardinality")) {
+                auto c2 = std::make_shared<Expr>(*x);
+                c2->a[0] = path(x->a[0]);
+                return c2;
+            }
+            if (x->k == Expr::INDEX) {
+                auto c2 = std::make_shared<Expr>(*x);
+                c2->a[0] = path(x->a[0]);
+                long long cv;
+                if (!const_scalar(x->a[1], cv)) {
+                    const int t = new_temp(e->pos);
+                    ex(x->a[1]);
+                    emit(mc::VM_STORET, t);
+                    const std::string nm = "\001p" + std::to_string(t);
+                    binds.push_back({nm, t, false, 0});
+                    auto idn = std::make_shared<Expr>();
+                    idn->k = Expr::ID; idn->s = nm; idn->pos = x->pos;
+                    c2->a[1] = idn;
+                }
+                return c2;
+            }
+            cfail("a prime (') on `" + expr_text(x) + "`: only variable names can be primed (x', f'[i], r'.f, Len(q'))", e->pos);
+        };
+        const EP access = path(e->a[0]);
+        emit(mc::VM_OLD_ON);
+        try {
+            emit_access(access);
+        } catch (CompileError &ce) {   // (the message speaks of the variable: say that it is the primed one)
+            ce.msg = "in the primed `" + expr_text(e) + "`: " + ce.msg + "; supported primed forms: x', f'[i], r'.f, Len(q'), Head(q'), q'[i], q' = <<constants>>, v' = v / v' # v of one variable, "
+                     "S' in set expressions, Cardinality(S'), r \\in msgs', msgs' = {}, UNCHANGED";
+            throw;
+        }
+        emit(mc::VM_OLD_OFF);
+        binds.resize(binds0);
+        next_temp = temp0;
+    }
+    int cells_of(size_t k) const { return (k + 1 < P.vars.size() ? P.vars[k + 1].base : cur_nv) - P.vars[k].base; }
+    int cur_nv = 0;
+    // UNCHANGED v / UNCHANGED <<v, w>>: every cell of every named variable is the same in both states
+    void unchanged(const EP &e) {
+        if (!in_acon) cfail("UNCHANGED outside an ACTION_CONSTRAINT", e->pos);
+        emit(mc::VM_PUSH, 1);
+        for (const auto &x : e->a) {
+            if (!is_variable(x)) cfail("UNCHANGED `" + expr_text(x) + "`: only variable names (and tuples of them) are supported", e->pos);
+            const size_t k = (size_t)var_index[x->s];
+            for (int i = 0; i < cells_of(k); i++) {
+                emit(mc::VM_LOAD, P.vars[k].base + i);
+                emit(mc::VM_OLD_ON); emit(mc::VM_LOAD, P.vars[k].base + i); emit(mc::VM_OLD_OFF);
+                emit(mc::VM_EQ); emit(mc::VM_AND);
+            }
+        }
+    }
+    std::string why_dropped(const std::string &name) const {   // the definition exists but uses records beyond the subset: say what
+        for (const auto &d : m.dropped_defs) if (d.first == name) return ": " + d.second;
+        return "";
+    }
+    bool bool_typed(const EP &e, int nest = 0) {
+        if (e->k == Expr::ID && nest < 16 && !is_variable(e))
+            for (const auto &d : m.defs) if (d.name == e->s && d.params.empty()) return bool_typed(d.body, nest + 1);
+        if (e->k == Expr::CALL && e->s == "UNCHANGED") return true;
+        if (e->k == Expr::PRIME) return type_of(e->a[0]) == 'b';
+        if (e->k == Expr::IF) return bool_typed(e->a[1], nest + 1);
+        return type_of(e) == 'b';
+    }
+    // the cfg's ACTION_CONSTRAINTs and VIEW: code after everything else's, entries in tables of the program's own (no header word, no byte of
+    // a program without them changes)
+    void cfg_more() {
+        if (cfg.action_constraints.size() > (size_t)mc::VM_MAX_ACON) cfail("at most " + std::to_string(mc::VM_MAX_ACON) + " ACTION_CONSTRAINTs are supported");
+        for (const auto &name : cfg.action_constraints) {
+            const Definition *def = nullptr;
+            for (const auto &d : m.defs) if (d.name == name && d.params.empty()) def = &d;
+            if (!def) cfail("ACTION_CONSTRAINT " + name + " is not a definition of the module this front-end can read" + why_dropped(name));
+            if (!bool_typed(def->body)) cfail("ACTION_CONSTRAINT " + name + " is not a Boolean-valued formula");
+            P.action_constraints.push_back(name);
+            P.acon_entry.push_back((int)c.size());
+            next_temp = 0; depth = 0; fallthrough = true;
+            in_acon = true;
+            ex(def->body);   // (depth 0: unprimed variables are read from v = the state being expanded)
+            emit(mc::VM_HALT);
+            in_acon = false;
+        }
+        if (!cfg.view.empty()) {
+            const Definition *def = nullptr;
+            for (const auto &d : m.defs) if (d.name == cfg.view && d.params.empty()) def = &d;
+            if (!def) cfail("VIEW " + cfg.view + " is not a definition of the module this front-end can read" + why_dropped(cfg.view));
+            std::vector<EP> comps;
+            if (def->body->k == Expr::TUPLE) comps = def->body->a; else comps.push_back(def->body);
+            if (comps.empty()) cfail("VIEW " + cfg.view + " is the empty tuple");
+            if (comps.size() > (size_t)mc::VM_MAX_VIEW) cfail("VIEW " + cfg.view + ": at most " + std::to_string(mc::VM_MAX_VIEW) + " components are supported");
+            int nexpr = 0;
+            P.view_text = expr_text(def->body);
+            for (const auto &x : comps) {
+                Program::ViewComp vc;
+                vc.text = expr_text(x);
+                if (is_variable(x)) {
+                    const size_t k = (size_t)var_index[x->s];
+                    vc.a = P.vars[k].base;
+                    vc.n = cells_of(k);
+                } else {
+                    if (x->k == Expr::TUPLE || x->k == Expr::SETENUM || x->k == Expr::SETOF || x->k == Expr::FUNCDEF || x->k == Expr::RECORD)
+                        cfail("VIEW " + cfg.view + ": the component `" + vc.text + "` is neither a variable nor a scalar expression");
+                    if (++nexpr > 8) cfail("VIEW " + cfg.view + ": at most 8 components that are expressions are supported");
+                    vc.a = (int)c.size();
+                    vc.n = 0;
+                    next_temp = 0; depth = 0; fallthrough = true;
+                    try {
+                        ex(x);
+                    } catch (const CompileError &ce) {
+                        cfail("VIEW " + cfg.view + ": the component `" + vc.text + "` is outside the expression subset: " + ce.msg);
+                    }
+                    emit(mc::VM_HALT);
+                }
+                P.view.push_back(vc);
+            }
+        }
+        if (max_depth > mc::SpecVm::STACK) cfail("an ACTION_CONSTRAINT or VIEW expression is too deeply nested for the interpreter's stack");
+    }
+
     // ---- expressions: leave one value on the stack
     void ex(const EP &e) {
         switch (e->k) {
@@ -758,9 +921,9 @@ struct Compiler {
                     binds.clear();
                     const Proc *sp = proc;
                     proc = nullptr;
-                    emit(mc::VM_OLD_ON);   // a defined operator speaks about the unprimed variables
+                    if (!in_acon) emit(mc::VM_OLD_ON);   // a defined operator speaks about the unprimed variables (an action constraint's: already read)
                     ex(d.body);
-                    emit(mc::VM_OLD_OFF);
+                    if (!in_acon) emit(mc::VM_OLD_OFF);
                     proc = sp;
                     binds = saved;
                     inline_depth--;
@@ -768,7 +931,9 @@ struct Compiler {
                 }
             cfail("unknown identifier `" + e->s + "`", e->pos);
         }
+        case Expr::PRIME: primed(e, [&](const EP &x) { ex(x); }); return;
         case Expr::CALL: {  // an operator of the define block / of the module, inlined: arguments evaluated once
+            if (e->s == "UNCHANGED") { unchanged(e); return; }
             if (e->s == "Cardinality" && e->a.size() == 1) {
                 if (const VarInfo *rs = rset_var(e->a[0])) { emit(mc::VM_LOAD, rs->base); return; }
                 ex_set(e->a[0]); emit(mc::VM_POPCNT); return;
@@ -823,9 +988,9 @@ struct Compiler {
             binds = inner;
             const Proc *sp = proc;
             proc = nullptr;
-            emit(mc::VM_OLD_ON);   // the arguments were evaluated in the caller's context; the body reads unprimed variables
+            if (!in_acon) emit(mc::VM_OLD_ON);   // the arguments were evaluated in the caller's context; the body reads unprimed variables
             ex(whole.empty() ? def->body : subst_ids(def->body, whole));
-            emit(mc::VM_OLD_OFF);
+            if (!in_acon) emit(mc::VM_OLD_OFF);
             proc = sp;
             binds = saved;
             next_temp = temp0;
@@ -866,8 +1031,55 @@ struct Compiler {
         default: cfail("this kind of expression is only supported as a constant set / initial value", e->pos);
         }
     }
+    // the forms of an ACTION_CONSTRAINT that prime a WHOLE sequence / set of records / function; false: none of them
+    bool primed_whole(const EP &e) {
+        const std::string &o = e->s;
+        if (e->a.size() != 2 || (e->a[0]->k != Expr::PRIME && e->a[1]->k != Expr::PRIME)) return false;
+        if ((o == "\\in" || o == "\\notin") && e->a[1]->k == Expr::PRIME && rset_var(e->a[1]->a[0])) {   // [type |-> "ack"] \in msgs'
+            const VarInfo &v = *rset_var(e->a[1]->a[0]);
+            if (!in_acon) cfail("a primed variable (`" + expr_text(e->a[1]) + "`) outside an ACTION_CONSTRAINT", e->pos);
+            push_record(v, e->a[0]);   // (the element's fields: read as written)
+            emit(mc::VM_OLD_ON);
+            emit_rs(mc::VM_RSHAS, v);
+            emit(mc::VM_OLD_OFF);
+            if (o == "\\notin") emit(mc::VM_NOT);
+            return true;
+        }
+        if (o != "=" && o != "#") return false;
+        for (int side = 0; side < 2; side++) {
+            const EP &pr = e->a[(size_t)side], &other = e->a[(size_t)(1 - side)];
+            if (pr->k != Expr::PRIME) continue;
+            const EP &x = pr->a[0];
+            if (rset_var(x) && other->k == Expr::SETENUM && other->a.empty()) {   // msgs' = {}
+                const int base = rset_var(x)->base;
+                primed(pr, [&](const EP &) { emit(mc::VM_LOAD, base); });
+                emit(mc::VM_PUSH, 0); emit(o == "=" ? mc::VM_EQ : mc::VM_NE);
+                return true;
+            }
+            if (seq_ref(x) && other->k == Expr::TUPLE) {   // q' = <<>>, q' # <<1, 2>>
+                for (const auto &el : other->a) {
+                    long long cv;
+                    if (!const_scalar(el, cv)) cfail("`" + expr_text(e) + "`: a primed sequence can be compared with a tuple of constants only", e->pos);
+                }
+                primed(pr, [&](const EP &q) { seq_equals(seq_ref(q), other, o == "#"); });
+                return true;
+            }
+            if (x->k == Expr::ID && is_variable(x) && whole_variable(x) && !set_var(x)) {   // q' = q, msgs' # msgs, f' = f: cell by cell
+                if (other->k != Expr::ID || other->s != x->s)
+                    cfail("`" + expr_text(e) + "`: a primed sequence / set of records / function can be compared with its own unprimed variable (" + x->s + "' = " + x->s +
+                          "), a sequence also with a tuple of constants, a set of records also with {}", e->pos);
+                auto u = std::make_shared<Expr>();
+                u->k = Expr::CALL; u->s = "UNCHANGED"; u->a = {x}; u->pos = e->pos;
+                unchanged(u);
+                if (o == "#") emit(mc::VM_NOT);
+                return true;
+            }
+        }
+        return false;
+    }
     void binop(const EP &e) {
         const std::string &o = e->s;
+        if (primed_whole(e)) return;
         if ((o == "\\in" || o == "\\notin") && rset_var(e->a[1])) {   // [type |-> "ack", from |-> self] \in msgs
             const VarInfo &v = *rset_var(e->a[1]);
             push_record(v, e->a[0]);
@@ -1930,6 +2142,10 @@ struct Compiler {
             }
         // ---- the predicates of the cfg's other temporal properties: code after the invariants', entries in a table of the program's own
         live_properties();
+        // ---- the cfg's ACTION_CONSTRAINTs and VIEW
+        cur_nv = nv;
+        cfg_more();
+        if (!P.view.empty()) P.live_refusal = "the cfg has a VIEW (the graph is one of representative states: fairness over it is not the spec's)";
         // ---- header
         c[mc::VMH_MAGIC] = mc::VM_MAGIC;
         c[mc::VMH_NV] = nv;
@@ -1947,6 +2163,13 @@ struct Compiler {
         c[mc::VMH_NUM_INIT_LO] = (int)(uint32_t)ninit;
         c[mc::VMH_NUM_INIT_HI] = (int)(uint32_t)(ninit >> 32);
         c[mc::VMH_CODE_LEN] = (int)c.size();
+        // ---- behind the image (not counted in its length): the table of the cfg's ACTION_CONSTRAINTs / VIEW, all zero without them (spec_vm_cfg.h VmExt)
+        const size_t x = c.size();
+        c.resize(x + (size_t)mc::VMX_SIZE, 0);
+        c[x + mc::VMX_NACON] = (int)P.acon_entry.size();
+        c[x + mc::VMX_NVIEW] = (int)P.view.size();
+        for (size_t k = 0; k < P.acon_entry.size(); k++) c[x + mc::VMX_ACON0 + k] = P.acon_entry[k];
+        for (size_t k = 0; k < P.view.size(); k++) { c[x + mc::VMX_VIEW_A0 + k] = P.view[k].a; c[x + mc::VMX_VIEW_N0 + k] = P.view[k].n; }
     }
 };
 
@@ -2009,6 +2232,7 @@ int vm_make_params(const int64_t *p, unsigned np, VmParams &o) {
     o.self_tab = c[VMH_SELF_TAB];
     o.code_len = c[VMH_CODE_LEN];
     o.num_init = (uint64_t)(uint32_t)c[VMH_NUM_INIT_LO] | (uint64_t)(uint32_t)c[VMH_NUM_INIT_HI] << 32;
+    if (P->image.size() != (size_t)o.code_len + (size_t)VMX_SIZE) return -1;   // (the table of the cfg's ACTION_CONSTRAINTs / VIEW behind the image)
     return 0;
 }
 

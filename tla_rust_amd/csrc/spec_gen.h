@@ -23,8 +23,12 @@
 //   static int run_init(uint64_t &ch, Cells &v)                                     // R_* of SpecVmT::Run
 //   template <int INST> static int run_inst(int32_t label, uint64_t &ch, Cells &v, const Cells &old, int &aux)
 //   static int run_inv(int k, Cells &v, int32_t &result)                            // INVARIANTs 0 .. NINV-1, then CONSTRAINTs
+// and, only for a program whose cfg has them:
+//   constexpr int NACON; static int run_acon(int k, const Cells &cur, const Cells &succ, int32_t &result)   // ACTION_CONSTRAINT k on cur -> succ
+//   constexpr int VIEW, VIEW_WORDS; static bool view_words(Cells &v, uint64_t *w)                   // the VIEW's values, two per word
 #pragma once
 #include "spec_vm.h"
+#include <type_traits>
 
 #ifndef MC_GEN_FP_SUM
 #define MC_GEN_FP_SUM 0
@@ -45,6 +49,12 @@ struct SpecGenPairs<G, true> {
     static constexpr int PAIR_FAMILIES = 1, TOTAL_SLOTS = G::NINST * G::MAXCH + 1, PAIR_ROUND_SLOTS = 20, PAIR_ROUNDS = (TOTAL_SLOTS + 19) / 20,
                          PAIR_KEYS = (MC_GEN_KEY_BY_INST && G::NKEYS <= 64) ? G::NKEYS : G::NLABELS, W_PAIR_BASE = -1;
 };
+// does the generated program carry action constraints / a view?  (members that exist only then)
+template <class G, class = void> struct gen_has_acon : std::false_type {};
+template <class G> struct gen_has_acon<G, std::void_t<decltype(G::NACON)>> : std::true_type {};
+template <class G, class = void> struct gen_has_view : std::false_type {};
+template <class G> struct gen_has_view<G, std::void_t<decltype(G::VIEW_WORDS)>> : std::true_type {};
+
 template <class G>
 constexpr bool spec_gen_pairs_ok() { return G::NINST * G::MAXCH + 1 <= 128 && G::NLABELS <= 64; }
 
@@ -72,21 +82,49 @@ struct SpecGenT : SpecGenPairs<G, spec_gen_pairs_ok<G>()> {
         return 0;
     }
 
-    MC_HD static uint64_t fp_words(const uint64_t *w) {  // (SpecVmT::fp_vals over the stored row: the interpreter's fingerprints when the layout is the interpreter's)
+    MC_HD static uint64_t fp_words(const uint64_t *w) { return fp_n<MAX_WORDS>(w); }
+    // the fingerprint a successor is looked up and stored by: of its stored row, or — cfg VIEW — of its view values, in the same per-term
+    // form; false = an evaluation error inside the view
+    MC_HD static bool fp_state(Cells &v, const uint64_t *w, uint64_t &fp) {
+        if constexpr (gen_has_view<G>::value) {
+            uint64_t vw[G::VIEW_WORDS];
+            const bool ok = G::view_words(v, vw);
+            fp = fp_n<G::VIEW_WORDS>(vw);
+            return ok;
+        } else {
+            fp = fp_words(w);
+            return true;
+        }
+    }
+    // cfg ACTION_CONSTRAINT: SpecVmCfgT::acon_status
+    MC_HD static unsigned acon_status(const Cells &cur, Cells &v) {
+        if constexpr (gen_has_acon<G>::value) {
+#pragma unroll
+            for (int k = 0; k < G::NACON; ++k) {
+                int32_t res = 0;
+                const int r = G::run_acon(k, cur, v, res);
+                if (r != R_OK) return ST_SPECERR;
+                if (!res) return ST_OUT_OF_MODEL;
+            }
+        }
+        return 0;
+    }
+    template <int N>
+    MC_HD static uint64_t fp_n(const uint64_t *w) {  // (SpecVmT::fp_vals over the stored row: the interpreter's fingerprints when the layout is the interpreter's)
 #if MC_GEN_FP_SUM
         // packed rows: the fingerprint is the sum of one hmum term per stored word (salted by the word's index; independent terms, two
         // 32 x 32 -> 64 multiply-accumulates each: mc_common.h, the raft / SSI lowerings' H) and ONE fmix64 over the sum, instead of a chain
-        // of MAX_WORDS dependent fmix64 rounds (six quarter-rate multiplies each).  The interpreter's layout keeps the interpreter's fingerprints.
+        // of N dependent fmix64 rounds (six quarter-rate multiplies each).  The interpreter's layout keeps the interpreter's fingerprints.
         if constexpr (G::PACKED) {
             uint64_t h = 0;
 #pragma unroll
-            for (int k = 0; k < MAX_WORDS; ++k) h += hmum(w[k], 0x632be59bd9b4e019ull * (uint64_t)(k + 1));
+            for (int k = 0; k < N; ++k) h += hmum(w[k], 0x632be59bd9b4e019ull * (uint64_t)(k + 1));
             return fp_nonzero(fmix64(h ^ 0x9e3779b97f4a7c15ull));
         }
 #endif
         uint64_t h = 0x9e3779b97f4a7c15ull;
 #pragma unroll
-        for (int k = 0; k < MAX_WORDS; ++k) h = fmix64(h ^ (w[k] + 0x632be59bd9b4e019ull * (uint64_t)(k + 1)));
+        for (int k = 0; k < N; ++k) h = fmix64(h ^ (w[k] + 0x632be59bd9b4e019ull * (uint64_t)(k + 1)));
         return fp_nonzero(h);
     }
     template <class Ref>
@@ -131,11 +169,22 @@ struct SpecGenT : SpecGenPairs<G, spec_gen_pairs_ok<G>()> {
         uint64_t w[MAX_WORDS];
 #pragma unroll
         for (int k = 0; k < MAX_WORDS; ++k) w[k] = s.get(k);
+        if constexpr (gen_has_view<G>::value) {
+            Cells v;
+            G::from_words(w, v);
+            uint64_t fp;
+            (void)fp_state(v, w, fp);
+            return fp;
+        }
         return fp_words(w);
     }
     MC_HD static unsigned init_status(const Params &, CWordRef s) {
         Cells v;
         unpack(s, v);
+        if constexpr (gen_has_view<G>::value) {
+            uint64_t vw[G::VIEW_WORDS];
+            if (!G::view_words(v, vw)) return ST_ENABLED | ST_SPECERR;
+        }
         return ST_ENABLED | inv_status(v);
     }
     template <class Ref>
@@ -180,7 +229,9 @@ struct SpecGenT : SpecGenPairs<G, spec_gen_pairs_ok<G>()> {
         if (r == R_ASSERT) return ST_ENABLED | ST_ASSERT;
         if (r == R_ERROR) return ST_ENABLED | ST_SPECERR;
         if (r == R_OVERFLOW) return ST_ENABLED | ST_OVERFLOW;
-        return ST_ENABLED | inv_status(v);
+        unsigned st = ST_ENABLED | inv_status(v);
+        if constexpr (gen_has_acon<G>::value) { if (!(st & (ST_SPECERR | ST_OUT_OF_MODEL))) st |= acon_status(cur, v); }
+        return st;
     }
     template <class Ref>
     MC_HD static unsigned eval(const Params &, const Local &l, Ref, int slot, uint64_t &fp) {
@@ -189,7 +240,7 @@ struct SpecGenT : SpecGenPairs<G, spec_gen_pairs_ok<G>()> {
         if (st & ST_ENABLED) {
             uint64_t w[MAX_WORDS];
             if (!G::to_words(v, w)) return ST_ENABLED | ST_SPECERR;   // outside an inferred range: reported, never stored
-            fp = fp_words(w);
+            if (!fp_state(v, w, fp)) return ST_ENABLED | ST_SPECERR;
         }
         return st;
     }
@@ -257,7 +308,7 @@ struct SpecGenT : SpecGenPairs<G, spec_gen_pairs_ok<G>()> {
         const unsigned st = step(cur, slot, v);
         if (st & ST_ENABLED) {
             if (!G::to_words(v, o.w)) return ST_ENABLED | ST_SPECERR;
-            fp = fp_words(o.w);
+            if (!fp_state(v, o.w, fp)) return ST_ENABLED | ST_SPECERR;
         }
         return st;
     }

@@ -8,6 +8,7 @@
 #include "spec_raft.h"
 #include "spec_ssi.h"
 #include "spec_vm.h"
+#include "spec_vm_cfg.h"
 
 namespace mc {
 
@@ -55,10 +56,10 @@ int dispatch_spec(const mc_spec_desc *d, F &&f) {
     case MC_SPEC_PCAL: {  // compiled PlusCal: params[0] = the mc_program handle (pcal_compile.cpp)
         VmParams p;
         if (vm_make_params(d->params, d->nparams, p)) return MC_EBADCFG;
-        if (p.nv <= 16) return f(SpecVm16{}, p);
-        if (p.nv <= 32) return f(SpecVm32{}, p);
-        if (p.nv <= 64) return f(SpecVm64{}, p);
-        return f(SpecVm{}, p);
+        if (p.nv <= 16) return f(SpecVmCfg16{}, p);   // (spec_vm_cfg.h: the interpreter with the cfg's ACTION_CONSTRAINTs / VIEW)
+        if (p.nv <= 32) return f(SpecVmCfg32{}, p);
+        if (p.nv <= 64) return f(SpecVmCfg64{}, p);
+        return f(SpecVmCfg{}, p);
     }
     default: return MC_EBADCFG;
     }
