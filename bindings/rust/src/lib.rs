@@ -69,6 +69,8 @@ pub struct mc_scc_info {
 #[repr(C)]
 pub struct mc_live_info { pub violated: i32, pub pad: u32, pub fair_components: u64, pub root: u64, pub root_size: u64, pub seconds: f64 }
 #[repr(C)]
+pub struct mc_live_strong_info { pub rounds: u32, pub scc_builds: u32, pub closed_states: u64, pub final_components: u64, pub seconds: f64 }
+#[repr(C)]
 pub struct mc_engine { _private: [u8; 0] }
 #[repr(C)]
 pub struct mc_program { _private: [u8; 0] }
@@ -94,6 +96,9 @@ extern "C" {
     pub fn mc_engine_liveness(e: *mut mc_engine, weak_fair_mask: u64, out: *mut mc_live_info) -> c_int;
     pub fn mc_engine_liveness_trace(e: *mut mc_engine, prefix_out: *mut u32, nprefix_inout: *mut usize, cycle_out: *mut u32,
                                     ncycle_inout: *mut usize) -> c_int;
+    // the same under strong fairness of the instances in strong_mask (`fair+ process`), weak fairness of those in weak_mask
+    pub fn mc_engine_liveness_strong(e: *mut mc_engine, weak_mask: u64, strong_mask: u64, out: *mut mc_live_info,
+                                     strong_out: *mut mc_live_strong_info) -> c_int;
     pub fn mc_engine_read_states(e: *mut mc_engine, first: u64, count: u64, out: *mut u8) -> c_int;
     // TLC's checkpoint / -recover (testout1:10): write / reload the states found so far; the next run continues
     pub fn mc_engine_checkpoint(e: *mut mc_engine, path: *const c_char) -> c_int;
@@ -126,6 +131,7 @@ extern "C" {
     // fairness of the algorithm (bit k of the mask: process instance k is weakly fair; *refusal: why Termination cannot be checked, or
     // null; returns the number of instances) and the cfg's PROPERTY names (null past the last)
     pub fn mc_program_fairness(p: *const mc_program, weak_fair_mask: *mut u64, refusal: *mut *const c_char) -> c_int;
+    pub fn mc_program_fairness_strong(p: *const mc_program, weak_mask: *mut u64, strong_mask: *mut u64, refusal: *mut *const c_char) -> c_int;
     pub fn mc_program_property(p: *const mc_program, index: c_int) -> *const c_char;
     // the cfg's VIEW (the text of its definition, null without one) and ACTION_CONSTRAINT names (null past the last)
     pub fn mc_program_view(p: *const mc_program) -> *const c_char;

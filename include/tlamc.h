@@ -118,6 +118,9 @@ typedef struct {
                             interpreter and says so on stderr */
 #define MC_F_GENERIC 128u /* mc_check_files: run a PlusCal module through the compiled program (MC_SPEC_PCAL) even
                              when a hand lowering of its algorithm exists (A/B of the two paths)  */
+#define MC_F_STRONGFAIR 33554432u /* mc_check_files (`mc -strongfair`): a `fair+ process` is checked under strong fairness (mc_program_fairness_strong,
+                             mc_engine_liveness_strong / mc_engine_liveness_check_strong) instead of being named as NOT checked.  Without
+                             `fair+` in the algorithm the report is the one without the flag. */
 #define MC_F_COVERAGE 16777216u /* TLC's -coverage: count, per action of the model, the successors it generated and the distinct states it
                              was first to find (mc_engine_coverage below; mc_check_files appends "The coverage statistics" to its
                              report).  Implies MC_F_TRACE.  One-GPU engines only: mc_engine_create refuses it with shard_count > 1.
@@ -354,6 +357,29 @@ int mc_engine_liveness_check(mc_engine *e, uint64_t weak_fair_mask, const mc_liv
 /* the component ids the last mc_engine_liveness_check judged: those of the graph induced by its M (the least arena index of the state's
  * component; a state outside M is its own) — mc_engine_scc_read's array for MC_LIVE_STABLE.  MC_ESTATE without such a check. */
 int mc_engine_liveness_components(mc_engine *e, uint64_t first, uint64_t count, uint32_t *scc_out);
+/* ------------------------------------------------------------------ the same under strong fairness of whole processes
+ * `fair+ process` asks for SF_vars(proc_p): a process that is enabled again and again must step.  weak_mask / strong_mask name the
+ * weakly and the strongly fair instances (disjoint: SF implies WF; mc_program_fairness_strong gives a program's).  A set X of M that
+ * is one state or strongly connected by its own edges is fair iff every weak process is taken inside X or disabled in some state of
+ * X, and every strong process that is enabled in some state of X is taken inside X; a check is violated iff some fair X holds a T
+ * state and is reachable inside M from an S state of M (Termination: M = all, S = the initial states, T = not Done).  Decided by
+ * refinement: the components of the open states, each weakly unfair one closed, each one blocked by strong processes stripped of the
+ * states that enable them, the rest found again, at most popcount(strong_mask) + 1 rounds.  With strong_mask == 0 every field of
+ * mc_live_info / mc_live_check_info but `seconds` is the weak call's.  mc_engine_liveness_components and mc_engine_liveness_trace
+ * serve the last check of either kind: after a strong one the refined ids (a final component's id where it was found, every other
+ * state its own index) and a cycle inside one final component that takes a real step of every strong process taken in it.  Device
+ * memory beside the weak calls': 25 bytes per state.  Errors: the weak twins', MC_EBADCFG for masks that overlap or name an instance
+ * the program does not have, MC_ESTATE for a refinement that did not converge within its bound. */
+typedef struct mc_live_strong_info {
+    uint32_t rounds;            /* of the refinement (1: no component was blocked)                    */
+    uint32_t scc_builds;        /* component builds of rounds >= 2 (never kept)                       */
+    uint64_t closed_states;     /* states of M the refinement closed                                  */
+    uint64_t final_components;  /* final violating components                                         */
+    double   seconds;           /* the whole call                                                     */
+} mc_live_strong_info;
+int mc_engine_liveness_strong(mc_engine *e, uint64_t weak_mask, uint64_t strong_mask, mc_live_info *out, mc_live_strong_info *strong_out);
+int mc_engine_liveness_check_strong(mc_engine *e, uint64_t weak_mask, uint64_t strong_mask, const mc_live_property *prop, mc_live_check_info *out,
+                                    mc_live_strong_info *strong_out);
 /* copy `count` resident states starting at arena index `first` (discovery order: level by level)
  * to the host, mc_state_bytes() bytes each — TLC's "states/" dump, for tests and tooling */
 int mc_engine_read_states(mc_engine *e, uint64_t first, uint64_t count, uint8_t *out);
@@ -685,6 +711,9 @@ int mc_program_assert_pos(const mc_program *p, int index, int *line, int *col); 
  * instance k in slot order; returns the number of instances.  *refusal (either may be NULL): NULL when mc_engine_liveness decides
  * `Termination` for this program, else the reason it cannot (`fair+`, a `+` / `-` label in a fair process, procedures). */
 int mc_program_fairness(const mc_program *p, uint64_t *weak_fair_mask, const char **refusal);
+/* the same for the strong calls: *strong_mask = the `fair+` instances, *weak_mask = the other fair ones (disjoint); *refusal is NULL
+ * for a program whose only obstacle was `fair+`, and mc_program_fairness's words for everything else */
+int mc_program_fairness_strong(const mc_program *p, uint64_t *weak_mask, uint64_t *strong_mask, const char **refusal);
 /* the cfg's PROPERTY / PROPERTIES names, in cfg order; NULL past the last (what a caller that runs the search itself — `mc -gpus` —
  * must name as NOT checked) */
 const char *mc_program_property(const mc_program *p, int index);

@@ -112,6 +112,12 @@ class LiveInfo(C.Structure):
                 ("root_size", C.c_uint64), ("seconds", C.c_double)]
 
 
+class LiveStrongInfo(C.Structure):
+    """mc_live_strong_info"""
+    _fields_ = [("rounds", C.c_uint32), ("scc_builds", C.c_uint32), ("closed_states", C.c_uint64), ("final_components", C.c_uint64),
+                ("seconds", C.c_double)]
+
+
 class LiveProperty(C.Structure):
     """mc_live_property"""
     _fields_ = [("origin", C.c_char * 64), ("name", C.c_char * 128), ("kind", C.c_int32), ("p", C.c_int32), ("q", C.c_int32),
@@ -269,6 +275,10 @@ def lib():
         L.mc_engine_predicates.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         L.mc_engine_liveness_components.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         L.mc_engine_liveness_check.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(LiveProperty), C.POINTER(LiveCheckInfo)]
+        L.mc_program_fairness_strong.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_char_p)]
+        L.mc_engine_liveness_strong.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(LiveInfo), C.POINTER(LiveStrongInfo)]
+        L.mc_engine_liveness_check_strong.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(LiveProperty), C.POINTER(LiveCheckInfo),
+                                                      C.POINTER(LiveStrongInfo)]
         L.mc_program_view.argtypes = [C.c_void_p]
         L.mc_program_view.restype = C.c_char_p
         L.mc_program_action_constraint.argtypes = [C.c_void_p, C.c_int]
@@ -472,6 +482,23 @@ class Engine:
         ci = LiveCheckInfo()
         _check(lib().mc_engine_liveness_check(self._h, weak_fair_mask, C.byref(lp), C.byref(ci)), "mc_engine_liveness_check")
         return Result((k, getattr(ci, k)) for k, _ in LiveCheckInfo._fields_ if k != "pad")
+
+    def liveness_strong(self, weak_mask, strong_mask):
+        """mc_engine_liveness_strong: `Termination` under weak fairness of the instances in weak_mask and strong fairness of those in
+        strong_mask (Program.strong_fairness): (liveness()'s dict, a dict with rounds, scc_builds, closed_states, final_components,
+        seconds)"""
+        li, si = LiveInfo(), LiveStrongInfo()
+        _check(lib().mc_engine_liveness_strong(self._h, weak_mask, strong_mask, C.byref(li), C.byref(si)), "mc_engine_liveness_strong")
+        return (Result((k, getattr(li, k)) for k, _ in LiveInfo._fields_ if k != "pad"), Result((k, getattr(si, k)) for k, _ in LiveStrongInfo._fields_))
+
+    def check_property_strong(self, weak_mask, strong_mask, prop):
+        """mc_engine_liveness_check_strong: check_property under the two masks: (check_property()'s dict, liveness_strong()'s second)"""
+        lp = LiveProperty(prop["origin"].encode(), prop["name"].encode(), prop["kind"], prop["p"], prop["q"], 1 if prop["refused"] else 0,
+                          (prop["reason"] or "").encode())
+        ci, si = LiveCheckInfo(), LiveStrongInfo()
+        _check(lib().mc_engine_liveness_check_strong(self._h, weak_mask, strong_mask, C.byref(lp), C.byref(ci), C.byref(si)),
+               "mc_engine_liveness_check_strong")
+        return (Result((k, getattr(ci, k)) for k, _ in LiveCheckInfo._fields_ if k != "pad"), Result((k, getattr(si, k)) for k, _ in LiveStrongInfo._fields_))
 
     def check_components(self, count):
         """mc_engine_liveness_components: numpy uint32, the component ids of the first `count` states in the graph the last
@@ -770,6 +797,10 @@ class Program:
         self.ninst = _check(lib().mc_program_fairness(h, C.byref(mask), C.byref(why)), "mc_program_fairness")
         self.fair_mask = int(mask.value)             # bit k: process instance k (slot order) is weakly fair
         self.live_refusal = why.value.decode() if why.value else None   # why Engine.liveness cannot decide Termination for it (None: it can)
+        weak, strong, why = C.c_uint64(0), C.c_uint64(0), C.c_char_p()
+        _check(lib().mc_program_fairness_strong(h, C.byref(weak), C.byref(strong), C.byref(why)), "mc_program_fairness_strong")
+        # (weak mask, strong mask: the `fair+` instances, why Engine.liveness_strong cannot decide for it or None)
+        self.strong_fairness = (int(weak.value), int(strong.value), why.value.decode() if why.value else None)
         # the cfg's PROPERTY names other than Termination: one dict per check (a quantifier instance of a conjunct) or per refused name —
         # origin, name, kind (MC_LIVE_*, LIVE_KINDS), p, q (indices into live_predicates, -1 = none), refused, reason
         self.live_properties, self.live_predicates = [], []

@@ -119,6 +119,8 @@ struct EngineBase {
     virtual int liveness(uint64_t weak_fair_mask, mc_live_info *out) = 0;
     virtual int predicates(uint64_t first, uint64_t count, uint32_t *bits_out) = 0;
     virtual int liveness_check(uint64_t weak_fair_mask, const mc_live_property *prop, mc_live_check_info *out) = 0;
+    virtual int liveness_strong(uint64_t weak, uint64_t strong, mc_live_info *out, mc_live_strong_info *sout) = 0;
+    virtual int liveness_check_strong(uint64_t weak, uint64_t strong, const mc_live_property *prop, mc_live_check_info *out, mc_live_strong_info *sout) = 0;
     int graph_read(uint64_t first, uint64_t count, uint64_t *offsets_out, uint32_t *dst_out, int32_t *action_out, size_t *nedges_inout) {
         return gr.read(first, count, offsets_out, dst_out, action_out, nedges_inout);
     }
@@ -687,6 +689,72 @@ struct Engine : EngineBase {
             }
             if (int rc = predicates_build("mc_engine_liveness_check")) return rc;
             return gr.live_check_masked(all, fair, kind, need_p ? prop->p : -1, need_q ? prop->q : -1, stream, t0, out);
+        }
+    }
+
+    // ------------------------------------------------------------------------------- the same under strong fairness:
+    // the weak twins' conditions and preparation, then StateGraph::live_check_strong
+    int strong_prepare(const char *name, uint64_t weak, uint64_t strong, bool fresh_proc, uint64_t *all_out) {
+        const std::string call(name);
+        if (cfg.shard_count > 1) { set_error(call + ": not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
+        if constexpr (!LiveProc<S>::HAS || !LivePred<S>::HAS) {
+            set_error(call + ": this lowering has no process instances (compiled PlusCal programs only)");
+            return MC_ENOSPEC;
+        } else {
+            if (!fr.have_run || ck.pending || fr.have_viol || fr.hi != fr.lo) {
+                set_error(call + ": needs a search of this engine that finished without a violation and with an empty queue (the complete state graph)");
+                return MC_ESTATE;
+            }
+            const int np = LiveProc<S>::count(prm);
+            if (np > LIVE_MAX_PROCS) { set_error(call + ": at most 64 process instances"); return MC_EBADCFG; }
+            const uint64_t all = np >= 64 ? ~0ull : (1ull << np) - 1;
+            if ((weak | strong) & ~all) { set_error(call + ": a fairness mask names a process instance the program does not have"); return MC_EBADCFG; }
+            if (weak & strong) { set_error(call + ": the weak and the strong mask overlap (a strongly fair process is weakly fair already)"); return MC_EBADCFG; }
+            if (!gr.built || !gr.lv.scc_built) { mc_scc_info si; if (int rc = scc(&si)) return rc; }
+            auto &lv = gr.lv;
+            lv.checked = false;
+            HIP_TRY(hipSetDevice(cfg.device));
+            if (fresh_proc || !lv.proc_built) {
+                const uint64_t edges = gr.info.edges;
+                if (int rc = graph_alloc(lv.proc, edges, "the edges' processes", name)) return rc;
+                HIP_TRY(hipMemsetAsync(lv.proc, 0xff, (edges ? edges : 1) * sizeof(int8_t), stream));
+                graph_chunks(k_live_proc<S>, 0, fr.lo, (const uint64_t *)gr.offsets.p, lv.proc.p);
+                lv.proc_built = true;
+            }
+            *all_out = all;
+            return MC_OK;
+        }
+    }
+    int liveness_strong(uint64_t weak, uint64_t strong, mc_live_info *out, mc_live_strong_info *sout) override {
+        memset(out, 0, sizeof *out);
+        memset(sout, 0, sizeof *sout);
+        const auto t0 = std::chrono::steady_clock::now();
+        uint64_t all = 0;
+        if (int rc = strong_prepare("mc_engine_liveness_strong", weak, strong, true, &all)) return rc;
+        return gr.live_check_strong(all, weak, strong, -1, -1, -1, stream, t0, out, nullptr, sout);
+    }
+    int liveness_check_strong(uint64_t weak, uint64_t strong, const mc_live_property *prop, mc_live_check_info *out, mc_live_strong_info *sout) override {
+        memset(out, 0, sizeof *out);
+        memset(sout, 0, sizeof *sout);
+        if constexpr (!LiveProc<S>::HAS || !LivePred<S>::HAS) {
+            set_error("mc_engine_liveness_check_strong: this lowering has no process instances (compiled PlusCal programs only)");
+            return MC_ENOSPEC;
+        } else {
+            const char *call = "mc_engine_liveness_check_strong";
+            if (prop->refused) { set_error(std::string(call) + ": the front end refused " + prop->name); return MC_EBADCFG; }
+            const int npred = vm_live_preds(prm.host, nullptr, 0);
+            const int kind = prop->kind;
+            if (kind < LIVE_LEADS_TO || kind > LIVE_STABLE) { set_error(std::string(call) + ": unknown kind " + std::to_string(kind)); return MC_EBADCFG; }
+            const bool need_p = kind == LIVE_LEADS_TO || kind == LIVE_STABLE, need_q = kind != LIVE_STABLE;
+            if ((need_p && (prop->p < 0 || prop->p >= npred)) || (need_q && (prop->q < 0 || prop->q >= npred)) || npred > LIVE_MAX_PREDS) {
+                set_error(std::string(call) + ": a predicate index the program does not have (it has " + std::to_string(npred) + " predicates)");
+                return MC_EBADCFG;
+            }
+            const auto t0 = std::chrono::steady_clock::now();
+            uint64_t all = 0;
+            if (int rc = strong_prepare(call, weak, strong, false, &all)) return rc;
+            if (int rc = predicates_build(call)) return rc;
+            return gr.live_check_strong(all, weak, strong, kind, need_p ? prop->p : -1, need_q ? prop->q : -1, stream, t0, nullptr, out, sout);
         }
     }
 
@@ -2268,6 +2336,13 @@ int mc_engine_predicates(mc_engine *e, uint64_t first, uint64_t count, uint32_t 
 }
 int mc_engine_liveness_check(mc_engine *e, uint64_t weak_fair_mask, const mc_live_property *prop, mc_live_check_info *out) {
     return e && prop && out ? e->impl->liveness_check(weak_fair_mask, prop, out) : MC_EBADCFG;
+}
+int mc_engine_liveness_strong(mc_engine *e, uint64_t weak_mask, uint64_t strong_mask, mc_live_info *out, mc_live_strong_info *strong_out) {
+    return e && out && strong_out ? e->impl->liveness_strong(weak_mask, strong_mask, out, strong_out) : MC_EBADCFG;
+}
+int mc_engine_liveness_check_strong(mc_engine *e, uint64_t weak_mask, uint64_t strong_mask, const mc_live_property *prop, mc_live_check_info *out,
+                                    mc_live_strong_info *strong_out) {
+    return e && prop && out && strong_out ? e->impl->liveness_check_strong(weak_mask, strong_mask, prop, out, strong_out) : MC_EBADCFG;
 }
 int mc_engine_liveness_components(mc_engine *e, uint64_t first, uint64_t count, uint32_t *scc_out) {
     return e && (scc_out || !count) ? e->impl->liveness_components(first, count, scc_out) : MC_EBADCFG;

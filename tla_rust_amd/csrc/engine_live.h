@@ -29,10 +29,20 @@
 //                                flag's place; en comes from the full row, taken from edges whose two ends share the component
 //               k_live_reach     dist[v], to a fixed point: 0 in a violating component, else 1 + the least dist of a successor in M
 //               k_live_witness   the states of M, the S states with a dist, and the least of those
+//   strong      (mc_engine_liveness_strong / mc_engine_liveness_check_strong) the refinement, one round per loop:
+//               k_live_open_init every state of M open, refined ids = own index
+//               k_scc_open       rounds >= 2, before the first trim: a state that is not open is a component of its own
+//               k_live_reduce    as above, over the round's components (a closed state merges into its own entry: nobody reads it)
+//               k_live_enabled   en of the open states, OR-ed per component into enabled[]
+//               k_live_classify  per root of an open component: the final violating components, counted, and the least root
+//               k_live_refine    per open state: closed / still open / final; a final state takes its component's id and size into the
+//                                refined arrays and dist 0; states closed and "some state is still open", one atomic per wavefront
+//               then k_live_reach / k_live_witness as above
 //
 // Memory, beside the graph's 8 bytes per state and 6 per edge: 16 bytes per state (transpose offsets 8, scc 4, colour / size 4) and 4 per
 // edge (transpose) for mc_engine_scc, 4 more per state while the transpose is built; mc_engine_liveness adds 1 byte per edge (proc) and 20
-// per state (taken 8, disabled 8, Done 4).
+// per state (taken 8, disabled 8, Done 4).  A strong check adds 25 per state: enabled 8, open / closed / final 1, the refined ids and
+// sizes 8, the working ids and sizes of rounds >= 2 another 8.
 #ifndef TLAMC_ENGINE_LIVE_H
 #define TLAMC_ENGINE_LIVE_H
 
@@ -303,6 +313,103 @@ k_live_witness(uint64_t n, const uint32_t *__restrict__ pred, LiveCheck ck, cons
     if (b && (int)(threadIdx.x & 63) == __ffsll((long long)b) - 1) {   // (the first bad lane of a wavefront holds its least state)
         atomicAdd(&cc->bad_starts, (unsigned long long)__popcll(b));
         atomicMin(&cc->witness, (unsigned)v);
+    }
+}
+
+// ---- strong fairness (mc_engine_liveness_strong / mc_engine_liveness_check_strong): the refinement of liveness.h
+struct LiveStrongCounters {
+    unsigned long long closed, final_components;   // states closed so far; final violating components so far
+    unsigned first_root, open;                     // the least final root, ~0u = none; some state is still open (cleared per round)
+};
+// every state of M is open, the others closed; a closed state's refined id is its own index
+template <bool MASKED>
+static __global__ void __launch_bounds__(256)
+k_live_open_init(uint64_t n, const uint32_t *__restrict__ pred, LiveCheck ck, uint8_t *__restrict__ open, uint32_t *__restrict__ fscc,
+                 uint32_t *__restrict__ fsize) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    open[v] = !MASKED || live_in_mask(ck, pred[v]) ? LIVE_ST_OPEN : LIVE_ST_CLOSED;
+    fscc[v] = (uint32_t)v;
+    fsize[v] = 1u;
+}
+// the open-set build, beside k_scc_mask: scc[] is all SCC_LIVE when this runs; a state that is not open is a component of its own
+static __global__ void __launch_bounds__(256)
+k_scc_open(uint64_t n, const uint8_t *__restrict__ open, uint32_t *__restrict__ scc) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v < n && open[v] != LIVE_ST_OPEN) scc[v] = (uint32_t)v;
+}
+// en of every open state (the whole row: the full graph's), OR-ed into enabled[] at the state's component of the round; k_live_reduce's
+// merge.  The entries were cleared before the launch.
+static __global__ void __launch_bounds__(256)
+k_live_enabled(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ proc,
+               const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, const uint8_t *__restrict__ open, unsigned long long *enabled) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = v < n && open[v] == LIVE_ST_OPEN;
+    uint64_t en = 0;
+    uint32_t comp = 0;
+    if (active) {
+        const uint64_t o = offsets[v];
+        en = live_enabled_in((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc);
+        comp = scc[v];
+    }
+    const bool alone = active && size[comp] == 1;
+    if (alone) enabled[comp] = en;
+    unsigned long long rest = __ballot(active && !alone);
+    const unsigned lane = threadIdx.x & 63;
+    while (rest) {   // (the loop's condition is the same in every lane)
+        const int lead = __ffsll((long long)rest) - 1;
+        const uint32_t c0 = (uint32_t)__shfl((int)comp, lead);
+        const bool same = active && !alone && comp == c0;
+        const unsigned long long e = wave_or_u64(same ? en : 0ull);
+        if ((int)lane == lead && e) atomicOr(&enabled[c0], e);
+        rest &= ~__ballot(same);
+    }
+}
+// has_target of a component: the property checks keep "holds a T state" in done[]; Termination keeps "holds a Done state", and T is
+// "not Done" (a Done state is absorbing: a component with one is that one state)
+__device__ __forceinline__ bool live_strong_target(bool term, unsigned done) { return term ? done == 0u : done != 0u; }
+// per root of an open component: the final violating ones, counted, and the least of them
+static __global__ void __launch_bounds__(256)
+k_live_classify(uint64_t n, const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, const uint8_t *__restrict__ open,
+                const unsigned long long *__restrict__ taken, const unsigned long long *__restrict__ disabled, const unsigned *__restrict__ done,
+                const unsigned long long *__restrict__ enabled, uint64_t all, uint64_t weak, uint64_t strong, bool term, LiveStrongCounters *sc) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool root = v < n && open[v] == LIVE_ST_OPEN && scc[v] == (uint32_t)v;
+    const bool bad = root && live_violates_strong(all, weak, strong, taken[v], disabled[v], enabled[v], live_strong_target(term, done[v]), size[v]);
+    const unsigned long long b = __ballot(bad);
+    if (b && (int)(threadIdx.x & 63) == __ffsll((long long)b) - 1) {   // (the first bad lane of a wavefront holds its least root)
+        atomicAdd(&sc->final_components, (unsigned long long)__popcll(b));
+        atomicMin(&sc->first_root, (unsigned)v);
+    }
+}
+// per open state: closed, kept open or final, by plain stores to its own entries; dist (property checks; null for Termination) is 0 in
+// a final component
+static __global__ void __launch_bounds__(256)
+k_live_refine(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ proc,
+              const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, const unsigned long long *__restrict__ taken,
+              const unsigned long long *__restrict__ disabled, const unsigned *__restrict__ done, const unsigned long long *__restrict__ enabled,
+              uint64_t all, uint64_t weak, uint64_t strong, bool term, uint8_t *open, uint32_t *__restrict__ fscc, uint32_t *__restrict__ fsize,
+              uint32_t *__restrict__ dist, LiveStrongCounters *sc) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = v < n && open[v] == LIVE_ST_OPEN;
+    uint8_t next = LIVE_ST_CLOSED;
+    if (active) {
+        const uint32_t c = scc[v];
+        const uint64_t tk = taken[c], en_c = enabled[c], o = offsets[v];
+        const int cls = live_classify(all, weak, strong, tk, disabled[c], en_c, live_strong_target(term, done[c]), size[c]);
+        const uint64_t en = live_enabled_in((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc);
+        next = live_refine_state(cls, live_blockers(all, strong, en_c, tk), en);
+        open[v] = next;
+        if (next == LIVE_ST_FINAL) {
+            fscc[v] = c;
+            fsize[v] = size[c];
+            if (dist) dist[v] = 0u;
+        }
+    }
+    const unsigned long long closing = __ballot(active && next == LIVE_ST_CLOSED), staying = __ballot(active && next == LIVE_ST_OPEN);
+    if ((threadIdx.x & 63) == 0) {
+        if (closing) atomicAdd(&sc->closed, (unsigned long long)__popcll(closing));
+        if (staying) atomicOr(&sc->open, 1u);
     }
 }
 

@@ -50,6 +50,13 @@ int mc_program_fairness(const mc_program *p, uint64_t *weak_fair_mask, const cha
     if (refusal) *refusal = p->prog.live_refusal.empty() ? nullptr : p->prog.live_refusal.c_str();
     return p->prog.ninst;
 }
+int mc_program_fairness_strong(const mc_program *p, uint64_t *weak_mask, uint64_t *strong_mask, const char **refusal) {
+    if (!p) return MC_EBADCFG;
+    if (weak_mask) *weak_mask = p->prog.fair_mask & ~p->prog.strong_mask;
+    if (strong_mask) *strong_mask = p->prog.strong_mask;
+    if (refusal) *refusal = p->prog.live_refusal_strong.empty() ? nullptr : p->prog.live_refusal_strong.c_str();
+    return p->prog.ninst;
+}
 int mc_program_live_property(const mc_program *p, int index, mc_live_property *out) {
     if (!p || !out || index < 0 || (size_t)index >= p->prog.live_props.size()) return MC_EBADCFG;
     const auto &lp = p->prog.live_props[(size_t)index];
@@ -1590,9 +1597,10 @@ static int check_files_impl(const char *tla_path, const char *cfg_path, const mc
     std::vector<uint32_t> live_prefix, live_cycle;
     bool live_violated = false;
     if (generic && !R.properties.empty()) {
-        uint64_t fair = 0;
+        uint64_t fair = 0, strong = 0;   // strong: the `fair+` instances, under MC_F_STRONGFAIR (else they are refused, by name)
         const char *refusal = nullptr;
-        mc_program_fairness(prog, &fair, &refusal);
+        if (cfg->flags & MC_F_STRONGFAIR) mc_program_fairness_strong(prog, &fair, &strong, &refusal);
+        else mc_program_fairness(prog, &fair, &refusal);
         const bool complete = res->verdict == MC_V_OK && res->queue_left == 0;
         bool checked = false;   // Termination was decided (a cfg that names it twice is checked once)
         std::set<std::string> seen_names;
@@ -1635,7 +1643,8 @@ static int check_files_impl(const char *tla_path, const char *cfg_path, const mc
                 if (cfg->flags & (MC_F_COVERAGE | MC_F_PROGRESS)) o.put("Checking temporal property %s\n", name.c_str());
                 for (const auto &lp : checks) {
                     mc_live_check_info ci;
-                    if ((rc = mc_engine_liveness_check(e, fair, &lp, &ci))) { mc_engine_destroy(e); return rc; }
+                    mc_live_strong_info si;
+                    if ((rc = strong ? mc_engine_liveness_check_strong(e, fair, strong, &lp, &ci, &si) : mc_engine_liveness_check(e, fair, &lp, &ci))) { mc_engine_destroy(e); return rc; }
                     if (!ci.violated) continue;
                     if ((rc = take_trace())) { mc_engine_destroy(e); return rc; }
                     break;
@@ -1645,7 +1654,8 @@ static int check_files_impl(const char *tla_path, const char *cfg_path, const mc
             if (checked) continue;
             checked = true;
             mc_live_info li;
-            if ((rc = mc_engine_liveness(e, fair, &li))) { mc_engine_destroy(e); return rc; }
+            mc_live_strong_info si;
+            if ((rc = strong ? mc_engine_liveness_strong(e, fair, strong, &li, &si) : mc_engine_liveness(e, fair, &li))) { mc_engine_destroy(e); return rc; }
             if (!li.violated) continue;
             if ((rc = take_trace())) { mc_engine_destroy(e); return rc; }
         }

@@ -12,6 +12,7 @@
 //   * LiveProc<S>: which process instance takes the edge of a (state, slot) pair — slot / maxch for the two compiled-program
 //     lowerings, LIVE_TERM for the terminating disjunct.  Other lowerings have no processes: LiveProc<S>::HAS is false.
 //   * live_real_step, live_state, live_merge, live_fair, live_violates: the rule over CSR rows, per-edge processes and component ids.
+//   * strong fairness of whole processes (`fair+`): the refinement at the end of this file, DESIGN section 19.
 // Compiles without HIP.
 #pragma once
 #include "graph.h"
@@ -207,6 +208,75 @@ MC_HD uint32_t live_reach_step(uint32_t self, uint32_t mine, const uint32_t *dst
         if (dd != LIVE_FAR && dd + 1 < best) best = dd + 1;
     }
     return best;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Strong fairness of whole processes (`fair+ process`; mc_engine_liveness_strong / mc_engine_liveness_check_strong).
+// Fair is split into W (weak) and F (strong), disjoint.  For a set X of M that is one state or strongly connected by its own edges:
+//
+//   enabled(X)    { p : en(s, p) for some s in X }                         (en in the FULL graph, as disabled(X))
+//   X is fair     iff  W \subseteq taken(X) \cup disabled(X)  and  F \cap enabled(X) \subseteq taken(X)
+//                 — a strongly fair process is taken inside X or disabled in EVERY state of X
+//   violated      iff  some fair X holds a T state and is reachable inside M from an S state of M
+//
+// A component of G[M] need not be fair for a subset of it to be, so the components are refined (a Streett-style emptiness check).
+// Every state of M starts open; a round finds the components of the subgraph induced by the open states and classifies each:
+//
+//   LIVE_CLOSE     no T state, or some p of W neither taken in C nor disabled somewhere in C: no subset of C is fair and holds a T state
+//                  the first way, and every subset inherits the second defect — all of C is closed
+//   LIVE_BLOCKED   B = F \cap enabled(C) \ taken(C) is not empty: the states s of C with en(s) \cap B # {} are closed, the rest stays open
+//   LIVE_FINAL     else: C is fair, final and violating
+//
+//   every fair X survives inside one final component: X is strongly connected, so it lies in one component C of each round it is open in;
+//   taken(X) \subseteq taken(C) and disabled(X) \subseteq disabled(C), so C is not weakly unfair, and it holds X's T state; a p of B is
+//   not taken in C, so not in X, so — X being fair — it is enabled in no state of X: the states closed are none of X's.  X stays open
+//   whole until its component is final.
+//   a final component's closed walk is a fair suffix: C is one state or strongly connected inside the open states, so a closed walk
+//   passes every state and every internal edge of C; every p of W is taken on it or disabled in a state of it; every p of F that is
+//   enabled in a state of C is taken on it (B = {}), and the others are disabled along all of it.
+//   A process of B is disabled in every state that survives, so it is in no later enabled(C'): at most popcount(F \cap all) rounds
+//   block, and one more ends.  With F = {} the first round is the weak rule exactly.
+//
+//   * live_enabled_in: en of one state.  live_blockers: B.  live_classify: the three cases.  live_fair_strong / live_violates_strong:
+//     the rule for one set.  live_closes_state: does a blocked component's state leave.  live_strong_rounds: the bound.
+constexpr int LIVE_CLOSE = 0, LIVE_BLOCKED = 1, LIVE_FINAL = 2;
+constexpr uint8_t LIVE_ST_CLOSED = 0, LIVE_ST_OPEN = 1, LIVE_ST_FINAL = 2;   // a state during the refinement
+
+// the processes enabled in a state: the whole row's, in the full graph — never those of the open subgraph alone
+MC_HD uint64_t live_enabled_in(uint32_t self, const uint32_t *dst, const int8_t *proc, uint64_t n, const uint32_t *scc) {
+    uint64_t en = 0, tk = 0;   // (tk: the steps that stay in the state's component of the open subgraph — not what closes a state)
+    live_state_masked(self, dst, proc, n, scc, [](uint32_t) { return true; }, &en, &tk);
+    return en;
+}
+// the strongly fair processes that keep the component from being fair: enabled somewhere in it, taken nowhere inside it
+MC_HD uint64_t live_blockers(uint64_t all, uint64_t strong, uint64_t enabled, uint64_t taken) {
+    return strong & all & enabled & ~taken;
+}
+MC_HD bool live_fair_strong(uint64_t all, uint64_t weak, uint64_t strong, uint64_t taken, uint64_t disabled, uint64_t enabled) {
+    return live_fair(all, weak, taken, disabled) && live_blockers(all, strong, enabled, taken) == 0;
+}
+MC_HD int live_classify(uint64_t all, uint64_t weak, uint64_t strong, uint64_t taken, uint64_t disabled, uint64_t enabled, bool has_target, uint32_t size) {
+    if (!live_violates_masked(all, weak, taken, disabled, has_target, size)) return LIVE_CLOSE;
+    return live_blockers(all, strong, enabled, taken) ? LIVE_BLOCKED : LIVE_FINAL;
+}
+MC_HD bool live_violates_strong(uint64_t all, uint64_t weak, uint64_t strong, uint64_t taken, uint64_t disabled, uint64_t enabled, bool has_target, uint32_t size) {
+    return live_classify(all, weak, strong, taken, disabled, enabled, has_target, size) == LIVE_FINAL;
+}
+// a state of a blocked component, with its own en mask: it is closed iff a blocker is enabled in it
+MC_HD bool live_closes_state(uint64_t blockers, uint64_t en) {
+    return (en & blockers) != 0;
+}
+// what an open state becomes once its component is classified
+MC_HD uint8_t live_refine_state(int cls, uint64_t blockers, uint64_t en) {
+    if (cls == LIVE_FINAL) return LIVE_ST_FINAL;
+    if (cls == LIVE_BLOCKED && !live_closes_state(blockers, en)) return LIVE_ST_OPEN;
+    return LIVE_ST_CLOSED;
+}
+// the rounds a refinement may take: every blocking round disables a strongly fair process for good
+MC_HD uint32_t live_strong_rounds(uint64_t all, uint64_t strong) {
+    uint32_t k = 1;
+    for (uint64_t f = strong & all; f; f &= f - 1) ++k;
+    return k;
 }
 
 }  // namespace mc

@@ -225,6 +225,9 @@ struct Program {
     // fairness (liveness.h): bit k = process instance k (the slot order: slot / maxch) is weakly fair
     unsigned long long fair_mask = 0;
     std::string live_refusal;             // "" = `Termination` can be checked on the state graph; else why not
+    // the same for the strong checks: the `fair+` instances among fair_mask's, and the refusal with `fair+` allowed
+    unsigned long long strong_mask = 0;
+    std::string live_refusal_strong;
     // the cfg's other temporal properties.  live_preds: the distinct state predicates they are made of, compiled after the
     // INVARIANTs and CONSTRAINTs into the same image but never run by the search (a table of their own: the entries are not in the header).
     // live_props: one entry per check — a quantifier instance of a conjunct of a named definition — or per refused name.

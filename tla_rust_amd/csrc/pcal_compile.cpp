@@ -1946,11 +1946,14 @@ struct Compiler {
                 if (!fair) continue;
                 if (k < 64) P.fair_mask |= 1ull << k;
                 const std::string who = insts[k].p->name.empty() ? std::string("the algorithm") : "process " + insts[k].p->name;
+                if (fair == 2 && k < 64) P.strong_mask |= 1ull << k;
+                const bool mods = insts[k].p->label_mods || has_mod(insts[k].p->body);
+                if (mods && P.live_refusal_strong.empty()) P.live_refusal_strong = who + " is fair and has a label with a `+` / `-` fairness modifier";
                 if (fair == 2 && P.live_refusal.empty()) P.live_refusal = who + " is `fair+` (strong fairness); only weak fairness is supported";
-                if ((insts[k].p->label_mods || has_mod(insts[k].p->body)) && P.live_refusal.empty()) P.live_refusal = who + " is fair and has a label with a `+` / `-` fairness modifier";
+                if (mods && P.live_refusal.empty()) P.live_refusal = who + " is fair and has a label with a `+` / `-` fairness modifier";
             }
-            if (m.had_procedures) P.live_refusal = "the algorithm has procedures (their actions get fairness conjuncts of their own)";
-            if (insts.size() > 64) P.live_refusal = "more than 64 process instances";
+            if (m.had_procedures) P.live_refusal = P.live_refusal_strong = "the algorithm has procedures (their actions get fairness conjuncts of their own)";
+            if (insts.size() > 64) P.live_refusal = P.live_refusal_strong = "more than 64 process instances";
         }
         // variables: globals, pc, process locals (the VARIABLES order of the translation)
         int nv = 0;
@@ -2145,7 +2148,7 @@ struct Compiler {
         // ---- the cfg's ACTION_CONSTRAINTs and VIEW
         cur_nv = nv;
         cfg_more();
-        if (!P.view.empty()) P.live_refusal = "the cfg has a VIEW (the graph is one of representative states: fairness over it is not the spec's)";
+        if (!P.view.empty()) P.live_refusal = P.live_refusal_strong = "the cfg has a VIEW (the graph is one of representative states: fairness over it is not the spec's)";
         // ---- header
         c[mc::VMH_MAGIC] = mc::VM_MAGIC;
         c[mc::VMH_NV] = nv;

@@ -17,6 +17,9 @@
 
 namespace mc {
 
+struct LiveCheck;      // liveness.h
+struct LiveCounters;   // engine_live.h
+
 // `count` elements for a graph array; the message names the call and the array
 template <class T>
 int graph_alloc(DevBuf<T> &b, size_t count, const char *what, const char *call = "mc_engine_graph") {
@@ -53,7 +56,7 @@ struct StateGraph {
         DevBuf<unsigned> done;      // [states] at a component's id: it holds a Done state
         mc_scc_info sinfo{};
         mc_live_info linfo{};
-        uint64_t fair = 0;
+        uint64_t fair = 0, strong = 0;   // of the last check: the weakly / strongly fair processes
         // what mc_engine_predicates / mc_engine_liveness_check add
         bool pred_built = false, proc_built = false;
         DevBuf<uint32_t> pred;      // [states] bit k = predicate k of the program's temporal properties holds in the state
@@ -64,11 +67,18 @@ struct StateGraph {
         int last_kind = -1, last_p = -1, last_q = -1;
         const Masked *last_mask = nullptr;     // its components (null: the full graph's)
         std::vector<uint32_t> descent;         // from the witness along falling dist to the first state of the component
+        // what mc_engine_liveness_strong / mc_engine_liveness_check_strong add
+        bool last_strong = false;              // the last check refined: its components are fscc's
+        DevBuf<unsigned long long> enabled;    // [states] at a component's id: the processes enabled in some state of it
+        DevBuf<uint8_t> open;                  // [states] LIVE_ST_*: closed, open or in a final component
+        DevBuf<uint32_t> fscc, fsize;          // [states] the refined ids (a closed state: its own index) and, at an id, the size
+        DevBuf<uint32_t> wscc, wsize;          // [states] the components of the open subgraph, rounds >= 2
         void release() {
             scc_built = checked = pred_built = proc_built = false;
             toff.reset(); tsrc.reset(); scc.reset(); size.reset(); proc.reset(); taken.reset(); disabled.reset(); done.reset();
             pred.reset(); dist.reset(); masks.clear(); descent.clear();
-            last_kind = -1; last_mask = nullptr;
+            enabled.reset(); open.reset(); fscc.reset(); fsize.reset(); wscc.reset(); wsize.reset();
+            last_kind = -1; last_mask = nullptr; last_strong = false; strong = 0;
         }
     } lv;
     void release() { built = false; offsets.reset(); dst.reset(); act.reset(); lv.release(); }
@@ -88,13 +98,22 @@ struct StateGraph {
     // the caller against the program's predicates)
     int live_check_masked(uint64_t all, uint64_t fair, int kind, int p, int q, hipStream_t stream, std::chrono::steady_clock::time_point started,
                           mc_live_check_info *out);
+    // mc_engine_liveness_strong (kind < 0: lout) / mc_engine_liveness_check_strong (cout), after the same preparation as the weak twins
+    int live_check_strong(uint64_t all, uint64_t weak, uint64_t strong, int kind, int p, int q, hipStream_t stream,
+                          std::chrono::steady_clock::time_point started, mc_live_info *lout, mc_live_check_info *cout, mc_live_strong_info *sout);
     int live_scc_read(uint64_t first, uint64_t count, uint32_t *scc_out);   // mc_engine_liveness_components
     int live_trace(const std::vector<uint64_t> &level_start, uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout);
 
 private:
     int scc_build(uint64_t n, hipStream_t stream);
     // trim + colouring over the transpose that is there; mask: the predicate whose states are left out (a component of their own each), -1 = none
-    int scc_components(uint64_t n, hipStream_t stream, int mask_q, DevBuf<uint32_t> &scc_buf, DevBuf<uint32_t> &size_buf, mc_scc_info &info);
+    // open: (rounds >= 2 of a strong check) only the states with LIVE_ST_OPEN there take part, in place of a predicate mask
+    int scc_components(uint64_t n, hipStream_t stream, int mask_q, DevBuf<uint32_t> &scc_buf, DevBuf<uint32_t> &size_buf, mc_scc_info &info,
+                       const uint8_t *open = nullptr);
+    int live_mask_components(int kind, int q, hipStream_t stream, const Live::Masked **mask_out, uint32_t *builds);
+    int live_reach_tail(const LiveCheck &ck, const uint32_t *scc, const uint32_t *size, const Live::Masked *mask, uint64_t fair, uint64_t strong,
+                        bool is_strong, uint32_t builds, const LiveCounters *d_lc, uint64_t strong_final, hipStream_t stream,
+                        std::chrono::steady_clock::time_point started, mc_live_check_info *out);
 };
 
 }  // namespace mc

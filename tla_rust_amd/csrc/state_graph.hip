@@ -94,7 +94,8 @@ int StateGraph::scc_build(uint64_t n, hipStream_t stream) {
     HIP_TRY(hipGetLastError());
     return scc_components(n, stream, -1, lv.scc, lv.size, lv.sinfo);
 }
-int StateGraph::scc_components(uint64_t n, hipStream_t stream, int mask_q, DevBuf<uint32_t> &scc_buf, DevBuf<uint32_t> &size_buf, mc_scc_info &info) {
+int StateGraph::scc_components(uint64_t n, hipStream_t stream, int mask_q, DevBuf<uint32_t> &scc_buf, DevBuf<uint32_t> &size_buf, mc_scc_info &info,
+                               const uint8_t *open) {
     DevBuf<unsigned> flag;
     DevBuf<LiveCounters> d_lc;
     int rc;
@@ -110,6 +111,7 @@ int StateGraph::scc_components(uint64_t n, hipStream_t stream, int mask_q, DevBu
     uint32_t *scc = scc_buf.p, *colour = size_buf.p;
     HIP_TRY(hipMemsetAsync(scc, 0xff, n * sizeof(uint32_t), stream));
     if (mask_q >= 0) live_launch(stream, k_scc_mask, n, (const uint32_t *)lv.pred.p, LiveCheck{LIVE_INF_OFTEN, -1, mask_q}, scc);
+    if (open) live_launch(stream, k_scc_open, n, open, scc);
     uint32_t trim_rounds = 0, colour_rounds = 0, back_rounds = 0, passes = 0;
     for (; n;) {
         if ((rc = live_fixed_point(stream, flag.p, trim_rounds, [&] { live_launch(stream, k_scc_trim, n, off, dst, toff, tsrc, scc, flag.p); }))) return rc;
@@ -191,6 +193,8 @@ int StateGraph::live_check(uint64_t all, uint64_t fair, hipStream_t stream, std:
     }
     lv.linfo.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count();
     lv.fair = fair;
+    lv.strong = 0;
+    lv.last_strong = false;
     lv.checked = true;
     lv.last_kind = -1;
     lv.last_mask = nullptr;
@@ -199,10 +203,10 @@ int StateGraph::live_check(uint64_t all, uint64_t fair, hipStream_t stream, std:
     return MC_OK;
 }
 int StateGraph::live_scc_read(uint64_t first, uint64_t count, uint32_t *scc_out) {
-    if (!built || !lv.checked || lv.last_kind < 0) { set_error("mc_engine_liveness_components: no property check (mc_engine_liveness_check runs one; the next search releases it)"); return MC_ESTATE; }
+    if (!built || !lv.checked || (lv.last_kind < 0 && !lv.last_strong)) { set_error("mc_engine_liveness_components: no property check (mc_engine_liveness_check runs one; the next search releases it)"); return MC_ESTATE; }
     if (first > info.states || count > info.states - first) { set_error("mc_engine_liveness_components: range beyond the graph's states"); return MC_EBADCFG; }
     HIP_TRY(hipSetDevice(device));
-    if (count) HIP_TRY(hipMemcpy(scc_out, (lv.last_mask ? lv.last_mask->scc.p : lv.scc.p) + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (count) HIP_TRY(hipMemcpy(scc_out, (lv.last_strong ? lv.fscc.p : lv.last_mask ? lv.last_mask->scc.p : lv.scc.p) + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return MC_OK;
 }
 int StateGraph::pred_read(uint64_t first, uint64_t count, uint32_t *bits_out) {
@@ -210,6 +214,26 @@ int StateGraph::pred_read(uint64_t first, uint64_t count, uint32_t *bits_out) {
     if (first > info.states || count > info.states - first) { set_error("mc_engine_predicates: range beyond the graph's states"); return MC_EBADCFG; }
     HIP_TRY(hipSetDevice(device));
     if (count) HIP_TRY(hipMemcpy(bits_out, lv.pred.p + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+// the components of G[M] for a property check: null (the full graph's) for <>[]P, else the build kept for the predicate that masks — made
+// and kept here when there is none
+int StateGraph::live_mask_components(int kind, int q, hipStream_t stream, const Live::Masked **mask_out, uint32_t *builds) {
+    const uint64_t n = info.states;
+    const Live::Masked *mask = nullptr;
+    if (kind != LIVE_STABLE) {
+        for (const auto &m : lv.masks) if (m->q == q) mask = m.get();
+        if (!mask) {
+            auto m = std::make_unique<Live::Masked>();
+            m->q = q;
+            mc_scc_info si;
+            if (int rc = scc_components(n, stream, q, m->scc, m->size, si)) return rc;
+            ++*builds;
+            mask = m.get();
+            lv.masks.push_back(std::move(m));
+        }
+    }
+    *mask_out = mask;
     return MC_OK;
 }
 // One (M, S, T) check over lv.pred: the components of G[M] (kept per mask), the rule per component, the reach pass, the witness; then,
@@ -224,37 +248,18 @@ int StateGraph::live_check_masked(uint64_t all, uint64_t fair, int kind, int p, 
     lv.checked = false;
     // ---- the components of G[M]: the full graph's for <>[]P, else one build per predicate that masks
     const Live::Masked *mask = nullptr;
-    if (kind != LIVE_STABLE) {
-        for (const auto &m : lv.masks) if (m->q == q) mask = m.get();
-        if (!mask) {
-            auto m = std::make_unique<Live::Masked>();
-            m->q = q;
-            mc_scc_info si;
-            if ((rc = scc_components(n, stream, q, m->scc, m->size, si))) return rc;
-            ++builds;
-            mask = m.get();
-            lv.masks.push_back(std::move(m));
-        }
-    }
+    if ((rc = live_mask_components(kind, q, stream, &mask, &builds))) return rc;
     const uint32_t *scc = mask ? mask->scc.p : lv.scc.p, *size = mask ? mask->size.p : lv.size.p, *pred = lv.pred.p;
     DevBuf<LiveCounters> d_lc;
-    DevBuf<LiveCheckCounters> d_cc;
-    DevBuf<unsigned> flag;
     if ((rc = graph_alloc(lv.taken, n, "the components' taken masks", call))) return rc;
     if ((rc = graph_alloc(lv.disabled, n, "the components' disabled masks", call))) return rc;
     if ((rc = graph_alloc(lv.done, n, "the components' target flags", call))) return rc;
     if ((rc = graph_alloc(lv.dist, n, "the distances", call))) return rc;
     if ((rc = graph_alloc(d_lc, 1, "the counters", call))) return rc;
-    if ((rc = graph_alloc(d_cc, 1, "the counters", call))) return rc;
-    if ((rc = graph_alloc(flag, 1, "the fixed-point flag", call))) return rc;
     LiveCounters lc;
     memset(&lc, 0, sizeof lc);
     lc.first_root = ~0u;
-    LiveCheckCounters cc;
-    memset(&cc, 0, sizeof cc);
-    cc.witness = ~0u;
     HIP_TRY(hipMemcpyAsync(d_lc, &lc, sizeof lc, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_cc, &cc, sizeof cc, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(lv.taken, 0, (n ? n : 1) * sizeof(unsigned long long), stream));
     HIP_TRY(hipMemsetAsync(lv.disabled, 0, (n ? n : 1) * sizeof(unsigned long long), stream));
     HIP_TRY(hipMemsetAsync(lv.done, 0, (n ? n : 1) * sizeof(unsigned), stream));
@@ -264,19 +269,41 @@ int StateGraph::live_check_masked(uint64_t all, uint64_t fair, int kind, int p, 
                 (const unsigned *)lv.done.p, all, fair, d_lc.p, pred, ck, lv.dist.p);
     live_launch(stream, k_live_reach_init, n, scc, pred, ck, lv.dist.p);
     HIP_TRY(hipGetLastError());
+    return live_reach_tail(ck, scc, size, mask, fair, 0, false, builds, d_lc.p, 0, stream, started, out);
+}
+// What a property check does once dist[] is 0 on the states of the violating components and LIVE_FAR elsewhere: the reach pass, the
+// witness, the counters, and — when violated — the descent from the witness.  scc / size: the ids and sizes the descent's component is
+// read from (a strong check: the refined ones; fair_components is then the caller's count, d_lc is not read).
+int StateGraph::live_reach_tail(const LiveCheck &ck, const uint32_t *scc, const uint32_t *size, const Live::Masked *mask, uint64_t fair, uint64_t strong,
+                                bool is_strong, uint32_t builds, const LiveCounters *d_lc, uint64_t strong_final, hipStream_t stream,
+                                std::chrono::steady_clock::time_point started, mc_live_check_info *out) {
+    const uint64_t n = info.states;
+    const int kind = ck.kind, p = ck.p, q = ck.q;
+    const uint32_t *pred = lv.pred.p;
+    DevBuf<LiveCheckCounters> d_cc;
+    DevBuf<unsigned> flag;
+    int rc;
+    if ((rc = graph_alloc(d_cc, 1, "the counters", "mc_engine_liveness_check"))) return rc;
+    if ((rc = graph_alloc(flag, 1, "the fixed-point flag", "mc_engine_liveness_check"))) return rc;
+    LiveCounters lc;
+    memset(&lc, 0, sizeof lc);
+    LiveCheckCounters cc;
+    memset(&cc, 0, sizeof cc);
+    cc.witness = ~0u;
+    HIP_TRY(hipMemcpyAsync(d_cc, &cc, sizeof cc, hipMemcpyHostToDevice, stream));
     uint32_t sweeps = 0;
     if (n && (rc = live_fixed_point(stream, flag.p, sweeps, [&] { live_launch(stream, k_live_reach, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, pred, ck, lv.dist.p, flag.p); },
                                     n + SCC_BATCH, "mc_engine_liveness_check: the reach pass")))
         return rc;
     live_launch(stream, k_live_witness, n, pred, ck, (const uint32_t *)lv.dist.p, (uint64_t)info.init_states, d_cc.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&lc, d_lc, sizeof lc, hipMemcpyDeviceToHost, stream));
+    if (d_lc) HIP_TRY(hipMemcpyAsync(&lc, d_lc, sizeof lc, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipMemcpyAsync(&cc, d_cc, sizeof cc, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     memset(out, 0, sizeof *out);
     out->violated = cc.bad_starts ? 1 : 0;
     out->sweeps = sweeps;
-    out->fair_components = lc.fair_components;
+    out->fair_components = d_lc ? lc.fair_components : strong_final;
     out->mask_states = cc.mask_states;
     out->bad_starts = cc.bad_starts;
     out->scc_builds = builds;
@@ -315,11 +342,118 @@ int StateGraph::live_check_masked(uint64_t all, uint64_t fair, int kind, int p, 
     lv.linfo.root_size = out->root_size;
     lv.linfo.seconds = out->seconds;
     lv.fair = fair;
+    lv.strong = strong;
+    lv.last_strong = is_strong;
     lv.last_kind = kind;
     lv.last_p = p;
     lv.last_q = q;
     lv.last_mask = mask;
     lv.checked = true;
+    return MC_OK;
+}
+// A check under strong fairness of the processes of `strong`: liveness.h's refinement, one round per loop.  kind < 0:
+// Termination (M = all, T = not Done; lout), else the (M, S, T) check of live_check_masked (cout).  Round 1 runs on the components a
+// weak check of the same M uses — lv.scc, or the mask's build, made and kept here as live_check_masked does —, later rounds on builds of
+// the open subgraph into lv.wscc / lv.wsize; nothing a weak check reads is written.  One blocking read per round beside the build's.
+int StateGraph::live_check_strong(uint64_t all, uint64_t weak, uint64_t strong, int kind, int p, int q, hipStream_t stream,
+                                  std::chrono::steady_clock::time_point started, mc_live_info *lout, mc_live_check_info *cout, mc_live_strong_info *sout) {
+    const uint64_t n = info.states, cells = n ? n : 1;
+    const bool term = kind < 0;
+    const LiveCheck ck{term ? LIVE_STABLE : kind, p, q};   // (Termination: every state is in M; the target is the Done flag's, not a predicate's)
+    const char *call = term ? "mc_engine_liveness_strong" : "mc_engine_liveness_check_strong";
+    int rc;
+    uint32_t builds = 0;
+    lv.checked = false;
+    const Live::Masked *mask = nullptr;
+    if (!term && (rc = live_mask_components(kind, q, stream, &mask, &builds))) return rc;
+    const uint32_t *pred = term ? nullptr : lv.pred.p;
+    DevBuf<LiveStrongCounters> d_sc;
+    if ((rc = graph_alloc(lv.taken, n, "the components' taken masks", call))) return rc;
+    if ((rc = graph_alloc(lv.disabled, n, "the components' disabled masks", call))) return rc;
+    if ((rc = graph_alloc(lv.done, n, "the components' target flags", call))) return rc;
+    if ((rc = graph_alloc(lv.enabled, n, "the components' enabled masks", call))) return rc;
+    if ((rc = graph_alloc(lv.open, n, "the open states", call))) return rc;
+    if ((rc = graph_alloc(lv.fscc, n, "the refined component ids", call))) return rc;
+    if ((rc = graph_alloc(lv.fsize, n, "the refined components' sizes", call))) return rc;
+    if (!term && (rc = graph_alloc(lv.dist, n, "the distances", call))) return rc;
+    if ((rc = graph_alloc(d_sc, 1, "the counters", call))) return rc;
+    LiveStrongCounters sc;
+    memset(&sc, 0, sizeof sc);
+    sc.first_root = ~0u;
+    HIP_TRY(hipMemcpyAsync(d_sc, &sc, sizeof sc, hipMemcpyHostToDevice, stream));
+    if (!term) HIP_TRY(hipMemsetAsync(lv.dist, 0xff, cells * sizeof(uint32_t), stream));   // (LIVE_FAR; k_live_refine puts 0 on the final components)
+    if (term) live_launch(stream, k_live_open_init<false>, n, pred, ck, lv.open.p, lv.fscc.p, lv.fsize.p);
+    else live_launch(stream, k_live_open_init<true>, n, pred, ck, lv.open.p, lv.fscc.p, lv.fsize.p);
+    const uint32_t *scc = mask ? mask->scc.p : lv.scc.p, *size = mask ? mask->size.p : lv.size.p;
+    const uint32_t bound = live_strong_rounds(all, strong);
+    uint32_t rounds = 0, strong_builds = 0;
+    for (;;) {
+        ++rounds;
+        HIP_TRY(hipMemsetAsync(lv.taken, 0, cells * sizeof(unsigned long long), stream));
+        HIP_TRY(hipMemsetAsync(lv.disabled, 0, cells * sizeof(unsigned long long), stream));
+        HIP_TRY(hipMemsetAsync(lv.done, 0, cells * sizeof(unsigned), stream));
+        HIP_TRY(hipMemsetAsync(lv.enabled, 0, cells * sizeof(unsigned long long), stream));
+        HIP_TRY(hipMemsetAsync(&d_sc.p->open, 0, sizeof(unsigned), stream));
+        if (term)
+            live_launch(stream, k_live_reduce<false>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, (const int8_t *)lv.proc.p, scc, size, all,
+                        lv.taken.p, lv.disabled.p, lv.done.p, pred, ck);
+        else
+            live_launch(stream, k_live_reduce<true>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, (const int8_t *)lv.proc.p, scc, size, all,
+                        lv.taken.p, lv.disabled.p, lv.done.p, pred, ck);
+        live_launch(stream, k_live_enabled, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, (const int8_t *)lv.proc.p, scc, size,
+                    (const uint8_t *)lv.open.p, lv.enabled.p);
+        live_launch(stream, k_live_classify, n, scc, size, (const uint8_t *)lv.open.p, (const unsigned long long *)lv.taken.p,
+                    (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p, (const unsigned long long *)lv.enabled.p, all, weak, strong, term,
+                    d_sc.p);
+        live_launch(stream, k_live_refine, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, (const int8_t *)lv.proc.p, scc, size,
+                    (const unsigned long long *)lv.taken.p, (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p,
+                    (const unsigned long long *)lv.enabled.p, all, weak, strong, term, lv.open.p, lv.fscc.p, lv.fsize.p, term ? (uint32_t *)nullptr : lv.dist.p,
+                    d_sc.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&sc, d_sc, sizeof sc, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (!sc.open) break;
+        if (rounds >= bound) {
+            set_error(std::string(call) + ": the refinement did not converge after " + std::to_string(rounds) + " rounds (" + std::to_string(bound - 1) +
+                      " strongly fair processes)");
+            return MC_ESTATE;
+        }
+        mc_scc_info si;
+        if ((rc = scc_components(n, stream, -1, lv.wscc, lv.wsize, si, lv.open.p))) return rc;
+        ++strong_builds;
+        scc = lv.wscc.p;
+        size = lv.wsize.p;
+    }
+    memset(sout, 0, sizeof *sout);
+    sout->rounds = rounds;
+    sout->scc_builds = strong_builds;
+    sout->closed_states = sc.closed;
+    sout->final_components = sc.final_components;
+    if (term) {
+        memset(&lv.linfo, 0, sizeof lv.linfo);
+        lv.linfo.violated = sc.final_components ? 1 : 0;
+        lv.linfo.fair_components = sc.final_components;
+        if (sc.final_components) {
+            uint32_t sz = 0;
+            HIP_TRY(hipMemcpy(&sz, lv.fsize.p + sc.first_root, sizeof sz, hipMemcpyDeviceToHost));
+            lv.linfo.root = sc.first_root;
+            lv.linfo.root_size = sz;
+        }
+        lv.linfo.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count();
+        lv.fair = weak;
+        lv.strong = strong;
+        lv.last_strong = true;
+        lv.checked = true;
+        lv.last_kind = -1;
+        lv.last_mask = nullptr;
+        lv.descent.clear();
+        *lout = lv.linfo;
+        sout->seconds = lv.linfo.seconds;
+        return MC_OK;
+    }
+    if ((rc = live_reach_tail(LiveCheck{kind, p, q}, lv.fscc.p, lv.fsize.p, mask, weak, strong, true, builds, nullptr, sc.final_components, stream, started, cout)))
+        return rc;
+    sout->seconds = cout->seconds;
     return MC_OK;
 }
 // The counterexample of the last mc_engine_liveness, built on the host from the arrays (deterministic given them).
@@ -359,7 +493,7 @@ int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *p
     std::vector<uint32_t> dst((size_t)edges), scc((size_t)n);
     std::vector<int8_t> proc((size_t)edges);
     HIP_TRY(hipMemcpy(off.data(), offsets.p, off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(scc.data(), prop && lv.last_mask ? lv.last_mask->scc.p : lv.scc.p, scc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(scc.data(), lv.last_strong ? lv.fscc.p : prop && lv.last_mask ? lv.last_mask->scc.p : lv.scc.p, scc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (edges) {
         HIP_TRY(hipMemcpy(dst.data(), this->dst.p, dst.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(proc.data(), lv.proc.p, proc.size() * sizeof(int8_t), hipMemcpyDeviceToHost));
@@ -388,7 +522,8 @@ int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *p
     };
     bool ok = true;
     for (int p = 0; p < 64 && ok; ++p) {
-        if (!(lv.fair >> p & 1)) continue;
+        if (!((lv.fair | lv.strong) >> p & 1)) continue;
+        const bool sf = lv.strong >> p & 1;   // strongly fair: taken inside, or — the refinement saw to it — disabled everywhere in the component
         bool found = false;
         for (size_t mi = 0; mi < members.size() && !found; ++mi) {   // a real step of p inside the component: the first in index order
             const uint32_t u = members[mi];
@@ -399,6 +534,7 @@ int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *p
                     cycle.push_back(dst[(size_t)k]);
                 }
         }
+        if (sf) found = true;
         for (size_t mi = 0; mi < members.size() && !found; ++mi) {   // else a state where p is disabled
             const uint32_t u = members[mi];
             uint64_t en = 0, tk = 0;
