@@ -444,6 +444,9 @@ int mc_engine_debug_phases(mc_engine *e, uint64_t *out48, int reset);
 /* profiling only: set / clear bits of the engine's flags between two calls (the A/B and ablation bits a kernel reads at run time) — e.g. run
  * to a level normally, then time ONE more level (mc_engine_step) with an ablation bit on.  Never changes what a run without the bits computes. */
 int mc_engine_debug_flags(mc_engine *e, uint32_t set, uint32_t clear);
+/* read-only: the form of the engine's seen-set — its buckets and the slots of one (8, or 4 where the table is so much larger than the arena
+ * that it can never be more than a third full); buckets * slots = table_capacity rounded up to whole 64-slot groups */
+int mc_engine_seen_layout(mc_engine *e, uint64_t *buckets, uint32_t *slots);
 void mc_engine_destroy(mc_engine *e);
 
 /* ------------------------------------------------------------------ sharded (multi-GPU) step API

@@ -572,6 +572,15 @@ class Engine:
         L.mc_engine_debug_flags.restype = C.c_int
         _check(L.mc_engine_debug_flags(self._h, set, clear), "mc_engine_debug_flags")
 
+    def seen_layout(self):
+        """mc_engine_seen_layout: (buckets, slots per bucket) of the engine's seen-set"""
+        L = lib()
+        L.mc_engine_seen_layout.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        L.mc_engine_seen_layout.restype = C.c_int
+        b, s = C.c_uint64(0), C.c_uint32(0)
+        _check(L.mc_engine_seen_layout(self._h, C.byref(b), C.byref(s)), "mc_engine_seen_layout")
+        return b.value, s.value
+
     def kernel_stats(self):
         ks = KernelStats()
         _check(lib().mc_engine_kernel_stats(self._h, C.byref(ks)), "mc_engine_kernel_stats")
