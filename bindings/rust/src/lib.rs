@@ -18,6 +18,7 @@ pub const MC_F_TRACE: u32 = 2;
 pub const MC_F_JIT: u32 = 262144; // MC_SPEC_PCAL: the compiled program as generated code, built for the device when the engine is created
 pub const MC_DOT_ACTIONLABELS: u32 = 1; // mc_check_files_dot: the action name on every edge
 pub const MC_DOT_COLORIZE: u32 = 2;     // ... and a colour per action, with a legend
+pub const MC_F_CONTINUE: u32 = 67108864; // TLC's -continue: search on past violated invariants and deadlocks (mc_engine_violations); implies MC_F_TRACE, one-GPU engines only
 pub const MC_F_COVERAGE: u32 = 16777216; // TLC's -coverage: per-action counts (mc_engine_coverage); implies MC_F_TRACE, one-GPU engines only
 pub const MC_MAX_LEVELS: usize = 4096;
 
@@ -55,6 +56,14 @@ pub struct mc_sim_result {
 // one entry of mc_engine_coverage: action id (-1 = Init), the states it was first to find, the successors it generated
 #[repr(C)]
 pub struct mc_action_coverage { pub action: i32, pub pad: u32, pub distinct: u64, pub generated: u64 }
+// one entry of mc_engine_violations (an engine created with MC_F_CONTINUE): per INVARIANT index, then deadlock, then the fatal error; 40 bytes.
+// first_state = u64::MAX: nothing found
+#[repr(C)]
+pub struct mc_violation {
+    pub kind: i32, pub invariant: i32, pub states: u64, pub outside: u64, pub first_state: u64, pub first_level: u32, pub trace_len: u32,
+}
+#[repr(C)]
+pub struct mc_violations_info { pub flagged_levels: u32, pub passes: u32, pub fatal: u32, pub pad: u32 } // fatal = 1: the last entry ended the search
 // what mc_engine_graph built: the state graph of the last search in CSR form (rows by arena index); 64 bytes
 #[repr(C)]
 pub struct mc_graph_info {
@@ -84,6 +93,10 @@ extern "C" {
     pub fn mc_engine_trace(e: *mut mc_engine, states: *mut u8, actions: *mut i32, n_inout: *mut usize) -> c_int;
     // entries for Init and every action of the model, in action-id order; *n_inout: capacity in, count out
     pub fn mc_engine_coverage(e: *mut mc_engine, out: *mut mc_action_coverage, n_inout: *mut usize) -> c_int;
+    // everything a search under MC_F_CONTINUE found; violation_trace: mc_engine_trace's contract for entry k
+    pub fn mc_engine_violations(e: *mut mc_engine, info: *mut mc_violations_info, out: *mut mc_violation, n_inout: *mut usize) -> c_int;
+    pub fn mc_engine_violation_trace(e: *mut mc_engine, k: usize, states: *mut u8, actions: *mut i32, n_inout: *mut usize) -> c_int;
+    pub fn mc_invariant_name(spec: *const mc_spec_desc, index: c_int) -> *const c_char;
     // the state graph, built on the device after a search and kept until the next one; graph_read: the rows of states
     // [first, first + count): count + 1 offsets relative to the first, *nedges_inout capacity in / edges out
     pub fn mc_engine_graph(e: *mut mc_engine, out: *mut mc_graph_info) -> c_int;

@@ -125,6 +125,11 @@ typedef struct {
                              was first to find (mc_engine_coverage below; mc_check_files appends "The coverage statistics" to its
                              report).  Implies MC_F_TRACE.  One-GPU engines only: mc_engine_create refuses it with shard_count > 1.
                              (Bits 19 - 23 are the kernels' own: engine_kernels.h.)  Without it nothing is launched or allocated for it. */
+#define MC_F_CONTINUE 67108864u /* TLC's -continue: a violated INVARIANT and a deadlock (MC_F_DEADLOCK) no longer end the search; a failed
+                             Assert, an evaluation error and every device error still end it at the end of their level.  mc_result's
+                             verdict, violated_invariant and trace_len, and mc_engine_trace, stay those of the FIRST flagged level;
+                             mc_engine_violations below lists everything found.  Implies MC_F_TRACE.  One-GPU engines only:
+                             mc_engine_create refuses it with shard_count > 1.  Without it nothing is launched or allocated for it. */
 
 typedef struct {
     int32_t device;          /* HIP device ordinal                                              */
@@ -224,6 +229,50 @@ typedef struct {
     uint64_t distinct, generated;
 } mc_action_coverage;
 int mc_engine_coverage(mc_engine *e, mc_action_coverage *out, size_t *n_inout);
+
+/* ------------------------------------------------------------------ every violation of a search (TLC's `-continue`)
+ * An engine created with MC_F_CONTINUE searches on past violated invariants and deadlocks and collects, per flagged BFS level (two
+ * passes over that level alone; a level without a violation costs nothing):
+ *   one entry per INVARIANT index of the model, in index order, zero rows included (mc_invariant_name names them);
+ *   then one entry for deadlock when MC_F_DEADLOCK is set;
+ *   then one entry for the fatal error — a failed Assert, an evaluation error — if one ended the run.
+ * states       distinct STORED states: those whose FIRST violated invariant is this one (a state is listed under one invariant only, as
+ *              TLC lists it), or the deadlocked states; each state once, however many parents generated it.
+ * outside      violating successors that are not stored (outside the CONSTRAINT, refused by an ACTION_CONSTRAINT), counted per
+ *              generation; always 0 for a lowering that checks stored states.  The fatal entry: the failing (state, action) pairs
+ *              of the level that ended the run.
+ * first_state  arena index of the first violator (the arena is in level order: a state of the earliest level; mc_engine_read_states
+ *              reads it), first_level its BFS level (1-based), trace_len the states of mc_engine_violation_trace.  An entry with
+ *              states == 0 && outside > 0, and the fatal entry: the state that was being expanded.  UINT64_MAX / 0 / 0: nothing found.
+ * mc_result's counters describe the search as far as it went: the complete graph when nothing fatal happened.
+ * Two limits.  The PROPERTY of the Paxos family (MC_SPEC_PAXOS) is a property of a step, not of a state: it has
+ * no row among the invariant entries; a step that breaks it ends the search and is the fatal entry (kind MC_V_INVARIANT, its index).
+ * The snapshot-isolation lowering (MC_SPEC_SSI) evaluates, per stored state, the invariants its last step can have changed, which is
+ * exact while every ancestor satisfied them: past a violator, a descendant that still breaks the same history invariant without
+ * touching it again is not counted, so `states` of those invariants can be below TLC's count under -continue.  Its `find` predicate
+ * and lock invariants are evaluated on every state.
+ * mc_engine_violations: *n_inout capacity in, count out (MC_EBADCFG with the count when the buffer is too small).  MC_ESTATE on an
+ * engine created without MC_F_CONTINUE.
+ * mc_engine_violation_trace: mc_engine_trace's contract for entry k: the parent chain that ends in first_state; where the violator is
+ * not stored (states == 0 && outside > 0) the chain of the smallest (parent, action slot) plus the successor rebuilt from it.
+ * MC_ESTATE without the flag; MC_EBADCFG for k out of range or an entry with nothing to show. */
+typedef struct {
+    int32_t kind;             /* MC_V_INVARIANT, MC_V_DEADLOCK, or the fatal error's MC_V_ASSERT / MC_V_SPECERR / MC_V_INVARIANT     */
+    int32_t invariant;        /* the index, or -1                                                           */
+    uint64_t states, outside;
+    uint64_t first_state;
+    uint32_t first_level, trace_len;
+} mc_violation;
+typedef struct {
+    uint32_t flagged_levels;  /* BFS levels (Init = level 1 included) after which a violation key was set  */
+    uint32_t passes;          /* launches of the two kernels of engine_violations.h                        */
+    uint32_t fatal;           /* 1: the LAST entry is the fatal error that ended the search                */
+    uint32_t pad;
+} mc_violations_info;
+int mc_engine_violations(mc_engine *e, mc_violations_info *info, mc_violation *out, size_t *n_inout);
+int mc_engine_violation_trace(mc_engine *e, size_t k, uint8_t *states_out, int32_t *actions_out, size_t *n_inout);
+/* the name of INVARIANT `index` of a spec, as the reports print it ("?" when there is none) */
+const char *mc_invariant_name(const mc_spec_desc *spec, int index);
 
 /* ------------------------------------------------------------------ the state graph (TLC's `-dump dot`)
  * After a search the engine knows every state it found; mc_engine_graph adds how they connect: the edge list of the reachable graph in

@@ -12,6 +12,7 @@ MC_MAX_LEVELS = 4096
 SPEC_IDS = {"atomic_add": 1, "pcal_intro": 2, "raft": 3, "ssi": 4, "pcal": 5, "paxos": 6}
 VERDICTS = ["ok", "invariant", "assert", "deadlock", "spec-error", "budget", "assume", "liveness"]
 MC_F_DEADLOCK, MC_F_TRACE, MC_F_TIMING, MC_F_MATRIX, MC_F_NOPROBE, MC_F_NOFAMILY = 1, 2, 4, 8, 16, 32
+MC_F_CONTINUE = 1 << 26  # TLC's -continue: search on past violations (Engine(keep_going=True), Engine.violations(); include/tlamc.h)
 MC_F_COVERAGE = 1 << 24  # TLC's -coverage: per-action counts (Engine(coverage=True), Engine.coverage(); include/tlamc.h)
 MC_F_UNVERIFIED = 512  # use the built-in lowering even when the module a wrapper EXTENDS cannot be found (include/tlamc.h)
 
@@ -90,6 +91,17 @@ class Transport(C.Structure):
 class ActionCoverage(C.Structure):
     """mc_action_coverage"""
     _fields_ = [("action", C.c_int32), ("pad", C.c_uint32), ("distinct", C.c_uint64), ("generated", C.c_uint64)]
+
+
+class Violation(C.Structure):
+    """mc_violation"""
+    _fields_ = [("kind", C.c_int32), ("invariant", C.c_int32), ("states", C.c_uint64), ("outside", C.c_uint64), ("first_state", C.c_uint64),
+                ("first_level", C.c_uint32), ("trace_len", C.c_uint32)]
+
+
+class ViolationsInfo(C.Structure):
+    """mc_violations_info"""
+    _fields_ = [("flagged_levels", C.c_uint32), ("passes", C.c_uint32), ("fatal", C.c_uint32), ("pad", C.c_uint32)]
 
 
 class GraphInfo(C.Structure):
@@ -184,6 +196,10 @@ def lib():
     L.mc_engine_trace.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]
     L.mc_engine_kernel_stats.argtypes = [C.c_void_p, C.POINTER(KernelStats)]
     L.mc_engine_coverage.argtypes = [C.c_void_p, C.POINTER(ActionCoverage), C.POINTER(C.c_size_t)]
+    L.mc_engine_violations.argtypes = [C.c_void_p, C.POINTER(ViolationsInfo), C.POINTER(Violation), C.POINTER(C.c_size_t)]
+    L.mc_engine_violation_trace.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]
+    L.mc_invariant_name.argtypes = [C.POINTER(SpecDesc), C.c_int]
+    L.mc_invariant_name.restype = C.c_char_p
     L.mc_engine_graph.argtypes = [C.c_void_p, C.POINTER(GraphInfo)]
     L.mc_engine_graph_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
     L.mc_engine_scc.argtypes = [C.c_void_p, C.POINTER(SccInfo)]
@@ -350,12 +366,13 @@ class Engine:
 
     def __init__(self, spec, params, device=0, table_capacity=0, arena_capacity=0, chunk_states=0, max_levels=0,
                  max_distinct=0, deadlock=True, trace=True, timing=False, matrix=False, shard_rank=0, shard_count=1, debug_flags=0, jit=False,
-                 coverage=False):
+                 coverage=False, keep_going=False):
         self.spec, self.params = spec, list(params)
         self.desc = spec_desc(spec, params)
         # jit (MC_SPEC_PCAL): MC_F_JIT — the compiled program as generated code, built for the device when the engine is created
         flags = (MC_F_DEADLOCK if deadlock else 0) | (MC_F_TRACE if trace else 0) | (MC_F_TIMING if timing else 0) | \
-            (MC_F_MATRIX if matrix else 0) | (262144 if jit else 0) | (MC_F_COVERAGE if coverage else 0) | debug_flags
+            (MC_F_MATRIX if matrix else 0) | (262144 if jit else 0) | (MC_F_COVERAGE if coverage else 0) | \
+            (MC_F_CONTINUE if keep_going else 0) | debug_flags
         self.cfg = Config(device, flags, table_capacity, arena_capacity, chunk_states, max_levels, max_distinct,
                           shard_rank, shard_count)
         self._h = C.c_void_p()
@@ -403,6 +420,41 @@ class Engine:
         _check(lib().mc_engine_coverage(self._h, rows, C.byref(n)), "mc_engine_coverage")
         return {("Init" if r.action < 0 else lib().mc_action_name(C.byref(self.desc), r.action).decode()): (int(r.distinct), int(r.generated))
                 for r in rows[:n.value]}
+
+    def violations(self):
+        """mc_engine_violations (TLC's -continue; an engine created with keep_going=True): a list of dicts, one per INVARIANT of the
+        model in index order (zero rows included), then one for deadlock when it is checked, then the fatal error that ended the
+        search, if any: kind (a verdict name), invariant (index or -1), name (the invariant's, "Deadlock", or the verdict name),
+        states, outside, first_state (None: nothing found), first_level, trace_len.  The list carries .flagged_levels and .passes."""
+        n, info = C.c_size_t(0), ViolationsInfo()
+        rc = lib().mc_engine_violations(self._h, C.byref(info), None, C.byref(n))
+        if rc != -1:   # (MC_EBADCFG + the count is the answer to a buffer of no entries)
+            _check(rc, "mc_engine_violations")
+        rows = (Violation * max(1, n.value))()
+        if n.value:
+            _check(lib().mc_engine_violations(self._h, C.byref(info), rows, C.byref(n)), "mc_engine_violations")
+
+        class Violations(list):
+            pass
+        out = Violations()
+        out.flagged_levels, out.passes = int(info.flagged_levels), int(info.passes)
+        for k, r in enumerate(rows[:n.value]):
+            name = lib().mc_invariant_name(C.byref(self.desc), r.invariant).decode() if r.invariant >= 0 else \
+                "Deadlock" if VERDICTS[r.kind] == "deadlock" else VERDICTS[r.kind]
+            out.append(Result(kind=VERDICTS[r.kind], invariant=int(r.invariant), name=name, states=int(r.states), outside=int(r.outside),
+                              first_state=None if r.first_state == 2 ** 64 - 1 else int(r.first_state), first_level=int(r.first_level),
+                              trace_len=int(r.trace_len), fatal=bool(info.fatal) and k + 1 == n.value))
+        return out
+
+    def violation_trace(self, k):
+        """mc_engine_violation_trace: [(action name, state text)] of the shortest behaviour to entry k of violations()"""
+        W = lib().mc_state_bytes(C.byref(self.desc))
+        cap = C.c_size_t(4096)
+        states = C.create_string_buffer(W * cap.value)
+        acts = (C.c_int32 * cap.value)()
+        _check(lib().mc_engine_violation_trace(self._h, k, states, acts, C.byref(cap)), "mc_engine_violation_trace")
+        return [(lib().mc_action_name(C.byref(self.desc), acts[i]).decode(), state_format(self.spec, self.params, states.raw[i * W:(i + 1) * W]))
+                for i in range(cap.value)]
 
     def graph_info(self):
         """mc_engine_graph: build the state graph of the last search on the device (it stays there until the next search) and return
@@ -887,8 +939,9 @@ class ResolvedSpec:
 
 
 def check_files(tla_path, cfg_path=None, device=0, **kw):
-    """`tlc X.tla` end to end (reference Makefile:6-7): returns (Result, report text)."""
-    cfg = Config(device, MC_F_DEADLOCK | MC_F_TRACE | (MC_F_UNVERIFIED if kw.get("unverified") else 0), kw.get("table_capacity", 0), kw.get("arena_capacity", 0),
+    """`tlc X.tla` end to end (reference Makefile:6-7): returns (Result, report text).  keep_going=True: `-continue` (MC_F_CONTINUE)."""
+    cfg = Config(device, MC_F_DEADLOCK | MC_F_TRACE | (MC_F_UNVERIFIED if kw.get("unverified") else 0) | (MC_F_CONTINUE if kw.get("keep_going") else 0),
+                 kw.get("table_capacity", 0), kw.get("arena_capacity", 0),
                  kw.get("chunk_states", 0), kw.get("max_levels", 0), kw.get("max_distinct", 0), 0, 1)
     r = CResult()
     buf = C.create_string_buffer(1 << 20)

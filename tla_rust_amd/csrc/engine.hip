@@ -49,6 +49,7 @@ namespace mc {
 #include "engine_pairs.h"     // k_expand_pairs: the by-pairs expand + insert + write kernel (specs with S::PAIR_FAMILIES)
 #include "engine_sim.h"       // k_simulate: simulation mode, one lane per random walk (mc_engine_simulate)
 #include "engine_coverage.h"  // k_coverage_generated / k_coverage_distinct: per-action counts (MC_F_COVERAGE, mc_engine_coverage)
+#include "engine_violations.h"  // k_viol_stored / k_viol_frontier: what a flagged level holds (MC_F_CONTINUE, mc_engine_violations)
 #include "engine_graph.h"     // k_graph_index / k_graph_degree / k_graph_fill / k_live_proc: the state graph in CSR form (mc_engine_graph)
 #include "state_graph.h"      // StateGraph: what consumes that form (reads, mc_engine_scc, mc_engine_liveness), and the device scans; compiled once
 namespace mc {
@@ -110,6 +111,8 @@ struct EngineBase {
     virtual size_t state_bytes() const = 0;
     virtual int simulate(const mc_sim_opts *opts, mc_sim_result *out) = 0;
     virtual int coverage(mc_action_coverage *out, size_t *n_inout) = 0;
+    virtual int violations(mc_violations_info *info, mc_violation *out, size_t *n_inout) = 0;
+    virtual int violation_trace(size_t k, uint8_t *states_out, int32_t *actions_out, size_t *n_inout) = 0;
     // ---- the state graph (state_graph.h).  The two calls that walk the arena with the lowering's kernels are the engine's; the rest
     // consumes the CSR arrays and is the StateGraph's.  Engine<S>::alloc says where the graph's engine keeps what those calls need.
     StateGraph gr;
@@ -343,6 +346,15 @@ struct Engine : EngineBase {
         std::vector<uint64_t> host;        // the bins as the last run left them (+ Init's generated, which no kernel counts)
         uint64_t init_generated = 0;
     } cov;
+    // ---- -continue (MC_F_CONTINUE, mc_engine_violations): what the flagged levels of the last search held
+    struct Vio {
+        bool on = false;
+        DevBuf<ViolBins> bins;             // bumped by the kernels of engine_violations.h
+        ViolBins host;                     // ... as the last flagged level left them
+        bool have_first = false, fatal = false;
+        unsigned long long first_key = ~0ull;   // DevCounters::viol_key of the first flagged level: what the run reports
+        uint32_t flagged_levels = 0, passes = 0;
+    } vio;
 
     // slot slices of a generic-kernel launch (k_expand_insert): as many as it takes to give the device a few thousand wavefronts,
     // for specs whose slots all go through the loop (no unrolled prefix) and that have enough of them; TLAMC_NOSLICE=1 = A/B
@@ -432,7 +444,115 @@ struct Engine : EngineBase {
             cov.host.assign((size_t)2 * cov.nbins, 0);
             cov.on = true;
         }
+        if (cfg.flags & MC_F_CONTINUE) {
+            if (ViolModel<S>::ninv(prm) > VIOL_MAX_INV) { set_error("MC_F_CONTINUE: the model has more than 32 invariants"); return MC_EBADCFG; }
+            HIP_TRY(vio.bins.alloc(1));
+            vio.on = true;
+        }
         return MC_OK;
+    }
+
+    // ------------------------------------------------------------------------------- -continue (engine_violations.h)
+    // All on `stream`, behind the kernels of the level they look at, and only for a level that set the violation key.
+    int viol_begin() {
+        memset(&vio.host, 0, sizeof vio.host);
+        for (int i = 0; i < VIOL_CELLS; i++) vio.host.first[i] = ~0ull;
+        vio.have_first = vio.fatal = false;
+        vio.first_key = ~0ull;
+        vio.flagged_levels = vio.passes = 0;
+        HIP_TRY(hipMemcpyAsync(vio.bins, &vio.host, sizeof vio.host, hipMemcpyHostToDevice, stream));
+        return MC_OK;
+    }
+    void viol_stored(uint64_t lo, uint64_t hi) {
+        for (uint64_t c0 = lo; c0 < hi; c0 += chunk) {
+            const uint64_t c1 = c0 + chunk < hi ? c0 + chunk : hi;
+            hipLaunchKernelGGL(k_viol_stored<S>, dim3((unsigned)((c1 - c0 + 255) / 256)), dim3(256), 0, stream, prm, (const uint64_t *)d_arena,
+                               (const uint32_t *)d_parent, (const uint16_t *)d_pslot, c0, c1, vio.bins.p);
+            vio.passes++;
+        }
+    }
+    void viol_frontier(uint64_t lo, uint64_t hi) {
+        each_chunk(lo, hi, [&](uint64_t c0, uint64_t c1, uint64_t ncols) {
+            hipLaunchKernelGGL(k_viol_frontier<S>, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, stream, prm, (const uint64_t *)d_arena,
+                               c0, c1, ncols, (unsigned)cfg.flags, vio.bins.p);
+            vio.passes++;
+        });
+    }
+    // The level that expanded [lo, hi) and stored [hi, new_hi) has set the key (h_ctr is the host's copy of the counters after it):
+    // remember the first key, run the passes, and either leave the key (a fatal kind: the level loop ends on it) or clear it on the
+    // device, stream-ordered, and in the host's copy.  expanded = false: only stored states were looked at (Init; check_frontier).
+    int viol_level(uint64_t lo, uint64_t hi, uint64_t new_hi, bool expanded) {
+        if (!vio.have_first) { vio.have_first = true; vio.first_key = h_ctr->viol_key; }
+        vio.flagged_levels++;
+        if (expanded) viol_frontier(lo, hi);
+        if (!expanded || ChecksOnExpand<S>::value) viol_stored(lo, hi);
+        else viol_stored(hi, new_hi);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&vio.host, vio.bins, sizeof vio.host, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (vio.host.count[VIOL_BINS + VIOL_BIN_FATAL]) { vio.fatal = true; return MC_OK; }
+        hipLaunchKernelGGL(k_clear_viol_key, dim3(1), dim3(1), 0, stream, d_ctr.p);
+        h_ctr->viol_key = ~0ull;
+        return MC_OK;
+    }
+    uint32_t level_of(uint64_t idx) const {   // 1-based BFS level of an arena index
+        const auto it = std::upper_bound(fr.level_start.begin(), fr.level_start.end(), idx);
+        return (uint32_t)(it - fr.level_start.begin());
+    }
+    // entry k of mc_engine_violations: what it is and where its evidence lies.  shown: 0 nothing, 1 a stored state, 2 a (state, slot) key
+    struct ViolEntry { mc_violation v; int shown; unsigned long long key; };
+    size_t viol_entries() const { return (size_t)ViolModel<S>::ninv(prm) + ((cfg.flags & MC_F_DEADLOCK) ? 1 : 0) + (vio.fatal ? 1 : 0); }
+    int viol_entry(size_t k, ViolEntry &e) {
+        const size_t ninv = (size_t)ViolModel<S>::ninv(prm);
+        memset(&e, 0, sizeof e);
+        e.v.invariant = -1;
+        e.v.first_state = ~0ull;
+        const bool dl = (cfg.flags & MC_F_DEADLOCK) != 0;
+        int bin;
+        if (k < ninv) { bin = (int)k; e.v.kind = MC_V_INVARIANT; e.v.invariant = (int32_t)k; }
+        else if (dl && k == ninv) { bin = VIOL_BIN_DEADLOCK; e.v.kind = MC_V_DEADLOCK; }
+        else if (vio.fatal && k == ninv + (dl ? 1 : 0)) bin = VIOL_BIN_FATAL;
+        else { set_error("mc_engine_violations: entry out of range"); return MC_EBADCFG; }
+        e.v.states = vio.host.count[bin];
+        e.v.outside = vio.host.count[VIOL_BINS + bin];
+        if (e.v.states) { e.shown = 1; e.v.first_state = vio.host.first[bin]; }
+        else if (e.v.outside) {
+            e.shown = 2;
+            e.key = vio.host.first[VIOL_BINS + bin];
+            e.v.first_state = viol_idx(e.key);
+            if (bin == VIOL_BIN_FATAL) { const Viol f(e.key); e.v.kind = f.verdict; e.v.invariant = f.invariant; }
+        }
+        if (e.shown) {   // (a stored state's shortest behaviour has as many states as its level: nothing is read from the device here)
+            e.v.first_level = level_of(e.v.first_state);
+            e.v.trace_len = e.v.first_level + (e.shown == 2 && Viol(e.key).extra_state() ? 1u : 0u);
+        }
+        return MC_OK;
+    }
+    int violations(mc_violations_info *info, mc_violation *out, size_t *n_inout) override {
+        if (!vio.on) { set_error("mc_engine_violations: the engine was created without MC_F_CONTINUE"); return MC_ESTATE; }
+        if (!fr.have_run) { set_error("mc_engine_violations: needs a search of this engine that returned a result"); return MC_ESTATE; }
+        const size_t n = viol_entries();
+        if (info) { info->flagged_levels = vio.flagged_levels; info->passes = vio.passes; info->fatal = vio.fatal ? 1u : 0u; info->pad = 0; }
+        if (n > *n_inout || !out) { *n_inout = n; set_error("mc_engine_violations: buffer too small"); return MC_EBADCFG; }
+        HIP_TRY(hipSetDevice(cfg.device));
+        for (size_t k = 0; k < n; k++) {
+            ViolEntry e;
+            if (int rc = viol_entry(k, e)) return rc;
+            out[k] = e.v;
+        }
+        *n_inout = n;
+        return MC_OK;
+    }
+    int violation_trace(size_t k, uint8_t *states_out, int32_t *actions_out, size_t *n_inout) override {
+        if (!vio.on) { set_error("mc_engine_violation_trace: the engine was created without MC_F_CONTINUE"); return MC_ESTATE; }
+        if (!fr.have_run) { set_error("mc_engine_violation_trace: needs a search of this engine that returned a result"); return MC_ESTATE; }
+        if (k >= viol_entries()) { set_error("mc_engine_violation_trace: entry out of range"); return MC_EBADCFG; }
+        HIP_TRY(hipSetDevice(cfg.device));
+        ViolEntry e;
+        if (int rc = viol_entry(k, e)) return rc;
+        if (!e.shown) { set_error("mc_engine_violation_trace: the entry has nothing to show"); return MC_EBADCFG; }
+        const bool extra = e.shown == 2 && Viol(e.key).extra_state();
+        return chain_trace(e.v.first_state, extra, extra ? Viol(e.key).slot : 0u, states_out, actions_out, n_inout);
     }
 
     // ------------------------------------------------------------------------------- coverage (engine_coverage.h)
@@ -963,6 +1083,10 @@ struct Engine : EngineBase {
         fr.level_start.push_back(0);
         // (a step that continues in place keeps counting; every other search starts its counts over)
         if (cov.on && !in_place && (rc = cov_begin(resuming ? ck.lo : 0, hi))) return rc;
+        if (vio.on) {   // (a search that is continued has found nothing so far: its tables start empty either way)
+            if ((rc = viol_begin())) return rc;
+            if (!resuming && h_ctr->viol_key != ~0ull && (rc = viol_level(0, hi, hi, false))) return rc;   // Init breaks an invariant
+        }
         if (resuming) {  // continue with the frontier [lo, hi) = the last, unexpanded level of the checkpointed run
             fr.level_start = ck.level_start;
             level = (uint32_t)fr.level_start.size();
@@ -1013,6 +1137,8 @@ struct Engine : EngineBase {
                 for (unsigned k = 0; k < h_lc->nlev; k++) {
                     kstat[0].units += hi - lo;  // states expanded by this level (the launches were timed with 0 units)
                     if (cov.on) { cov_generated(lo, hi); cov_distinct(hi, h_lc->level_hi[k]); }
+                    // (k_end_level stops a batch at its first flagged level: the key is that of the last level it completed)
+                    if (vio.on && k + 1 == h_lc->nlev && h_ctr->viol_key != ~0ull && (rc = viol_level(lo, hi, h_lc->level_hi[k], true))) return rc;
                     if ((rc = close_level(lo, hi, h_lc->level_hi[k], level, out))) return rc;
                 }
                 progress(level, lo, hi);
@@ -1078,12 +1204,16 @@ struct Engine : EngineBase {
                 fr.mat_list_hint = (uint64_t)((double)(via / (chunk_no ? chunk_no : 1u)) * (growth > 1.0 ? growth : 1.0)) + 1;
             }
             if (cov.on) { cov_generated(lo, hi); cov_distinct(hi, h_ctr->arena_next); }
+            if (vio.on && h_ctr->viol_key != ~0ull && (rc = viol_level(lo, hi, h_ctr->arena_next, true))) return rc;
             if ((rc = close_level(lo, hi, h_ctr->arena_next, level, out))) return rc;
             progress(level, lo, hi);
         }
         if (cov.on && (rc = cov_end())) return rc;
         // a run that stops with an unexpanded frontier (budget) has not evaluated that level's check-on-expand invariants yet
         if (hi > lo && h_ctr->viol_key == ~0ull && !fr.stop_frontier && (rc = check_frontier(lo, hi))) return rc;
+        if (vio.on && hi > lo && !vio.fatal && h_ctr->viol_key != ~0ull && (rc = viol_level(lo, hi, hi, false))) return rc;   // ... and counted
+        // -continue: the run reports its FIRST flagged level, whatever came after it
+        const unsigned long long run_key = vio.on && vio.have_first ? vio.first_key : h_ctr->viol_key;
         const auto t1 = std::chrono::steady_clock::now();
         out->seconds = std::chrono::duration<double>(t1 - t0).count();
         out->distinct = h_ctr->arena_next;
@@ -1102,9 +1232,9 @@ struct Engine : EngineBase {
         out->levels = level;
         fr.lo = lo;
         fr.hi = hi;
-        if (h_ctr->viol_key != ~0ull) {
+        if (run_key != ~0ull) {
             fr.have_viol = true;
-            fr.last_viol = h_ctr->viol_key;
+            fr.last_viol = run_key;
             const Viol v(fr.last_viol);
             out->verdict = v.verdict;
             out->violated_invariant = v.invariant;
@@ -1330,8 +1460,11 @@ struct Engine : EngineBase {
         chain.clear();
         if (!fr.have_viol) return MC_ESTATE;
         if (Viol(fr.last_viol).slot == SLOT_INIT) return MC_OK;  // violated by an initial state: handled by the caller
+        return chain_to(viol_idx(fr.last_viol), chain);
+    }
+    int chain_to(uint64_t idx, std::vector<uint64_t> &chain) {   // ... to the stored state idx
+        chain.clear();
         if (!d_parent) { set_error("engine created without MC_F_TRACE"); return MC_ESTATE; }
-        uint64_t idx = viol_idx(fr.last_viol);
         for (int guard = 0; guard < MC_MAX_LEVELS; ++guard) {
             chain.push_back(idx);
             uint32_t p;
@@ -1348,34 +1481,39 @@ struct Engine : EngineBase {
         if (!fr.have_viol) { *n_inout = 0; return MC_OK; }
         HIP_TRY(hipSetDevice(cfg.device));
         const Viol v(fr.last_viol);
-        const unsigned slot = v.slot;
-        std::vector<uint64_t> words;
-        std::vector<int32_t> acts;
-        if (slot == SLOT_INIT) {  // an initial state violates an invariant
-            words.resize(W);
+        if (v.slot == SLOT_INIT) {  // an initial state violates an invariant
+            std::vector<uint64_t> words(W);
             S::init(prm, viol_idx(fr.last_viol), WordRef{words.data(), 1});
-            acts.push_back(-1);
-        } else {
-            std::vector<uint64_t> chain;
-            int rc = build_chain(chain);
-            if (rc) return rc;
-            words.resize(chain.size() * W);
-            for (size_t k = 0; k < chain.size(); ++k) {
-                if ((rc = fetch_state(chain[k], &words[k * W]))) return rc;
-                if (k == 0) acts.push_back(-1);
-                else {
-                    uint16_t ps;
-                    HIP_TRY(hipMemcpy(&ps, d_pslot + chain[k], sizeof ps, hipMemcpyDeviceToHost));
-                    acts.push_back(S::action_of(prm, &words[(k - 1) * W], (int)ps));
-                }
-            }
-            if (v.extra_state()) {  // append the violating successor
-                std::vector<uint64_t> last(words.end() - W, words.end());
-                words.resize(words.size() + W);
-                S::apply(prm, CWordRef{last.data(), 1}, (int)slot, WordRef{&words[words.size() - W], 1});
-                acts.push_back(S::action_of(prm, last.data(), (int)slot));
+            std::vector<int32_t> acts{-1};
+            return trace_out(words, acts, states_out, actions_out, n_inout);
+        }
+        return chain_trace(viol_idx(fr.last_viol), v.extra_state(), v.slot, states_out, actions_out, n_inout);
+    }
+    // the behaviour that ends in the stored state `end` (its parent chain), plus — extra — the successor rebuilt from (end, slot)
+    int chain_trace(uint64_t end, bool extra, unsigned slot, uint8_t *states_out, int32_t *actions_out, size_t *n_inout) {
+        std::vector<uint64_t> words, chain;
+        std::vector<int32_t> acts;
+        int rc = chain_to(end, chain);
+        if (rc) return rc;
+        words.resize(chain.size() * W);
+        for (size_t k = 0; k < chain.size(); ++k) {
+            if ((rc = fetch_state(chain[k], &words[k * W]))) return rc;
+            if (k == 0) acts.push_back(-1);
+            else {
+                uint16_t ps;
+                HIP_TRY(hipMemcpy(&ps, d_pslot + chain[k], sizeof ps, hipMemcpyDeviceToHost));
+                acts.push_back(S::action_of(prm, &words[(k - 1) * W], (int)ps));
             }
         }
+        if (extra) {  // append the violating successor
+            std::vector<uint64_t> last(words.end() - W, words.end());
+            words.resize(words.size() + W);
+            S::apply(prm, CWordRef{last.data(), 1}, (int)slot, WordRef{&words[words.size() - W], 1});
+            acts.push_back(S::action_of(prm, last.data(), (int)slot));
+        }
+        return trace_out(words, acts, states_out, actions_out, n_inout);
+    }
+    int trace_out(const std::vector<uint64_t> &words, const std::vector<int32_t> &acts, uint8_t *states_out, int32_t *actions_out, size_t *n_inout) {
         const size_t n = acts.size();
         if (n > *n_inout) { *n_inout = n; set_error("trace buffer too small"); return MC_EBADCFG; }
         if constexpr (HasExport<S>::value) {  // rows leave the engine in the spec's PUBLIC layout (generated code: the interpreter's row)
@@ -2275,6 +2413,12 @@ int mc_engine_create(const mc_spec_desc *spec, const mc_config *cfg, mc_engine *
         with_trace.flags |= MC_F_TRACE;   // distinct[a] is read off the trace records
         cfg = &with_trace;
     }
+    if (cfg->flags & MC_F_CONTINUE) {
+        if (cfg->shard_count > 1) { set_error("MC_F_CONTINUE: not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
+        with_trace = *cfg;
+        with_trace.flags |= MC_F_TRACE;   // the stored pass re-evaluates the trace records; every entry has a behaviour
+        cfg = &with_trace;
+    }
     EngineBase *impl = nullptr;
     const int group = spec_group(spec);
     int rc = MC_EBADCFG;
@@ -2328,6 +2472,12 @@ int mc_engine_simulate(mc_engine *e, const mc_sim_opts *opts, mc_sim_result *out
     return e && opts && out ? e->impl->simulate(opts, out) : MC_EBADCFG;
 }
 int mc_engine_coverage(mc_engine *e, mc_action_coverage *out, size_t *n_inout) { return e && n_inout ? e->impl->coverage(out, n_inout) : MC_EBADCFG; }
+int mc_engine_violations(mc_engine *e, mc_violations_info *info, mc_violation *out, size_t *n_inout) {
+    return e && n_inout ? e->impl->violations(info, out, n_inout) : MC_EBADCFG;
+}
+int mc_engine_violation_trace(mc_engine *e, size_t k, uint8_t *states_out, int32_t *actions_out, size_t *n_inout) {
+    return e && n_inout ? e->impl->violation_trace(k, states_out, actions_out, n_inout) : MC_EBADCFG;
+}
 int mc_engine_graph(mc_engine *e, mc_graph_info *out) { return e && out ? e->impl->graph(out) : MC_EBADCFG; }
 int mc_engine_graph_read(mc_engine *e, uint64_t first, uint64_t count, uint64_t *offsets_out, uint32_t *dst_out, int32_t *action_out, size_t *nedges_inout) {
     return e && nedges_inout ? e->impl->graph_read(first, count, offsets_out, dst_out, action_out, nedges_inout) : MC_EBADCFG;

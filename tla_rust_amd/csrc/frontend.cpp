@@ -714,6 +714,8 @@ int mc_program_assert_pos(const mc_program *p, int index, int *line, int *col) {
 }
 void mc_program_free(mc_program *p) { delete p; }
 
+static const char *invariant_name(const mc_spec_desc *d, int idx);
+const char *mc_invariant_name(const mc_spec_desc *spec, int index) { return spec ? invariant_name(spec, index) : "?"; }
 static const char *invariant_name(const mc_spec_desc *d, int idx) {
     if (d->spec_id == MC_SPEC_PCAL) {
         const pcal::Program *P = (const pcal::Program *)(intptr_t)d->params[0];
@@ -1189,6 +1191,8 @@ static bool no_behavior_cfg(const char *tla_path, const char *cfg_path) {
 // its TLC log testout2): the general evaluator of tlaeval.h runs TLC's breadth-first search on the host and the report says so.
 static int host_evaluate(const char *tla_path, const char *cfg_path, const mc_config *cfg, const std::string &module, char *report,
                          size_t report_cap, mc_result *res) {
+    if (cfg->flags & MC_F_CONTINUE)   // (the host search ends at its first error; what -continue lists is collected by the GPU engine)
+        return fe_fail(MC_ENOSPEC, "%s: -continue is not available for a module evaluated on the host (it needs a GPU lowering)", module.c_str());
     std::string cpath;
     if (cfg_path) cpath = cfg_path;
     else {
@@ -1258,6 +1262,60 @@ static int host_evaluate(const char *tla_path, const char *cfg_path, const mc_co
     return MC_OK;
 }
 
+// A behaviour in TLC's layout: "State k: <Action line .. of module M>" and the state's text (README.md:270-311)
+static void put_behavior(Out &o, const mc_spec_desc &d, const std::vector<std::string> &srcL, const std::string &def_module, const uint8_t *states,
+                         const int32_t *acts, size_t n) {
+    const size_t W = mc_state_bytes(&d);
+    std::vector<char> txt(1 << 16);
+    for (size_t k = 0; k < n; k++) {
+        mc_state_format(&d, &states[k * W], txt.data(), txt.size());
+        if (acts[k] < 0) { o.put("State %zu: <Initial predicate>\n%s\n\n", k + 1, txt.data()); continue; }
+        const char *an = mc_action_name(&d, acts[k]);
+        const Span sp = definition_span(srcL, an);
+        if (sp.ok)  // README.md:278
+            o.put("State %zu: <Action line %d, col %d to line %d, col %d of module %s>\n%s\n\n", k + 1, sp.l1, sp.c1, sp.l2, sp.c2,
+                  def_module.c_str(), txt.data());
+        else
+            o.put("State %zu: <Action %s of module %s>\n%s\n\n", k + 1, an, def_module.c_str(), txt.data());
+    }
+}
+
+// TLC's -continue: everything the search found after its first error (mc_engine_violations), one line per entry and, under each line
+// that has a violator and is not the first error, its shortest behaviour.  The layout is ours.
+static int put_violations(Out &o, mc_engine *e, const Resolved &R, const mc_result *res) {
+    const mc_spec_desc &d = R.d;
+    size_t n = 0;
+    mc_violations_info info;
+    mc_engine_violations(e, &info, nullptr, &n);   // (the count)
+    std::vector<mc_violation> rows(n ? n : 1);
+    if (int rc = mc_engine_violations(e, &info, rows.data(), &n)) return rc;
+    const std::vector<std::string> srcL = split_lines(R.def_text.empty() ? R.tla : R.def_text);
+    const std::string &def_module = R.def_text.empty() ? R.module : R.def_module_name;
+    const size_t W = mc_state_bytes(&d);
+    o.put("The search continued past the first error (-continue).  Every violation found (a state is listed under its first violated invariant only):\n");
+    bool first_shown = false;   // the first error's behaviour is printed above: the first entry of its kind that has a violator
+    for (size_t k = 0; k < n; k++) {
+        const mc_violation &v = rows[k];
+        const bool fatal = info.fatal && k + 1 == n;
+        std::string head;
+        if (fatal) head = v.kind == MC_V_ASSERT ? "Assert failed" : v.kind == MC_V_INVARIANT ? std::string("Action property ") + invariant_name(&d, v.invariant) : "Evaluation error";
+        else head = v.kind == MC_V_DEADLOCK ? "Deadlock" : std::string("Invariant ") + invariant_name(&d, v.invariant);
+        if (fatal) o.put("%s: the search ended here, %llu failing step%s, first at depth %u\n", head.c_str(), (unsigned long long)v.outside, v.outside == 1 ? "" : "s", v.first_level);
+        else if (!v.states && !v.outside) { o.put("%s: 0 distinct states\n", head.c_str()); continue; }
+        else if (v.outside) o.put("%s: %llu distinct state%s, %llu outside the model, first at depth %u\n", head.c_str(), (unsigned long long)v.states, v.states == 1 ? "" : "s",
+                                  (unsigned long long)v.outside, v.first_level);
+        else o.put("%s: %llu distinct state%s, first at depth %u\n", head.c_str(), (unsigned long long)v.states, v.states == 1 ? "" : "s", v.first_level);
+        const bool is_first = !first_shown && v.kind == res->verdict && v.invariant == res->violated_invariant;
+        if (is_first) { first_shown = true; continue; }
+        size_t m = v.trace_len ? v.trace_len : 1;
+        std::vector<uint8_t> states(m * W);
+        std::vector<int32_t> acts(m);
+        if (mc_engine_violation_trace(e, k, states.data(), acts.data(), &m) == MC_OK && m) put_behavior(o, d, srcL, def_module, states.data(), acts.data(), m);
+    }
+    o.put("End of the violations (%u flagged level%s).\n", info.flagged_levels, info.flagged_levels == 1 ? "" : "s");
+    return MC_OK;
+}
+
 // The error part of a report: TLC's message for the violation, the behaviour that leads to it (mc_engine_trace) and, for an Assert,
 // the positions of the failing conjunct.  Both the BFS (mc_check_files_ckpt) and simulation (mc_simulate_files) print it.
 static void put_error_report(Out &o, mc_engine *e, const Resolved &R, int32_t verdict, int32_t violated_invariant, uint32_t trace_len) {
@@ -1310,18 +1368,7 @@ static void put_error_report(Out &o, mc_engine *e, const Resolved &R, int32_t ve
     }
     if (have_trace) {
         o.put("Error: The behavior up to this point is:\n");
-        std::vector<char> txt(1 << 16);
-        for (size_t k = 0; k < n; k++) {
-            mc_state_format(&d, &states[k * W], txt.data(), txt.size());
-            if (acts[k] < 0) { o.put("State %zu: <Initial predicate>\n%s\n\n", k + 1, txt.data()); continue; }
-            const char *an = mc_action_name(&d, acts[k]);
-            const Span sp = definition_span(srcL, an);
-            if (sp.ok)  // README.md:278
-                o.put("State %zu: <Action line %d, col %d to line %d, col %d of module %s>\n%s\n\n", k + 1, sp.l1, sp.c1, sp.l2, sp.c2,
-                      def_module.c_str(), txt.data());
-            else
-                o.put("State %zu: <Action %s of module %s>\n%s\n\n", k + 1, an, def_module.c_str(), txt.data());
-        }
+        put_behavior(o, d, srcL, def_module, states.data(), acts.data(), n);
     }
     if (verdict == MC_V_ASSERT) {  // README.md:313-316: the conjunct being evaluated and the Assert call itself
         int first = 0;
@@ -1703,6 +1750,8 @@ static int check_files_impl(const char *tla_path, const char *cfg_path, const mc
     } else {
         put_error_report(o, e, R, res->verdict, res->violated_invariant, res->trace_len);
     }
+    if ((cfg->flags & MC_F_CONTINUE) && res->verdict != MC_V_OK && res->verdict != MC_V_BUDGET && res->verdict != MC_V_LIVENESS &&
+        (rc = put_violations(o, e, R, res))) { mc_engine_destroy(e); return rc; }
     if (cfg->flags & MC_F_COVERAGE) {   // TLC's -coverage: one row per action, "<Name>: distinct:generated" (the layout is ours: INTEGRATION.md)
         size_t n = 0;
         mc_engine_coverage(e, nullptr, &n);   // (the count)

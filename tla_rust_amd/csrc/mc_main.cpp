@@ -5,7 +5,7 @@
 //   mc X.tla [-config X.cfg] [-deadlock] [-workers N] [-device D] [-generic] [-dump FILE] [-dump dot[,actionlabels][,colorize] FILE]
 //            [-maxdistinct N] [-maxlevels N] [-tablelog2 T] [-arena N] [-chunk N]
 //            [-checkpoint FILE] [-recover FILE] [-gpus P [-samedevice | -torch] [-exchange exact|measured|packed] [-fanout N]] [-noprogress] [-I DIR]
-//            [-coverage [MINUTES]] [-strongfair]
+//            [-coverage [MINUTES]] [-strongfair] [-continue]
 //   mc X.tla -simulate [num=N] [-depth D] [-seed S] [-config X.cfg] [-deadlock] [-jit] [-device D] [-noprogress] [-I DIR]
 //   mc --transpile X.tla [Y.tla ...]      the `pcal2tla *tla` of the reference's Makefile:3-4: inserts (or
 //                                         replaces) the TLA+ translation of the PlusCal algorithm in place,
@@ -50,6 +50,12 @@
 //             depth give the same walks and the same report.  The report has the error and its behaviour as the search's has, "The
 //             number of states generated: G" and the walks, but no distinct-state count or search depth: nothing was searched
 //             exhaustively.  -gpus, -dump, -checkpoint and -recover do not apply; a module without a GPU lowering is refused.
+// -continue: TLC's -continue: a violated invariant or a deadlock no longer ends the search (MC_F_CONTINUE).  The report prints the first
+//             error with its behaviour as ever, then one line per invariant of the model (and one for deadlock): the distinct states
+//             that break it — each state under its FIRST violated invariant only —, the violating successors outside the model, the
+//             depth of the first one, and its shortest behaviour; a failed Assert or an evaluation error still ends the search and
+//             comes last.  The exit status is the first error's.  Not with -simulate, -gpus, -recover or -checkpoint; a module
+//             evaluated on the host is refused.
 // -coverage [N]: TLC's -coverage: after the search the report lists, for Init and for every action of the model (every label of a PlusCal
 //             algorithm and its terminating disjunct), "<Name>: D:G" — the distinct states the action was first to find and the states it
 //             generated; an action with 0:0 never fired (MC_F_COVERAGE, mc_engine_coverage).  TLC's argument, the minutes between two
@@ -356,6 +362,11 @@ int main(int argc, char **argv) {
             for (int j = 1; j < argc; j++)
                 for (const char *other : {"-simulate", "-gpus", "-recover"})
                     if (!strcmp(argv[j], other)) { fprintf(stderr, "mc: -coverage is not available with %s\n", other); return 1; }
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "-continue"))
+            for (int j = 1; j < argc; j++)
+                for (const char *other : {"-simulate", "-gpus", "-recover", "-checkpoint"})
+                    if (!strcmp(argv[j], other)) { fprintf(stderr, "mc: -continue is not available with %s\n", other); return 1; }
     if (gpus && !getenv("MC_RANK"))
         for (int i = 1; i < argc; i++)
             if (!strcmp(argv[i], "-dump") && i + 1 < argc && (!strcmp(argv[i + 1], "dot") || !strncmp(argv[i + 1], "dot,", 4))) {
@@ -411,6 +422,7 @@ int main(int argc, char **argv) {
             uint64_t minutes = 0;   // TLC's interval between two coverage reports: accepted, not used
             if (i + 1 < argc && parse_u64(argv[i + 1], &minutes)) ++i;
         }
+        else if (!strcmp(argv[i], "-continue")) cfg.flags |= MC_F_CONTINUE;
         else if (!strcmp(argv[i], "-deadlock")) cfg.flags &= ~MC_F_DEADLOCK;
         else if (arg("-dump") && (!strcmp(argv[i + 1], "dot") || !strncmp(argv[i + 1], "dot,", 4))) {   // TLC: -dump dot[,actionlabels][,colorize] FILE
             for (const char *s = argv[++i] + 3; *s;) {
@@ -470,6 +482,8 @@ int main(int argc, char **argv) {
                 "                [-maxdistinct N] [-maxlevels N] [-tablelog2 T] [-arena N] [-chunk N]\n"
                 "                [-checkpoint FILE] [-recover FILE] [-gpus P [-torch]]                    check X.tla like `tlc X.tla`\n"
                 "                [-coverage [MINUTES]]                                                    ... and list every action's distinct:generated counts\n"
+                "                [-continue]                                                              ... and search on past violated invariants and deadlocks:\n"
+                "                the first error as ever, then every invariant with its number of violating states and a shortest behaviour\n"
                 "                a PlusCal X.tla whose X.cfg says PROPERTY Termination: checked under the algorithm's weak fairness (`fair process`,\n"
                 "                `--fair algorithm`) on the complete state graph; so is a PROPERTY that names a definition of the shape <>A, []<>A,\n"
                 "                <>[]A or A ~> B over state predicates (under \\A over constant sets, and conjunctions of these); any other temporal\n"
