@@ -79,6 +79,15 @@ pub struct mc_scc_info {
 pub struct mc_live_info { pub violated: i32, pub pad: u32, pub fair_components: u64, pub root: u64, pub root_size: u64, pub seconds: f64 }
 #[repr(C)]
 pub struct mc_live_strong_info { pub rounds: u32, pub scc_builds: u32, pub closed_states: u64, pub final_components: u64, pub seconds: f64 }
+// one check a cfg's PROPERTY name became (mc_program_live_property), and what mc_engine_liveness_check* report about it
+#[repr(C)]
+pub struct mc_live_property { pub origin: [c_char; 64], pub name: [c_char; 128], pub kind: i32, pub p: i32, pub q: i32, pub refused: i32, pub reason: [c_char; 256] }
+#[repr(C)]
+pub struct mc_live_check_info { pub violated: i32, pub sweeps: u32, pub fair_components: u64, pub witness: u64, pub root: u64, pub root_size: u64,
+                                pub mask_states: u64, pub bad_starts: u64, pub scc_builds: u32, pub pad: u32, pub seconds: f64 }
+// fairness label by label: of_unit[u] = the WF / SF conjuncts unit u (an edge's class: instance and label of the source state) belongs to
+#[repr(C)]
+pub struct mc_fair_units { pub nunits: i32, pub nconj: i32, pub of_unit: [u64; 128], pub weak_mask: u64, pub strong_mask: u64 }
 #[repr(C)]
 pub struct mc_engine { _private: [u8; 0] }
 #[repr(C)]
@@ -112,6 +121,14 @@ extern "C" {
     // the same under strong fairness of the instances in strong_mask (`fair+ process`), weak fairness of those in weak_mask
     pub fn mc_engine_liveness_strong(e: *mut mc_engine, weak_mask: u64, strong_mask: u64, out: *mut mc_live_info,
                                      strong_out: *mut mc_live_strong_info) -> c_int;
+    // the same under pcal2tla's conjuncts label by label (`+` / `-` labels, `fair+`): the table from mc_program_fairness_units
+    pub fn mc_engine_liveness_units(e: *mut mc_engine, fu: *const mc_fair_units, out: *mut mc_live_info, strong_out: *mut mc_live_strong_info) -> c_int;
+    pub fn mc_engine_liveness_check_units(e: *mut mc_engine, fu: *const mc_fair_units, prop: *const mc_live_property, out: *mut mc_live_check_info,
+                                          strong_out: *mut mc_live_strong_info) -> c_int;
+    pub fn mc_engine_liveness_edge_units(e: *mut mc_engine, first_edge: u64, count: u64, unit_out: *mut i8) -> c_int;
+    pub fn mc_program_translated_labelfair(p: *const mc_program) -> *const c_char;
+    pub fn mc_program_fairness_units(p: *const mc_program, out: *mut mc_fair_units, refusal: *mut *const c_char) -> c_int;
+    pub fn mc_program_fairness_conjunct(p: *const mc_program, k: c_int) -> *const c_char;
     pub fn mc_engine_read_states(e: *mut mc_engine, first: u64, count: u64, out: *mut u8) -> c_int;
     // TLC's checkpoint / -recover (testout1:10): write / reload the states found so far; the next run continues
     pub fn mc_engine_checkpoint(e: *mut mc_engine, path: *const c_char) -> c_int;

@@ -121,6 +121,10 @@ typedef struct {
 #define MC_F_STRONGFAIR 33554432u /* mc_check_files (`mc -strongfair`): a `fair+ process` is checked under strong fairness (mc_program_fairness_strong,
                              mc_engine_liveness_strong / mc_engine_liveness_check_strong) instead of being named as NOT checked.  Without
                              `fair+` in the algorithm the report is the one without the flag. */
+#define MC_F_LABELFAIR 134217728u /* mc_check_files (`mc -labelfair`): liveness under pcal2tla's fairness label by label — `fair+`, `+` / `-` labels,
+                             procedures — by units and conjuncts (mc_program_fairness_units, mc_engine_liveness_units /
+                             mc_engine_liveness_check_units) instead of naming the properties as NOT checked.  Without it every report is
+                             what it was; a program with none of these forms gets the same report with it. */
 #define MC_F_COVERAGE 16777216u /* TLC's -coverage: count, per action of the model, the successors it generated and the distinct states it
                              was first to find (mc_engine_coverage below; mc_check_files appends "The coverage statistics" to its
                              report).  Implies MC_F_TRACE.  One-GPU engines only: mc_engine_create refuses it with shard_count > 1.
@@ -429,6 +433,36 @@ typedef struct mc_live_strong_info {
 int mc_engine_liveness_strong(mc_engine *e, uint64_t weak_mask, uint64_t strong_mask, mc_live_info *out, mc_live_strong_info *strong_out);
 int mc_engine_liveness_check_strong(mc_engine *e, uint64_t weak_mask, uint64_t strong_mask, const mc_live_property *prop, mc_live_check_info *out,
                                     mc_live_strong_info *strong_out);
+/* ------------------------------------------------------------------ fairness label by label
+ * PlusCal's fairness is finer than "one process, one conjunct": a label `l:-` of a fair process is left out of its conjunct, a label
+ * `l:+` gets a conjunct SF_vars(l(self)) of its own, and every procedure a fair process reaches gets one (the labels of the procedure's
+ * copies in that process; the process's own conjunct is then over its own labels alone).  Two notions replace
+ * "process instance" in the rule above.  A UNIT is the class of an edge: a function of the instance that steps and of the label at
+ * pc[self] in the source state (at most 127).  A CONJUNCT is one WF_vars / SF_vars conjunct of the translation's Spec, a set of units
+ * of one instance (at most 64); of_unit[u] has one bit per conjunct unit u belongs to — two for a `+` label of a weakly fair process,
+ * none for a `-` label or a label of an unfair process.  weak_mask / strong_mask are masks of conjuncts.  The rule is the strong
+ * calls' with "conjunct" for "process": an edge of unit u counts for the conjuncts of of_unit[u].  mc_program_fairness_units fills
+ * the struct for a compiled program (returns the number of conjuncts; *refusal as mc_program_fairness: a VIEW, more than 64
+ * conjuncts or 127 units — named with the count); mc_program_fairness_conjunct: conjunct k for its instance, as the translation prints it with the
+ * instance's identifier for `self` (an identifier that is neither an integer nor written out in the process's set is shown as the
+ * number the program keeps for it), NULL past the last.  The engine calls take the edges' units from the program (k_live_unit) and the table from *fu.  Errors: the strong
+ * twins', and MC_EBADCFG for masks that overlap, a conjunct bit >= nconj in a mask or in of_unit[], nunits or nconj out of range or
+ * nunits smaller than the program's units.  When every unit is one process instance, of_unit[u] = 1 << u and the masks are
+ * mc_program_fairness_strong's, every field but `seconds` equals the strong calls'.  mc_engine_liveness_components and
+ * mc_engine_liveness_trace serve the last check of any kind: after this one the cycle takes, for every weak conjunct, a real step
+ * of it inside the component or passes a state where it is disabled, and a real step of every strong conjunct taken in the component. */
+typedef struct mc_fair_units {
+    int32_t  nunits, nconj;     /* units 0 .. nunits - 1 (<= 127), conjuncts 0 .. nconj - 1 (<= 64)    */
+    uint64_t of_unit[128];      /* the conjuncts of every unit; 0 past nunits                         */
+    uint64_t weak_mask;         /* the WF_vars conjuncts                                              */
+    uint64_t strong_mask;       /* the SF_vars conjuncts (disjoint)                                   */
+} mc_fair_units;
+int mc_engine_liveness_units(mc_engine *e, const mc_fair_units *fu, mc_live_info *out, mc_live_strong_info *strong_out);
+int mc_engine_liveness_check_units(mc_engine *e, const mc_fair_units *fu, const mc_live_property *prop, mc_live_check_info *out,
+                                   mc_live_strong_info *strong_out);
+/* the units of the edges [first_edge, first_edge + count) of mc_engine_graph_read's numbering, as the last check by units filled them
+ * (-1: the terminating disjunct); MC_ESTATE without such a check */
+int mc_engine_liveness_edge_units(mc_engine *e, uint64_t first_edge, uint64_t count, int8_t *unit_out);
 /* copy `count` resident states starting at arena index `first` (discovery order: level by level)
  * to the host, mc_state_bytes() bytes each — TLC's "states/" dump, for tests and tooling */
 int mc_engine_read_states(mc_engine *e, uint64_t first, uint64_t count, uint8_t *out);
@@ -766,6 +800,12 @@ int mc_program_fairness(const mc_program *p, uint64_t *weak_fair_mask, const cha
 /* the same for the strong calls: *strong_mask = the `fair+` instances, *weak_mask = the other fair ones (disjoint); *refusal is NULL
  * for a program whose only obstacle was `fair+`, and mc_program_fairness's words for everything else */
 int mc_program_fairness_strong(const mc_program *p, uint64_t *weak_mask, uint64_t *strong_mask, const char **refusal);
+/* the same label by label (mc_fair_units, above): pcal2tla's conjuncts for `fair+`, `+` / `-` labels and procedures */
+int mc_program_fairness_units(const mc_program *p, mc_fair_units *out, const char **refusal);
+const char *mc_program_fairness_conjunct(const mc_program *p, int k);
+/* mc_program_translated with Spec's fairness conjuncts written label by label, as pcal2tla writes them (the same text for a program
+ * without `+` / `-` labels in fair processes) */
+const char *mc_program_translated_labelfair(const mc_program *p);
 /* the cfg's PROPERTY / PROPERTIES names, in cfg order; NULL past the last (what a caller that runs the search itself — `mc -gpus` —
  * must name as NOT checked) */
 const char *mc_program_property(const mc_program *p, int index);

@@ -124,6 +124,22 @@ class LiveInfo(C.Structure):
                 ("root_size", C.c_uint64), ("seconds", C.c_double)]
 
 
+class FairUnits(C.Structure):
+    """mc_fair_units"""
+    _fields_ = [("nunits", C.c_int32), ("nconj", C.c_int32), ("of_unit", C.c_uint64 * 128), ("weak_mask", C.c_uint64), ("strong_mask", C.c_uint64)]
+
+    @classmethod
+    def make(cls, of_unit, nconj, weak_mask, strong_mask, nunits=None):
+        """from a list of conjunct masks, one per unit"""
+        fu = cls()
+        fu.nunits = len(of_unit) if nunits is None else nunits
+        fu.nconj = nconj
+        for u, m in enumerate(of_unit):
+            fu.of_unit[u] = m
+        fu.weak_mask, fu.strong_mask = weak_mask, strong_mask
+        return fu
+
+
 class LiveStrongInfo(C.Structure):
     """mc_live_strong_info"""
     _fields_ = [("rounds", C.c_uint32), ("scc_builds", C.c_uint32), ("closed_states", C.c_uint64), ("final_components", C.c_uint64),
@@ -295,6 +311,15 @@ def lib():
         L.mc_engine_liveness_strong.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(LiveInfo), C.POINTER(LiveStrongInfo)]
         L.mc_engine_liveness_check_strong.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(LiveProperty), C.POINTER(LiveCheckInfo),
                                                       C.POINTER(LiveStrongInfo)]
+        L.mc_program_fairness_units.argtypes = [C.c_void_p, C.POINTER(FairUnits), C.POINTER(C.c_char_p)]
+        L.mc_program_fairness_conjunct.argtypes = [C.c_void_p, C.c_int]
+        L.mc_program_fairness_conjunct.restype = C.c_char_p
+        L.mc_program_translated_labelfair.argtypes = [C.c_void_p]
+        L.mc_program_translated_labelfair.restype = C.c_char_p
+        L.mc_engine_liveness_units.argtypes = [C.c_void_p, C.POINTER(FairUnits), C.POINTER(LiveInfo), C.POINTER(LiveStrongInfo)]
+        L.mc_engine_liveness_edge_units.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.mc_engine_liveness_check_units.argtypes = [C.c_void_p, C.POINTER(FairUnits), C.POINTER(LiveProperty), C.POINTER(LiveCheckInfo),
+                                                     C.POINTER(LiveStrongInfo)]
         L.mc_program_view.argtypes = [C.c_void_p]
         L.mc_program_view.restype = C.c_char_p
         L.mc_program_action_constraint.argtypes = [C.c_void_p, C.c_int]
@@ -550,6 +575,29 @@ class Engine:
         ci, si = LiveCheckInfo(), LiveStrongInfo()
         _check(lib().mc_engine_liveness_check_strong(self._h, weak_mask, strong_mask, C.byref(lp), C.byref(ci), C.byref(si)),
                "mc_engine_liveness_check_strong")
+        return (Result((k, getattr(ci, k)) for k, _ in LiveCheckInfo._fields_ if k != "pad"), Result((k, getattr(si, k)) for k, _ in LiveStrongInfo._fields_))
+
+    def liveness_units(self, fair_units):
+        """mc_engine_liveness_units: `Termination` under the fairness conjuncts of a FairUnits (Program.fairness_units[0]) — `+` / `-`
+        labels and `fair+` as pcal2tla translates them: liveness_strong()'s pair"""
+        li, si = LiveInfo(), LiveStrongInfo()
+        _check(lib().mc_engine_liveness_units(self._h, C.byref(fair_units), C.byref(li), C.byref(si)), "mc_engine_liveness_units")
+        return (Result((k, getattr(li, k)) for k, _ in LiveInfo._fields_ if k != "pad"), Result((k, getattr(si, k)) for k, _ in LiveStrongInfo._fields_))
+
+    def edge_units(self, first, count):
+        """mc_engine_liveness_edge_units: the units of `count` edges (graph()'s numbering) as the last check by units filled them (numpy int8)"""
+        import numpy as np
+        out = np.empty(max(count, 1), dtype=np.int8)
+        _check(lib().mc_engine_liveness_edge_units(self._h, first, count, out.ctypes.data_as(C.c_void_p)), "mc_engine_liveness_edge_units")
+        return out[:count]
+
+    def check_property_units(self, fair_units, prop):
+        """mc_engine_liveness_check_units: check_property under the conjuncts of a FairUnits: check_property_strong()'s pair"""
+        lp = LiveProperty(prop["origin"].encode(), prop["name"].encode(), prop["kind"], prop["p"], prop["q"], 1 if prop["refused"] else 0,
+                          (prop["reason"] or "").encode())
+        ci, si = LiveCheckInfo(), LiveStrongInfo()
+        _check(lib().mc_engine_liveness_check_units(self._h, C.byref(fair_units), C.byref(lp), C.byref(ci), C.byref(si)),
+               "mc_engine_liveness_check_units")
         return (Result((k, getattr(ci, k)) for k, _ in LiveCheckInfo._fields_ if k != "pad"), Result((k, getattr(si, k)) for k, _ in LiveStrongInfo._fields_))
 
     def check_components(self, count):
@@ -862,6 +910,10 @@ class Program:
         _check(lib().mc_program_fairness_strong(h, C.byref(weak), C.byref(strong), C.byref(why)), "mc_program_fairness_strong")
         # (weak mask, strong mask: the `fair+` instances, why Engine.liveness_strong cannot decide for it or None)
         self.strong_fairness = (int(weak.value), int(strong.value), why.value.decode() if why.value else None)
+        # label by label: (FairUnits, the conjuncts' texts, why Engine.liveness_units cannot decide for it or None)
+        fu, why = FairUnits(), C.c_char_p()
+        nconj = lib().mc_program_fairness_units(h, C.byref(fu), C.byref(why))
+        self.fairness_units = (fu, [lib().mc_program_fairness_conjunct(h, k).decode() for k in range(nconj)], why.value.decode() if why.value else None)
         # the cfg's PROPERTY names other than Termination: one dict per check (a quantifier instance of a conjunct) or per refused name —
         # origin, name, kind (MC_LIVE_*, LIVE_KINDS), p, q (indices into live_predicates, -1 = none), refused, reason
         self.live_properties, self.live_predicates = [], []
@@ -878,8 +930,9 @@ class Program:
         while lib().mc_program_action_constraint(h, len(self.action_constraints)):
             self.action_constraints.append(lib().mc_program_action_constraint(h, len(self.action_constraints)).decode())
 
-    def translated(self):
-        return lib().mc_program_translated(self._h).decode()
+    def translated(self, label_fair=False):
+        """the module text after translation; label_fair: Spec's fairness conjuncts label by label, as pcal2tla writes `+` / `-` labels"""
+        return (lib().mc_program_translated_labelfair if label_fair else lib().mc_program_translated)(self._h).decode()
 
     def invariant(self, index):
         return lib().mc_program_invariant(self._h, index).decode()

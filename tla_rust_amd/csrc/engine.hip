@@ -125,6 +125,9 @@ struct EngineBase {
     virtual int liveness_check(uint64_t weak_fair_mask, const mc_live_property *prop, mc_live_check_info *out) = 0;
     virtual int liveness_strong(uint64_t weak, uint64_t strong, mc_live_info *out, mc_live_strong_info *sout) = 0;
     virtual int liveness_check_strong(uint64_t weak, uint64_t strong, const mc_live_property *prop, mc_live_check_info *out, mc_live_strong_info *sout) = 0;
+    virtual int liveness_units(const mc_fair_units *fu, mc_live_info *out, mc_live_strong_info *sout) = 0;
+    virtual int liveness_edge_units(uint64_t first, uint64_t count, int8_t *unit_out) = 0;
+    virtual int liveness_check_units(const mc_fair_units *fu, const mc_live_property *prop, mc_live_check_info *out, mc_live_strong_info *sout) = 0;
     int graph_read(uint64_t first, uint64_t count, uint64_t *offsets_out, uint32_t *dst_out, int32_t *action_out, size_t *nedges_inout) {
         return gr.read(first, count, offsets_out, dst_out, action_out, nedges_inout);
     }
@@ -876,6 +879,87 @@ struct Engine : EngineBase {
             if (int rc = strong_prepare(call, weak, strong, false, &all)) return rc;
             if (int rc = predicates_build(call)) return rc;
             return gr.live_check_strong(all, weak, strong, kind, need_p ? prop->p : -1, need_q ? prop->q : -1, stream, t0, nullptr, out, sout);
+        }
+    }
+
+    // ------------------------------------------------------------------------------- the same label by label: the table's
+    // conditions, the strong twins' preparation with k_live_unit<S> in k_live_proc<S>'s place, then StateGraph::live_check_strong
+    DevBuf<int8_t> live_unit_tab;   // the program's (instance, label) -> unit table, as k_live_unit<S> reads it
+    int units_prepare(const char *name, const mc_fair_units *fu, bool fresh_unit, uint64_t *all_out) {
+        const std::string call(name);
+        if (cfg.shard_count > 1) { set_error(call + ": not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
+        if constexpr (!LiveProc<S>::HAS || !LivePred<S>::HAS) {
+            set_error(call + ": this lowering has no process instances (compiled PlusCal programs only)");
+            return MC_ENOSPEC;
+        } else {
+            if (!fr.have_run || ck.pending || fr.have_viol || fr.hi != fr.lo) {
+                set_error(call + ": needs a search of this engine that finished without a violation and with an empty queue (the complete state graph)");
+                return MC_ESTATE;
+            }
+            if (fu->nunits < 0 || fu->nunits > LIVE_MAX_UNITS) { set_error(call + ": " + std::to_string(fu->nunits) + " units (at most 127)"); return MC_EBADCFG; }
+            if (fu->nconj < 0 || fu->nconj > LIVE_MAX_CONJ) { set_error(call + ": " + std::to_string(fu->nconj) + " conjuncts (at most 64)"); return MC_EBADCFG; }
+            const uint64_t all = live_all_conjuncts(fu->nconj);
+            if ((fu->weak_mask | fu->strong_mask) & ~all) { set_error(call + ": a fairness mask names a conjunct beyond nconj"); return MC_EBADCFG; }
+            if (fu->weak_mask & fu->strong_mask) { set_error(call + ": the weak and the strong mask overlap (a conjunct is WF or SF)"); return MC_EBADCFG; }
+            for (int u = 0; u < LIVE_UNIT_TAB; ++u)
+                if (fu->of_unit[u] & (u < fu->nunits ? ~all : ~0ull)) {
+                    set_error(call + ": of_unit[" + std::to_string(u) + "] names " + (u < fu->nunits ? "a conjunct beyond nconj" : "conjuncts for a unit beyond nunits"));
+                    return MC_EBADCFG;
+                }
+            int ni = 0, nl = 0;
+            const int nu = vm_live_units(prm.host, &ni, &nl, nullptr, 0);
+            if (fu->nunits < nu) { set_error(call + ": the program has " + std::to_string(nu) + " units, the table " + std::to_string(fu->nunits)); return MC_EBADCFG; }
+            if (!gr.built || !gr.lv.scc_built) { mc_scc_info si; if (int rc = scc(&si)) return rc; }
+            auto &lv = gr.lv;
+            lv.checked = false;
+            HIP_TRY(hipSetDevice(cfg.device));
+            if (fresh_unit || !lv.unit_built) {
+                const uint64_t edges = gr.info.edges;
+                std::vector<int8_t> tab((size_t)ni * (size_t)nl + 1, (int8_t)LIVE_TERM);
+                vm_live_units(prm.host, &ni, &nl, tab.data(), (int)tab.size());
+                if (int rc = graph_alloc(live_unit_tab, tab.size(), "the units of the labels", name)) return rc;
+                if (int rc = graph_alloc(lv.unit, edges, "the edges' units", name)) return rc;
+                HIP_TRY(hipMemcpyAsync(live_unit_tab, tab.data(), tab.size() * sizeof(int8_t), hipMemcpyHostToDevice, stream));
+                HIP_TRY(hipMemsetAsync(lv.unit, 0xff, (edges ? edges : 1) * sizeof(int8_t), stream));
+                graph_chunks(k_live_unit<S>, 0, fr.lo, (const uint64_t *)gr.offsets.p, LiveUnitTab{ni, nl, (const int8_t *)live_unit_tab.p}, lv.unit.p);
+                HIP_TRY(hipStreamSynchronize(stream));   // (the host table is read by the copy until here)
+                lv.unit_built = true;
+            }
+            *all_out = all;
+            return MC_OK;
+        }
+    }
+    int liveness_edge_units(uint64_t first, uint64_t count, int8_t *unit_out) override { return gr.live_unit_read(first, count, unit_out); }
+    int liveness_units(const mc_fair_units *fu, mc_live_info *out, mc_live_strong_info *sout) override {
+        memset(out, 0, sizeof *out);
+        memset(sout, 0, sizeof *sout);
+        const auto t0 = std::chrono::steady_clock::now();
+        uint64_t all = 0;
+        if (int rc = units_prepare("mc_engine_liveness_units", fu, true, &all)) return rc;
+        return gr.live_check_strong(all, fu->weak_mask, fu->strong_mask, -1, -1, -1, stream, t0, out, nullptr, sout, fu->of_unit);
+    }
+    int liveness_check_units(const mc_fair_units *fu, const mc_live_property *prop, mc_live_check_info *out, mc_live_strong_info *sout) override {
+        memset(out, 0, sizeof *out);
+        memset(sout, 0, sizeof *sout);
+        if constexpr (!LiveProc<S>::HAS || !LivePred<S>::HAS) {
+            set_error("mc_engine_liveness_check_units: this lowering has no process instances (compiled PlusCal programs only)");
+            return MC_ENOSPEC;
+        } else {
+            const char *call = "mc_engine_liveness_check_units";
+            if (prop->refused) { set_error(std::string(call) + ": the front end refused " + prop->name); return MC_EBADCFG; }
+            const int npred = vm_live_preds(prm.host, nullptr, 0);
+            const int kind = prop->kind;
+            if (kind < LIVE_LEADS_TO || kind > LIVE_STABLE) { set_error(std::string(call) + ": unknown kind " + std::to_string(kind)); return MC_EBADCFG; }
+            const bool need_p = kind == LIVE_LEADS_TO || kind == LIVE_STABLE, need_q = kind != LIVE_STABLE;
+            if ((need_p && (prop->p < 0 || prop->p >= npred)) || (need_q && (prop->q < 0 || prop->q >= npred)) || npred > LIVE_MAX_PREDS) {
+                set_error(std::string(call) + ": a predicate index the program does not have (it has " + std::to_string(npred) + " predicates)");
+                return MC_EBADCFG;
+            }
+            const auto t0 = std::chrono::steady_clock::now();
+            uint64_t all = 0;
+            if (int rc = units_prepare(call, fu, false, &all)) return rc;
+            if (int rc = predicates_build(call)) return rc;
+            return gr.live_check_strong(all, fu->weak_mask, fu->strong_mask, kind, need_p ? prop->p : -1, need_q ? prop->q : -1, stream, t0, nullptr, out, sout, fu->of_unit);
         }
     }
 
@@ -2495,6 +2579,16 @@ int mc_engine_liveness_check(mc_engine *e, uint64_t weak_fair_mask, const mc_liv
 }
 int mc_engine_liveness_strong(mc_engine *e, uint64_t weak_mask, uint64_t strong_mask, mc_live_info *out, mc_live_strong_info *strong_out) {
     return e && out && strong_out ? e->impl->liveness_strong(weak_mask, strong_mask, out, strong_out) : MC_EBADCFG;
+}
+int mc_engine_liveness_units(mc_engine *e, const mc_fair_units *fu, mc_live_info *out, mc_live_strong_info *strong_out) {
+    return e && fu && out && strong_out ? e->impl->liveness_units(fu, out, strong_out) : MC_EBADCFG;
+}
+int mc_engine_liveness_edge_units(mc_engine *e, uint64_t first_edge, uint64_t count, int8_t *unit_out) {
+    return e && (unit_out || !count) ? e->impl->liveness_edge_units(first_edge, count, unit_out) : MC_EBADCFG;
+}
+int mc_engine_liveness_check_units(mc_engine *e, const mc_fair_units *fu, const mc_live_property *prop, mc_live_check_info *out,
+                                   mc_live_strong_info *strong_out) {
+    return e && fu && prop && out && strong_out ? e->impl->liveness_check_units(fu, prop, out, strong_out) : MC_EBADCFG;
 }
 int mc_engine_liveness_check_strong(mc_engine *e, uint64_t weak_mask, uint64_t strong_mask, const mc_live_property *prop, mc_live_check_info *out,
                                     mc_live_strong_info *strong_out) {

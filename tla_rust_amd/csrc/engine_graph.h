@@ -9,6 +9,7 @@
 //   k_graph_degree   pass 1, one lane per expanded state: the slot loop to the wavefront's largest nslots, degree[i] = its edges
 //   k_graph_fill     pass 2, the same loop: dst[offsets[i] + k], act[offsets[i] + k] in slot order
 //   k_live_proc      the loop a third time, for mc_engine_liveness: proc[offsets[i] + k] beside act[] (LiveProc<S>, liveness.h)
+//   k_live_unit      and a fourth time, for mc_engine_liveness_units: unit[offsets[i] + k], from the slot's instance and the label it stands at
 //   k_live_pred      one lane per stored state, the same chunks: pred[i] = the state predicates of the cfg's temporal properties that hold
 //                    in it, one bit each (LivePred<S>, liveness.h)
 // Between the passes an exclusive scan turns degree into offsets.  Nothing here writes the arena, the seen-set or a counter of the search.
@@ -151,6 +152,37 @@ k_live_proc(typename S::Params prm, const uint64_t *__restrict__ arena, uint64_t
         const unsigned kind = graph_edge(S::eval(prm, loc, s, slot, f), f, table, seen, pos);
         if (kind != GE_SELF && kind != GE_EDGE) continue;
         if (out < end) proc[out] = (int8_t)LiveProc<S>::of(prm, slot);
+        ++out;
+    }
+}
+
+// unit[] beside proc[] (mc_engine_liveness_units): the same walk and the same graph_edge decisions; the unit of an
+// edge is a function of the instance of the slot and of the label that instance stands at in the row the walk has loaded (the SOURCE
+// state), read from the (instance, label) -> unit table in device memory
+template <class S>
+__global__ void __launch_bounds__(256)
+k_live_unit(typename S::Params prm, const uint64_t *__restrict__ arena, uint64_t lo, uint64_t hi, uint64_t ncols,
+            const uint64_t *__restrict__ table, uint64_t seen, const uint64_t *__restrict__ offsets, LiveUnitTab tab, int8_t *__restrict__ unit) {
+    const uint64_t col = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t idx = (lo & ~63ull) + col;
+    const bool active = col < ncols && idx >= lo && idx < hi;
+    const CWordRef s = arena_cref(arena, active ? idx : lo, S::words(prm));
+    typename S::Local loc;
+    int ns = 0;
+    uint64_t out = 0, end = 0;
+    if (active) {
+        S::load(prm, s, loc);
+        ns = S::nslots(prm, loc);
+        out = offsets[idx];
+        end = offsets[idx + 1];
+    }
+    const int wns = (int)wave_max_u32((unsigned)ns);
+    for (int slot = 0; slot < wns; ++slot) {
+        if (slot >= ns) continue;   // (no wavefront operation inside the loop)
+        uint64_t f = 0, pos;
+        const unsigned kind = graph_edge(S::eval(prm, loc, s, slot, f), f, table, seen, pos);
+        if (kind != GE_SELF && kind != GE_EDGE) continue;
+        if (out < end) unit[out] = (int8_t)live_edge_unit<S>(prm, loc, tab, slot);
         ++out;
     }
 }

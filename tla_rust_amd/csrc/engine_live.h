@@ -38,11 +38,15 @@
 //               k_live_refine    per open state: closed / still open / final; a final state takes its component's id and size into the
 //                                refined arrays and dist 0; states closed and "some state is still open", one atomic per wavefront
 //               then k_live_reach / k_live_witness as above
+//   units       (mc_engine_liveness_units / mc_engine_liveness_check_units) the refinement with the edges' UNITS in
+//               proc[]'s place and masks of fairness CONJUNCTS: k_live_reduce_units / k_live_enabled_units / k_live_refine_units stage
+//               of_unit[] in LDS and run the bodies of their process-level twins, instantiated for the table; the twins stay the code
+//               they were.  Everything that reads masks alone (k_live_classify, the reach pass, the witness) serves both.
 //
 // Memory, beside the graph's 8 bytes per state and 6 per edge: 16 bytes per state (transpose offsets 8, scc 4, colour / size 4) and 4 per
 // edge (transpose) for mc_engine_scc, 4 more per state while the transpose is built; mc_engine_liveness adds 1 byte per edge (proc) and 20
 // per state (taken 8, disabled 8, Done 4).  A strong check adds 25 per state: enabled 8, open / closed / final 1, the refined ids and
-// sizes 8, the working ids and sizes of rounds >= 2 another 8.
+// sizes 8, the working ids and sizes of rounds >= 2 another 8.  A check by units adds 1 byte per edge (unit) and the table's 1 KiB.
 #ifndef TLAMC_ENGINE_LIVE_H
 #define TLAMC_ENGINE_LIVE_H
 
@@ -209,12 +213,21 @@ __device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) 
     return v;
 }
 
+// The table-driven forms: of_unit[] (LIVE_UNIT_TAB entries in device memory) is staged in LDS at block start and
+// indexed per edge from there — a per-lane index into a by-value kernel argument would end up in scratch.  Every thread of the block
+// gets here (no kernel below returns early).
+__device__ __forceinline__ void live_stage_units(const uint64_t *__restrict__ of_unit, uint64_t *tab) {
+    if (threadIdx.x < (unsigned)LIVE_UNIT_TAB) tab[threadIdx.x] = of_unit[threadIdx.x];
+    __syncthreads();
+}
+
 // MASKED: scc / size are those of G[M]; only the states of M are merged, and `done` says "the component holds a T state"
-template <bool MASKED>
-static __global__ void __launch_bounds__(256)
-k_live_reduce(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ proc,
-              const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, uint64_t all, unsigned long long *taken,
-              unsigned long long *disabled, unsigned *done, const uint32_t *__restrict__ pred, LiveCheck ck) {
+// UNITS: proc[] holds units and of_unit (LDS) maps them to conjuncts; else of_unit is not read and the code is the process-level one
+template <bool MASKED, bool UNITS>
+__device__ __forceinline__ void
+live_reduce_body(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ proc,
+                 const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, uint64_t all, unsigned long long *taken,
+                 unsigned long long *disabled, unsigned *done, const uint32_t *__restrict__ pred, LiveCheck ck, const uint64_t *of_unit) {
     const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = v < n && (!MASKED || live_in_mask(ck, pred[v]));
     uint64_t en = 0, tk = 0;
@@ -222,7 +235,12 @@ k_live_reduce(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *
     uint32_t comp = 0;
     if (active) {
         const uint64_t o = offsets[v];
-        if constexpr (MASKED) {
+        if constexpr (MASKED && UNITS) {
+            live_state_masked_units((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc, of_unit, [&](uint32_t d) { return d < n && live_in_mask(ck, pred[d]); }, &en, &tk);
+            dn = live_in_target(ck, pred[v]);
+        } else if constexpr (UNITS) {
+            live_state_units((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc, of_unit, &en, &tk, &dn);
+        } else if constexpr (MASKED) {
             live_state_masked((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc, [&](uint32_t d) { return d < n && live_in_mask(ck, pred[d]); }, &en, &tk);
             dn = live_in_target(ck, pred[v]);
         } else {
@@ -250,6 +268,23 @@ k_live_reduce(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *
         }
         rest &= ~__ballot(same);
     }
+}
+template <bool MASKED>
+static __global__ void __launch_bounds__(256)
+k_live_reduce(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ proc,
+              const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, uint64_t all, unsigned long long *taken,
+              unsigned long long *disabled, unsigned *done, const uint32_t *__restrict__ pred, LiveCheck ck) {
+    live_reduce_body<MASKED, false>(n, offsets, dst, proc, scc, size, all, taken, disabled, done, pred, ck, nullptr);
+}
+template <bool MASKED>
+static __global__ void __launch_bounds__(256)
+k_live_reduce_units(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ unit,
+                    const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, uint64_t all, unsigned long long *taken,
+                    unsigned long long *disabled, unsigned *done, const uint32_t *__restrict__ pred, LiveCheck ck,
+                    const uint64_t *__restrict__ of_unit) {
+    __shared__ uint64_t tab[LIVE_UNIT_TAB];
+    live_stage_units(of_unit, tab);
+    live_reduce_body<MASKED, true>(n, offsets, dst, unit, scc, size, all, taken, disabled, done, pred, ck, tab);
 }
 
 // MASKED: only the components of states in M are judged, by live_violates_masked; dist[v] = 0 at a violating root, LIVE_FAR elsewhere
@@ -340,16 +375,19 @@ k_scc_open(uint64_t n, const uint8_t *__restrict__ open, uint32_t *__restrict__ 
 }
 // en of every open state (the whole row: the full graph's), OR-ed into enabled[] at the state's component of the round; k_live_reduce's
 // merge.  The entries were cleared before the launch.
-static __global__ void __launch_bounds__(256)
-k_live_enabled(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ proc,
-               const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, const uint8_t *__restrict__ open, unsigned long long *enabled) {
+template <bool UNITS>
+__device__ __forceinline__ void
+live_enabled_body(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ proc,
+                  const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, const uint8_t *__restrict__ open, unsigned long long *enabled,
+                  const uint64_t *of_unit) {
     const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = v < n && open[v] == LIVE_ST_OPEN;
     uint64_t en = 0;
     uint32_t comp = 0;
     if (active) {
         const uint64_t o = offsets[v];
-        en = live_enabled_in((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc);
+        if constexpr (UNITS) en = live_enabled_in_units((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc, of_unit);
+        else en = live_enabled_in((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc);
         comp = scc[v];
     }
     const bool alone = active && size[comp] == 1;
@@ -364,6 +402,19 @@ k_live_enabled(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t 
         if ((int)lane == lead && e) atomicOr(&enabled[c0], e);
         rest &= ~__ballot(same);
     }
+}
+static __global__ void __launch_bounds__(256)
+k_live_enabled(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ proc,
+               const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, const uint8_t *__restrict__ open, unsigned long long *enabled) {
+    live_enabled_body<false>(n, offsets, dst, proc, scc, size, open, enabled, nullptr);
+}
+static __global__ void __launch_bounds__(256)
+k_live_enabled_units(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ unit,
+                     const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, const uint8_t *__restrict__ open, unsigned long long *enabled,
+                     const uint64_t *__restrict__ of_unit) {
+    __shared__ uint64_t tab[LIVE_UNIT_TAB];
+    live_stage_units(of_unit, tab);
+    live_enabled_body<true>(n, offsets, dst, unit, scc, size, open, enabled, tab);
 }
 // has_target of a component: the property checks keep "holds a T state" in done[]; Termination keeps "holds a Done state", and T is
 // "not Done" (a Done state is absorbing: a component with one is that one state)
@@ -384,12 +435,13 @@ k_live_classify(uint64_t n, const uint32_t *__restrict__ scc, const uint32_t *__
 }
 // per open state: closed, kept open or final, by plain stores to its own entries; dist (property checks; null for Termination) is 0 in
 // a final component
-static __global__ void __launch_bounds__(256)
-k_live_refine(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ proc,
-              const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, const unsigned long long *__restrict__ taken,
-              const unsigned long long *__restrict__ disabled, const unsigned *__restrict__ done, const unsigned long long *__restrict__ enabled,
-              uint64_t all, uint64_t weak, uint64_t strong, bool term, uint8_t *open, uint32_t *__restrict__ fscc, uint32_t *__restrict__ fsize,
-              uint32_t *__restrict__ dist, LiveStrongCounters *sc) {
+template <bool UNITS>
+__device__ __forceinline__ void
+live_refine_body(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ proc,
+                 const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, const unsigned long long *__restrict__ taken,
+                 const unsigned long long *__restrict__ disabled, const unsigned *__restrict__ done, const unsigned long long *__restrict__ enabled,
+                 uint64_t all, uint64_t weak, uint64_t strong, bool term, uint8_t *open, uint32_t *__restrict__ fscc, uint32_t *__restrict__ fsize,
+                 uint32_t *__restrict__ dist, LiveStrongCounters *sc, const uint64_t *of_unit) {
     const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = v < n && open[v] == LIVE_ST_OPEN;
     uint8_t next = LIVE_ST_CLOSED;
@@ -397,7 +449,9 @@ k_live_refine(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *
         const uint32_t c = scc[v];
         const uint64_t tk = taken[c], en_c = enabled[c], o = offsets[v];
         const int cls = live_classify(all, weak, strong, tk, disabled[c], en_c, live_strong_target(term, done[c]), size[c]);
-        const uint64_t en = live_enabled_in((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc);
+        uint64_t en;
+        if constexpr (UNITS) en = live_enabled_in_units((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc, of_unit);
+        else en = live_enabled_in((uint32_t)v, dst + o, proc + o, offsets[v + 1] - o, scc);
         next = live_refine_state(cls, live_blockers(all, strong, en_c, tk), en);
         open[v] = next;
         if (next == LIVE_ST_FINAL) {
@@ -411,6 +465,24 @@ k_live_refine(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *
         if (closing) atomicAdd(&sc->closed, (unsigned long long)__popcll(closing));
         if (staying) atomicOr(&sc->open, 1u);
     }
+}
+static __global__ void __launch_bounds__(256)
+k_live_refine(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ proc,
+              const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, const unsigned long long *__restrict__ taken,
+              const unsigned long long *__restrict__ disabled, const unsigned *__restrict__ done, const unsigned long long *__restrict__ enabled,
+              uint64_t all, uint64_t weak, uint64_t strong, bool term, uint8_t *open, uint32_t *__restrict__ fscc, uint32_t *__restrict__ fsize,
+              uint32_t *__restrict__ dist, LiveStrongCounters *sc) {
+    live_refine_body<false>(n, offsets, dst, proc, scc, size, taken, disabled, done, enabled, all, weak, strong, term, open, fscc, fsize, dist, sc, nullptr);
+}
+static __global__ void __launch_bounds__(256)
+k_live_refine_units(uint64_t n, const uint64_t *__restrict__ offsets, const uint32_t *__restrict__ dst, const int8_t *__restrict__ unit,
+                    const uint32_t *__restrict__ scc, const uint32_t *__restrict__ size, const unsigned long long *__restrict__ taken,
+                    const unsigned long long *__restrict__ disabled, const unsigned *__restrict__ done, const unsigned long long *__restrict__ enabled,
+                    uint64_t all, uint64_t weak, uint64_t strong, bool term, uint8_t *open, uint32_t *__restrict__ fscc, uint32_t *__restrict__ fsize,
+                    uint32_t *__restrict__ dist, LiveStrongCounters *sc, const uint64_t *__restrict__ of_unit) {
+    __shared__ uint64_t tab[LIVE_UNIT_TAB];
+    live_stage_units(of_unit, tab);
+    live_refine_body<true>(n, offsets, dst, unit, scc, size, taken, disabled, done, enabled, all, weak, strong, term, open, fscc, fsize, dist, sc, tab);
 }
 
 // ---- the scans (state_graph.h declares them)

@@ -50,6 +50,21 @@ int mc_program_fairness(const mc_program *p, uint64_t *weak_fair_mask, const cha
     if (refusal) *refusal = p->prog.live_refusal.empty() ? nullptr : p->prog.live_refusal.c_str();
     return p->prog.ninst;
 }
+int mc_program_fairness_units(const mc_program *p, mc_fair_units *out, const char **refusal) {
+    if (!p || !out) return 0;
+    memset(out, 0, sizeof *out);
+    const auto &P = p->prog;
+    out->nunits = (int32_t)(P.conj_of_unit.size() > 127 ? 127 : P.conj_of_unit.size());
+    out->nconj = (int32_t)P.fair_conj.size();
+    for (int u = 0; u < out->nunits; u++) out->of_unit[u] = P.conj_of_unit[(size_t)u];
+    for (size_t k = 0; k < P.fair_conj.size(); k++) (P.fair_conj[k].strong ? out->strong_mask : out->weak_mask) |= 1ull << k;
+    if (refusal) *refusal = P.live_refusal_units.empty() ? nullptr : P.live_refusal_units.c_str();
+    return out->nconj;
+}
+const char *mc_program_fairness_conjunct(const mc_program *p, int k) {
+    return p && k >= 0 && (size_t)k < p->prog.fair_conj.size() ? p->prog.fair_conj[(size_t)k].text.c_str() : nullptr;
+}
+const char *mc_program_translated_labelfair(const mc_program *p) { return p ? p->prog.translated_labelfair.c_str() : ""; }
 int mc_program_fairness_strong(const mc_program *p, uint64_t *weak_mask, uint64_t *strong_mask, const char **refusal) {
     if (!p) return MC_EBADCFG;
     if (weak_mask) *weak_mask = p->prog.fair_mask & ~p->prog.strong_mask;
@@ -356,8 +371,12 @@ constexpr uint64_t H_VOTING = 0xa61c2608a8ec9233ull;            // examples/Paxo
 constexpr uint64_t H_PAXOS = 0x979510bc1153e9fbull;             // examples/Paxos/Paxos.tla
 constexpr uint64_t H_CONSENSUS = 0x96d890afa5b1ac82ull;         // examples/Paxos/Consensus.tla
 
-bool algorithm_text(const std::string &t, std::string &out) {
-    const size_t i = t.find("--algorithm");
+// fair_too (MC_F_LABELFAIR alone: without the option a `--fair algorithm` module goes where it went): the keyword `--fair algorithm`
+// starts an algorithm as well, whichever of the two comes first in the text
+bool algorithm_text(const std::string &t, std::string &out, bool fair_too = false) {
+    size_t i = t.find("--algorithm");
+    const size_t f = fair_too ? t.find("--fair algorithm") : std::string::npos;
+    if (f < i) i = f;
     if (i == std::string::npos) return false;
     const size_t j = t.find("end algorithm", i);
     if (j != std::string::npos) { out = t.substr(i, j + strlen("end algorithm") - i); return true; }
@@ -1048,7 +1067,7 @@ static int resolve_files(const char *tla_path, const char *cfg_path, unsigned fl
     // A PlusCal module goes through the hand lowering when its algorithm text is one the registry knows, and
     // through the compiled program (spec_vm.h) otherwise — or always with MC_F_GENERIC (A/B of the two paths).
     std::string part;
-    const bool has_alg = algorithm_text(tla, part);
+    const bool has_alg = algorithm_text(tla, part, (flags & MC_F_LABELFAIR) != 0);
     const uint64_t alg_hash = has_alg ? text_hash(part) : 0;
     bool generic = has_alg && (flags & MC_F_GENERIC);
     if (!has_alg) {  // the Paxos family is recognised by what the model EXTENDS and by the cfg's replacements
@@ -1646,7 +1665,10 @@ static int check_files_impl(const char *tla_path, const char *cfg_path, const mc
     if (generic && !R.properties.empty()) {
         uint64_t fair = 0, strong = 0;   // strong: the `fair+` instances, under MC_F_STRONGFAIR (else they are refused, by name)
         const char *refusal = nullptr;
-        if (cfg->flags & MC_F_STRONGFAIR) mc_program_fairness_strong(prog, &fair, &strong, &refusal);
+        mc_fair_units fu;                // under MC_F_LABELFAIR: pcal2tla's conjuncts label by label, whatever else is set
+        const bool units = (cfg->flags & MC_F_LABELFAIR) != 0;
+        if (units) mc_program_fairness_units(prog, &fu, &refusal);
+        else if (cfg->flags & MC_F_STRONGFAIR) mc_program_fairness_strong(prog, &fair, &strong, &refusal);
         else mc_program_fairness(prog, &fair, &refusal);
         const bool complete = res->verdict == MC_V_OK && res->queue_left == 0;
         bool checked = false;   // Termination was decided (a cfg that names it twice is checked once)
@@ -1691,7 +1713,8 @@ static int check_files_impl(const char *tla_path, const char *cfg_path, const mc
                 for (const auto &lp : checks) {
                     mc_live_check_info ci;
                     mc_live_strong_info si;
-                    if ((rc = strong ? mc_engine_liveness_check_strong(e, fair, strong, &lp, &ci, &si) : mc_engine_liveness_check(e, fair, &lp, &ci))) { mc_engine_destroy(e); return rc; }
+                    if ((rc = units ? mc_engine_liveness_check_units(e, &fu, &lp, &ci, &si)
+                              : strong ? mc_engine_liveness_check_strong(e, fair, strong, &lp, &ci, &si) : mc_engine_liveness_check(e, fair, &lp, &ci))) { mc_engine_destroy(e); return rc; }
                     if (!ci.violated) continue;
                     if ((rc = take_trace())) { mc_engine_destroy(e); return rc; }
                     break;
@@ -1702,7 +1725,8 @@ static int check_files_impl(const char *tla_path, const char *cfg_path, const mc
             checked = true;
             mc_live_info li;
             mc_live_strong_info si;
-            if ((rc = strong ? mc_engine_liveness_strong(e, fair, strong, &li, &si) : mc_engine_liveness(e, fair, &li))) { mc_engine_destroy(e); return rc; }
+            if ((rc = units ? mc_engine_liveness_units(e, &fu, &li, &si)
+                      : strong ? mc_engine_liveness_strong(e, fair, strong, &li, &si) : mc_engine_liveness(e, fair, &li))) { mc_engine_destroy(e); return rc; }
             if (!li.violated) continue;
             if ((rc = take_trace())) { mc_engine_destroy(e); return rc; }
         }

@@ -12,7 +12,8 @@
 //   * LiveProc<S>: which process instance takes the edge of a (state, slot) pair — slot / maxch for the two compiled-program
 //     lowerings, LIVE_TERM for the terminating disjunct.  Other lowerings have no processes: LiveProc<S>::HAS is false.
 //   * live_real_step, live_state, live_merge, live_fair, live_violates: the rule over CSR rows, per-edge processes and component ids.
-//   * strong fairness of whole processes (`fair+`): the refinement at the end of this file, DESIGN section 19.
+//   * strong fairness of whole processes (`fair+`): the refinement further down, DESIGN section 19.
+//   * fairness label by label (`+` / `-` labels): units and conjuncts, at the end of this file, DESIGN section 21.
 // Compiles without HIP.
 #pragma once
 #include "graph.h"
@@ -277,6 +278,107 @@ MC_HD uint32_t live_strong_rounds(uint64_t all, uint64_t strong) {
     uint32_t k = 1;
     for (uint64_t f = strong & all; f; f &= f - 1) ++k;
     return k;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Fairness label by label (mc_engine_liveness_units / mc_engine_liveness_check_units).  Two notions replace "process":
+//
+//   unit       the class of an edge (unit[] in proc[]'s place, LIVE_TERM as before, at most LIVE_MAX_UNITS): a function of the instance
+//              that steps and of the label at pc[self] in the SOURCE state
+//   conjunct   one WF_vars / SF_vars conjunct of the translation's Spec, at most LIVE_MAX_CONJ: a set of units of one instance.
+//              of_unit[u] = the conjuncts unit u belongs to — two for a `+` label of a weakly fair process (the process's WF, its own
+//              SF), none for a `-` label or a label of an unfair process
+//
+// Every mask of the rule — en, taken, disabled, enabled, the blockers, weak / strong, all — is then a mask of CONJUNCTS: an edge
+// contributes of_unit[u] where it contributed 1ull << p, and the functions above that take masks alone (live_merge, live_fair,
+// live_classify, live_refine_state, live_strong_rounds, ...) are used as they are.  With of_unit[u] = 1ull << u the three functions
+// below are live_state, live_state_masked and live_enabled_in.
+constexpr int LIVE_MAX_UNITS = 127, LIVE_MAX_CONJ = 64;
+constexpr int LIVE_UNIT_TAB = 128;   // entries of an of_unit[] table: every int8_t unit >= 0 indexes inside it
+
+// the conjuncts an edge of unit u counts for
+MC_HD uint64_t live_conjuncts(const uint64_t *of_unit, int u) {
+    return u >= 0 ? of_unit[u] : 0;
+}
+MC_HD void live_state_units(uint32_t self, const uint32_t *dst, const int8_t *unit, uint64_t n, const uint32_t *scc, const uint64_t *of_unit, uint64_t *en,
+                            uint64_t *taken, bool *done) {
+    uint64_t e = 0, t = 0;
+    bool d = false;
+    const uint32_t mine = scc[self];
+    for (uint64_t k = 0; k < n; ++k) {
+        const int u = unit[k];
+        if (u == LIVE_TERM) d = true;
+        if (!live_real_step(u, self, dst[k])) continue;
+        const uint64_t c = live_conjuncts(of_unit, u);
+        e |= c;
+        if (scc[dst[k]] == mine) t |= c;
+    }
+    *en = e;
+    *taken = t;
+    *done = d;
+}
+template <class InM>
+MC_HD void live_state_masked_units(uint32_t self, const uint32_t *dst, const int8_t *unit, uint64_t n, const uint32_t *scc, const uint64_t *of_unit, InM &&in_m,
+                                   uint64_t *en, uint64_t *taken) {
+    uint64_t e = 0, t = 0;
+    const uint32_t mine = scc[self];
+    for (uint64_t k = 0; k < n; ++k) {
+        const int u = unit[k];
+        if (!live_real_step(u, self, dst[k])) continue;
+        const uint64_t c = live_conjuncts(of_unit, u);
+        e |= c;   // (the FULL graph's, as in live_state_masked)
+        if (in_m(dst[k]) && scc[dst[k]] == mine) t |= c;
+    }
+    *en = e;
+    *taken = t;
+}
+// the conjuncts enabled in a state: the whole row's, in the full graph
+MC_HD uint64_t live_enabled_in_units(uint32_t self, const uint32_t *dst, const int8_t *unit, uint64_t n, const uint32_t *scc, const uint64_t *of_unit) {
+    uint64_t e = 0, t = 0;
+    live_state_masked_units(self, dst, unit, n, scc, of_unit, [](uint32_t) { return true; }, &e, &t);
+    return e;
+}
+// LiveLabel<S>: the label instance `inst` stands at (the pc cell of the row the walk has loaded — the lowering's own load, never the
+// raw words of a packed row), -1 where the lowering has no processes.  LiveUnitTab: unit[inst * nlabels + label] in device memory;
+// live_unit_of: the unit of an edge taken by `inst` from a state where it stands at `label`; a pair the table does not hold is the
+// instance's own unit (units 0 .. ninst - 1), never LIVE_TERM: that would read the edge as the terminating disjunct's.
+template <class S>
+struct LiveLabel {
+    MC_HD static int of(const typename S::Params &, const typename S::Local &, int) { return -1; }
+};
+template <int MAXV>
+struct LiveLabel<SpecVmT<MAXV>> {
+    MC_HD static int of(const VmParams &p, const typename SpecVmT<MAXV>::Local &l, int inst) { return inst >= 0 && inst < p.ninst ? l.v[p.pc_base + inst] : -1; }
+};
+template <int MAXV>
+struct LiveLabel<SpecVmCfgT<MAXV>> : LiveLabel<SpecVmT<MAXV>> {};
+template <class G>
+struct LiveLabel<SpecGenT<G>> {
+    template <int I>
+    MC_HD static int chain(const typename SpecGenT<G>::Local &l, int inst) {
+        if constexpr (I < G::NINST) return inst == I ? (int)G::template pc_of<I>(l.v) : chain<I + 1>(l, inst);
+        else return -1;
+    }
+    MC_HD static int of(const VmParams &, const typename SpecGenT<G>::Local &l, int inst) { return chain<0>(l, inst); }
+};
+struct LiveUnitTab { int ninst, nlabels; const int8_t *unit; };
+MC_HD int live_unit_of(const LiveUnitTab &t, int inst, int label) {
+    if (inst < 0 || inst >= t.ninst || inst > LIVE_MAX_UNITS - 1) return LIVE_TERM;
+    return label >= 0 && label < t.nlabels ? t.unit[inst * t.nlabels + label] : inst;   // (a label the table does not know: the instance's own unit)
+}
+// the unit of the edge a (state, slot) pair contributes: the slot's instance and the label it stands at in `src`, the loaded row of the
+// SOURCE state; LIVE_TERM for the terminating disjunct alone
+template <class S>
+MC_HD int live_edge_unit(const typename S::Params &prm, const typename S::Local &src, const LiveUnitTab &tab, int slot) {
+    const int inst = LiveProc<S>::of(prm, slot);
+    return inst == LIVE_TERM ? LIVE_TERM : live_unit_of(tab, inst, LiveLabel<S>::of(prm, src, inst));
+}
+// what the host keeps about the units of a compiled program (defined in pcal_compile.cpp, beside vm_live_preds): the number of units,
+// with *ninst / *nlabels the table's shape and unit_out[inst * nlabels + label] filled when cap holds it (cap 0: the shape alone)
+int vm_live_units(const void *host, int *ninst, int *nlabels, int8_t *unit_out, int cap);
+// every conjunct of a table with nconj conjuncts
+MC_HD uint64_t live_all_conjuncts(int nconj) {
+    return nconj >= 64 ? ~0ull : (1ull << nconj) - 1;
 }
 
 }  // namespace mc

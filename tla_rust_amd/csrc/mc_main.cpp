@@ -5,7 +5,7 @@
 //   mc X.tla [-config X.cfg] [-deadlock] [-workers N] [-device D] [-generic] [-dump FILE] [-dump dot[,actionlabels][,colorize] FILE]
 //            [-maxdistinct N] [-maxlevels N] [-tablelog2 T] [-arena N] [-chunk N]
 //            [-checkpoint FILE] [-recover FILE] [-gpus P [-samedevice | -torch] [-exchange exact|measured|packed] [-fanout N]] [-noprogress] [-I DIR]
-//            [-coverage [MINUTES]] [-strongfair] [-continue]
+//            [-coverage [MINUTES]] [-strongfair] [-labelfair] [-continue]
 //   mc X.tla -simulate [num=N] [-depth D] [-seed S] [-config X.cfg] [-deadlock] [-jit] [-device D] [-noprogress] [-I DIR]
 //   mc --transpile X.tla [Y.tla ...]      the `pcal2tla *tla` of the reference's Makefile:3-4: inserts (or
 //                                         replaces) the TLA+ translation of the PlusCal algorithm in place,
@@ -64,6 +64,9 @@
 // -strongfair: a `fair+ process` of a PlusCal algorithm is checked under strong fairness (MC_F_STRONGFAIR: mc_program_fairness_strong,
 //             mc_engine_liveness_strong / mc_engine_liveness_check_strong) instead of being named as NOT checked; an algorithm without
 //             `fair+` gets the report it gets without the option.  `+` / `-` labels, procedures, a VIEW and -gpus stay refused.
+// -labelfair: liveness under pcal2tla's fairness label by label (MC_F_LABELFAIR: mc_program_fairness_units, mc_engine_liveness_units /
+//             mc_engine_liveness_check_units): `fair+`, `l:-` and `l:+` labels and procedures are checked instead of being
+//             named as NOT checked; an algorithm with none of them gets the report it gets without the option.  A VIEW and -gpus stay refused.
 // -deadlock : as with TLC, do NOT check for deadlock.  -workers is accepted and ignored (the
 // GPU is the worker pool).  Exit status: 0 no error, 12 safety violation (invariant / assert),
 // 11 deadlock, 1 any other failure — TLC's convention.
@@ -457,6 +460,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-jit")) cfg.flags |= MC_F_JIT;
         else if (!strcmp(argv[i], "-unverified")) cfg.flags |= MC_F_UNVERIFIED;
         else if (!strcmp(argv[i], "-strongfair")) cfg.flags |= MC_F_STRONGFAIR;
+        else if (!strcmp(argv[i], "-labelfair")) cfg.flags |= MC_F_LABELFAIR;
         else if (arg("-I")) {  // one more directory searched for EXTENDed / INSTANCEd modules (appended to $TLA_PATH)
             const char *old = getenv("TLA_PATH");
             const std::string v = old && *old ? std::string(old) + ":" + argv[i + 1] : std::string(argv[i + 1]);
@@ -490,6 +494,8 @@ int main(int argc, char **argv) {
                 "                property is named as NOT checked, with the reason\n"
                 "                [-strongfair]                                                            ... and check a `fair+ process` under strong fairness\n"
                 "                (SF: a process enabled again and again must step) instead of naming its properties as NOT checked; `+` / `-` labels stay refused\n"
+                "                [-labelfair]                                                             ... and check under pcal2tla's fairness label by label:\n"
+                "                `fair+`, a label `l:-` (left out of its conjunct), a label `l:+` (SF of that action alone), a conjunct per procedure a fair process calls\n"
                 "                a PlusCal X.tla whose X.cfg says ACTION_CONSTRAINT A: a step that violates A is generated and its successor checked,\n"
                 "                but not stored; VIEW V (a tuple of variables and scalar expressions): a state is fingerprinted by its view, the\n"
                 "                first state to arrive stands for its view value.  As with TLC: unless equal views imply equal futures, WHICH state\n"

@@ -575,7 +575,8 @@ struct Parser {
     bool macro_call(std::vector<SP> &out) {
         size_t j = i;
         std::string label;
-        if (t[j].t == Tok::IDENT && t[j + 1].t == Tok::SYM && t[j + 1].s == ":" && j + 2 < t.size()) { label = t[j].s; j += 2; if (t[j].t == Tok::SYM && (t[j].s == "+" || t[j].s == "-")) j++; }
+        char label_mod = 0;
+        if (t[j].t == Tok::IDENT && t[j + 1].t == Tok::SYM && t[j + 1].s == ":" && j + 2 < t.size()) { label = t[j].s; j += 2; if (t[j].t == Tok::SYM && (t[j].s == "+" || t[j].s == "-")) label_mod = t[j++].s[0]; }
         if (!macros || t[j].t != Tok::IDENT || !(t[j + 1].t == Tok::SYM && t[j + 1].s == "(")) return false;
         const Macro *mac = nullptr;
         for (const auto &m : *macros) if (m.name == t[j].s) mac = &m;
@@ -593,7 +594,7 @@ struct Parser {
         for (const auto &s : mac->body) {
             SP c = subst(s, m);
             c->pos = s->k == Stmt::ASSERT ? s->pos : at;
-            if (first) c->label = label;
+            if (first) { c->label = label; c->fair_mod = label_mod; if (label_mod) saw_label_mod = true; }
             first = false;
             out.push_back(c);
         }
@@ -784,7 +785,7 @@ struct Parser {
         if (is_sym("{")) {  // a compound statement in a sequence: its statements join the sequence
             std::vector<SP> inner = c_block();
             if (inner.empty()) fail("empty compound statement");
-            if (!s->label.empty()) { if (!inner[0]->label.empty()) fail("two labels on one statement"); inner[0]->label = s->label; }
+            if (!s->label.empty()) { if (!inner[0]->label.empty()) fail("two labels on one statement"); inner[0]->label = s->label; inner[0]->fair_mod = s->fair_mod; }
             for (auto &x : inner) out.push_back(x);
             return;
         }
@@ -1350,6 +1351,7 @@ struct ProcExpander {
         std::map<std::string, Rec> rec;
     };
     std::set<std::string> recursive;   // procedures that can reach themselves through `call`
+    std::string cur_proc;              // the procedure whose body expand() is copying ("" = a process's own body): Stmt::in_proc of the copies
     static int stack_depth() {
         const char *e = getenv("TLAMC_PCAL_STACK");
         const int d = e ? atoi(e) : 4;
@@ -1471,7 +1473,10 @@ struct ProcExpander {
         if (first_call) {   // the ONE copy of the body in this process; its `return`s are IF statements filled in by finish_returns
             const std::string lsuf = rc.entry.substr(pr.body[0]->label.size());
             const std::map<std::string, std::string> inner = rc.ren;
+            const std::string caller = cur_proc;
+            cur_proc = pr.name;
             std::vector<SP> body = expand(pr.body, job, inner, lsuf, std::string(), "@" + pr.name, {});
+            cur_proc = caller;
             job.copies.insert(job.copies.end(), body.begin(), body.end());
         }
         return out;
@@ -1537,6 +1542,9 @@ struct ProcExpander {
             const std::string next = i + 1 < v.size() ? (v[i + 1]->label.empty() ? std::string() : v[i + 1]->label + lsuf) : cont;
             auto c = std::make_shared<Stmt>(*s);
             if (!c->label.empty()) c->label += lsuf;
+            if (!cur_proc.empty()) { c->in_proc = cur_proc; c->src_label = s->label; }
+            // a statement made here in the place of a labelled one keeps what the label says about fairness
+            auto tag = [&](const SP &x) { x->fair_mod = c->fair_mod; x->in_proc = c->in_proc; x->src_label = c->src_label; };
             c->e = rename(s->e, ren);
             c->idx = rename(s->idx, ren);
             if (s->k == Stmt::ASSIGN || s->k == Stmt::WITH) { auto it = ren.find(s->var); if (it != ren.end()) c->var = it->second; }
@@ -1555,6 +1563,7 @@ struct ProcExpander {
                     fail(s->pos, "`call` directly followed by `return` (pcal2tla's tail call: the frame is replaced, not pushed) is not supported: put a label on the return");
                 if (next.empty()) fail(s->pos, "the statement after a `call` must have a label (p-manual section 3.5)");
                 std::vector<SP> stmts = call(s, c->label, job, ren, next);
+                if (!stmts.empty()) tag(stmts[0]);   // (the call's label is the CALLER's)
                 out.insert(out.end(), stmts.begin(), stmts.end());
                 continue;
             }
@@ -1565,6 +1574,7 @@ struct ProcExpander {
                     ph->k = Stmt::IF;
                     ph->pos = s->pos;
                     ph->label = c->label;
+                    tag(ph);
                     out.push_back(ph);
                     job.rec[ret.substr(1)].returns.emplace_back(ph, s->pos);
                     continue;
@@ -1573,7 +1583,7 @@ struct ProcExpander {
                 for (const auto &r : reset) {
                     auto rc = std::make_shared<Stmt>(*r);
                     rc->pos = s->pos;
-                    if (first) rc->label = c->label;
+                    if (first) { rc->label = c->label; tag(rc); }
                     first = false;
                     out.push_back(rc);
                 }
@@ -1581,7 +1591,7 @@ struct ProcExpander {
                 g->k = Stmt::GOTO;
                 g->pos = s->pos;
                 g->var = ret;
-                if (first) g->label = c->label;
+                if (first) { g->label = c->label; tag(g); }
                 out.push_back(g);
                 continue;
             }
@@ -1685,7 +1695,10 @@ struct ProcExpander {
         }
         job.active.push_back(pr.name);
         std::map<std::string, std::string> inner = ren;  // (a procedure sees globals and its own variables; an enclosing procedure's are not in scope)
+        const std::string caller = cur_proc;
+        cur_proc = pr.name;
         std::vector<SP> body = expand(pr.body, job, inner, lsuf, std::string(), after, reset);
+        cur_proc = caller;
         job.active.pop_back();
         job.copies.insert(job.copies.end(), body.begin(), body.end());
         return out;
@@ -2215,6 +2228,9 @@ struct RecordFlattener {
                 for (const auto &o : s->more) assignment(*o, flat);
                 auto c = std::make_shared<Stmt>(*flat[0]);
                 c->label = s->label;
+                c->fair_mod = s->fair_mod;
+                c->in_proc = s->in_proc;
+                c->src_label = s->src_label;
                 c->more.assign(flat.begin() + 1, flat.end());
                 s = c;
                 continue;
@@ -3061,7 +3077,57 @@ void collect_labels(const std::vector<SP> &v, const std::string &cont, std::vect
 
 }  // namespace
 
-std::string translate(const Module &m) {
+std::vector<FairLabel> fair_labels(const Proc &p) {
+    std::vector<FairLabel> out;
+    std::function<void(const std::vector<SP> &)> walk = [&](const std::vector<SP> &v) {
+        for (const auto &s : v) {
+            if (!s->label.empty()) { FairLabel l; l.label = s->label; l.section = s->in_proc; l.src = s->src_label.empty() ? s->label : s->src_label; l.mod = s->fair_mod; out.push_back(l); }
+            for (const auto &b : s->blocks) walk(b);
+        }
+    };
+    walk(p.body);
+    return out;
+}
+std::vector<FairGroup> fairness_groups(const Module &m, const Proc &p) {
+    std::vector<FairGroup> out;
+    const int fair = p.fair ? p.fair : m.fair_algorithm ? 1 : 0;   // (0: label modifiers in an unfair process mean nothing)
+    const std::vector<FairLabel> ls = fair_labels(p);
+    std::vector<std::string> sections{""};   // the process's own labels, then the procedures in the order their copies appear
+    for (const auto &l : ls) if (std::find(sections.begin(), sections.end(), l.section) == sections.end()) sections.push_back(l.section);
+    for (const auto &sec : sections) {
+        FairGroup g;
+        g.strong = fair == 2;
+        g.section = sec;
+        g.whole = sec.empty() && sections.size() == 1;
+        std::vector<std::string> plus;
+        for (const auto &l : ls) {
+            if (l.section != sec) continue;
+            g.labels.push_back(l.label);
+            if (l.mod == '-') g.minus.push_back(l.label);
+            if (l.mod == '+' && fair == 1 && std::find(plus.begin(), plus.end(), l.src) == plus.end()) plus.push_back(l.src);
+        }
+        if (fair) out.push_back(g);
+        for (const auto &src : plus) {   // SF_vars(l(self)): every copy of l in this process is that one action
+            FairGroup s;
+            s.strong = true;
+            s.section = sec;
+            s.plus = src;
+            for (const auto &l : ls) if (l.section == sec && l.src == src && l.mod == '+') s.labels.push_back(l.label);
+            out.push_back(s);
+        }
+    }
+    return out;
+}
+std::string fair_group_text(const FairGroup &g, const std::string &act, const std::string &pc, const std::string &suffix) {
+    std::string a, minus;
+    if (g.whole) a = act;
+    else for (const auto &l : g.labels) a += (a.empty() ? "" : " \\/ ") + l + suffix;
+    for (const auto &l : g.minus) minus += (minus.empty() ? "\"" : ", \"") + l + "\"";
+    if (!minus.empty()) a = "(" + pc + " \\notin {" + minus + "}) /\\ " + (g.whole || g.labels.size() == 1 ? a : "(" + a + ")");
+    return std::string(g.strong ? "SF" : "WF") + "_vars(" + a + ")";
+}
+
+std::string translate(const Module &m, bool label_fair) {
     std::string o = "\\* BEGIN TRANSLATION\n";
     const bool multi = !(m.procs.size() == 1 && m.procs[0].name.empty());
     std::vector<std::string> vars;
@@ -3221,7 +3287,19 @@ std::string translate(const Module &m) {
         // (approximated for what liveness checking refuses: `+` / `-` labels do not restrict or strengthen the conjunct label by label, and
         //  procedures get no conjuncts of their own, as pcal2tla would write them)
         std::vector<std::string> fairness;
-        if (!multi) { if (m.fair_algorithm) fairness.push_back("WF_vars(Next)"); }
+        if (label_fair) {
+            // label by label: a `-` label is left out of its process's conjunct — (pc[self] \notin Minus) /\ P(self) —, a
+            // `+` label of a weakly fair process gets SF_vars(l(self)) beside it; modifiers of an unfair process and `+` under fair+ mean nothing
+            for (const auto &p : m.procs) {
+                const int fair = p.fair ? p.fair : m.fair_algorithm ? 1 : 0;
+                if (!fair) continue;
+                const bool set = multi && p.is_set;
+                const std::string q = set ? "\\A self \\in " + pe(p.id, none, empty, empty) + " : " : "";
+                const std::string act = !multi ? "Next" : set ? p.name + "(self)" : p.name;
+                const std::string pc = !multi ? "pc" : set ? "pc[self]" : "pc[" + pe(p.id, none, empty, empty) + "]";
+                for (const auto &g : fairness_groups(m, p)) fairness.push_back(q + fair_group_text(g, act, pc, set ? "(self)" : ""));
+            }
+        } else if (!multi) { if (m.fair_algorithm) fairness.push_back("WF_vars(Next)"); }
         else
             for (const auto &p : m.procs) {
                 const int fair = p.fair ? p.fair : m.fair_algorithm ? 1 : 0;
@@ -3242,8 +3320,8 @@ std::string translate(const Module &m) {
     return o;
 }
 
-std::string transpile_text(const std::string &text, const Module &m) {
-    const std::string tr = translate(m);
+std::string transpile_text(const std::string &text, const Module &m, bool label_fair) {
+    const std::string tr = translate(m, label_fair);
     if (m.has_translation) {
         const size_t b = find_line_start(text, m.tr_first_line);
         size_t e = find_line_start(text, m.tr_last_line + 1);

@@ -34,6 +34,8 @@ struct Stmt {
     enum K { ASSIGN, IF, WHILE, EITHER, WITH, AWAIT, ASSERT, SKIP, GOTO, PRINT, CALL, RETURN } k = SKIP;
     std::string label;                     // "" = unlabeled
     char fair_mod = 0;                     // the label's fairness modifier: '+' (`l:+`), '-' (`l:-`) or 0
+    std::string in_proc, src_label;        // a statement of a procedure's body copied into a process (expand_procedures): the procedure,
+                                           // and the label as the procedure wrote it (every copy of `l` is one action l(self) of pcal2tla)
     Pos pos;                               // of the statement keyword / lhs (asserts print it)
     std::string var;                       // ASSIGN lhs, WITH variable, GOTO target
     EP idx;                                // ASSIGN lhs index (x[i] := e), may be null
@@ -173,10 +175,21 @@ struct Module {
 std::string parse_module(const std::string &text, Module &out);
 
 // The text `pcal2tla` inserts: from "\* BEGIN TRANSLATION" to "\* END TRANSLATION" inclusive, '\n' terminated.
-std::string translate(const Module &m);
+// Fairness label by label: the conjuncts pcal2tla gives one process — its own (the labels of its body, without the
+// copies of procedure bodies), one per procedure it reaches, one SF per `+` label of a weakly fair process (all copies of the label
+// together) — as sets of the translation's labels; empty for an unfair process.  minus: the `-` labels among `labels`, restricted away.
+// whole: the process's own conjunct when it reaches no procedure: the action is the process's (P(self), Next), not a disjunction.
+struct FairGroup { bool strong = false, whole = false; std::string section, plus; std::vector<std::string> labels, minus; };
+struct FairLabel { std::string label, section, src; char mod = 0; };
+std::vector<FairLabel> fair_labels(const Proc &p);
+std::vector<FairGroup> fairness_groups(const Module &m, const Proc &p);
+// act: the process's action; pc: its pc cell; suffix: "(self)" / "(<id>)" / "" after a label's name
+std::string fair_group_text(const FairGroup &g, const std::string &act, const std::string &pc, const std::string &suffix);
+// label_fair: Spec's fairness conjuncts as pcal2tla writes them for `+` / `-` labels instead of one per process
+std::string translate(const Module &m, bool label_fair = false);
 
 // The whole module with the translation inserted after the algorithm comment (replacing an existing one).
-std::string transpile_text(const std::string &text, const Module &m);
+std::string transpile_text(const std::string &text, const Module &m, bool label_fair = false);
 
 // ------------------------------------------------------------------------------------------------
 // Compilation to the stack machine of spec_vm.h.
@@ -228,6 +241,16 @@ struct Program {
     // the same for the strong checks: the `fair+` instances among fair_mask's, and the refusal with `fair+` allowed
     unsigned long long strong_mask = 0;
     std::string live_refusal_strong;
+    // fairness label by label: pcal2tla's conjuncts exactly.  unit_of[inst * nlabels + label] = the unit of an edge
+    // instance `inst` takes from a state where it stands at `label` (the instance's own unit for "Done" and for a label of another process); units 0 .. ninst - 1 are the
+    // instances' own ("the remaining labels of the process body"), the units of `-` label sets and of single `+` labels follow.
+    // conj_of_unit[u] = the conjuncts unit u belongs to; fair_conj[k]: conjunct k, weak or strong, as text for its instance.
+    struct FairConj { bool strong = false; std::string text; };
+    std::vector<signed char> unit_of;
+    std::vector<unsigned long long> conj_of_unit;
+    std::vector<FairConj> fair_conj;
+    std::string live_refusal_units;       // "" = the checks by units decide this program's properties; else why not
+    std::string translated_labelfair;     // `translated` with the conjuncts above in Spec (the same text for a program without these forms)
     // the cfg's other temporal properties.  live_preds: the distinct state predicates they are made of, compiled after the
     // INVARIANTs and CONSTRAINTs into the same image but never run by the search (a table of their own: the entries are not in the header).
     // live_props: one entry per check — a quantifier instance of a conjunct of a named definition — or per refused name.

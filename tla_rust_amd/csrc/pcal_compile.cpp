@@ -1955,6 +1955,69 @@ struct Compiler {
             if (m.had_procedures) P.live_refusal = P.live_refusal_strong = "the algorithm has procedures (their actions get fairness conjuncts of their own)";
             if (insts.size() > 64) P.live_refusal = P.live_refusal_strong = "more than 64 process instances";
         }
+        {   // fairness label by label: the units of the edges and pcal2tla's conjuncts, per instance in the slot order
+            auto id_text = [&](const Inst &x) -> std::string {   // the instance's identifier as the translation's text can name it
+                const EP &e = x.p->id;
+                if (!e) return "0";
+                const EP *at = nullptr;
+                if (x.p->is_set && e->k == Expr::SETENUM) { const auto &ids = ids_of[x.p]; for (size_t k = 0; k < ids.size() && k < e->a.size(); k++) if (ids[k] == x.self) at = &e->a[k]; }
+                else if (!x.p->is_set) at = &e;
+                if (at && (*at)->k == Expr::STR) return "\"" + (*at)->s + "\"";
+                if (at && (*at)->k == Expr::ID) return (*at)->s;
+                return std::to_string(x.self);
+            };
+            const size_t nl = (size_t)P.nlabels;
+            P.unit_of.assign(insts.size() * nl, (signed char)-1);
+            for (size_t k = 0; k < insts.size() && k < 127; k++)   // every label the loop below does not set ("Done", another process's): the instance's own unit
+                for (size_t l = 0; l < nl; l++) P.unit_of[k * nl + l] = (signed char)k;
+            size_t nunits = insts.size();          // unit k = "the remaining labels" of instance k
+            std::vector<unsigned long long> of_unit(insts.size(), 0);
+            size_t overflow_conj = 0;
+            auto new_conj = [&](bool strong, const std::string &text) -> unsigned long long {
+                if (P.fair_conj.size() >= 64) { ++overflow_conj; return 0; }
+                Program::FairConj c;
+                c.strong = strong;
+                c.text = text;
+                P.fair_conj.push_back(c);
+                return 1ull << (P.fair_conj.size() - 1);
+            };
+            auto set_unit = [&](size_t k, const std::string &label, size_t u) { if (nl && u < 128) P.unit_of[k * nl + (size_t)str_id[label]] = (signed char)u; };
+            for (size_t k = 0; k < insts.size(); k++) {
+                const Proc &pr = *insts[k].p;
+                const int fair = pr.fair ? pr.fair : m.fair_algorithm ? 1 : 0;
+                const bool set = P.multi && pr.is_set;
+                const std::string self = id_text(insts[k]);
+                const std::string act = !P.multi ? "Next" : set ? pr.name + "(" + self + ")" : pr.name;
+                const std::string pc = !P.multi ? "pc" : "pc[" + self + "]";
+                // the conjuncts of this instance, and for every label the conjuncts whose action a step from it is
+                const std::vector<FairGroup> groups = fairness_groups(m, pr);
+                std::vector<unsigned long long> bit;
+                for (const auto &g : groups) bit.push_back(new_conj(g.strong, fair_group_text(g, act, pc, set ? "(" + self + ")" : "")));
+                if (fair && !groups.empty()) of_unit[k] = bit[0];   // (unit k is in the process's own conjunct, whether a label is left for it or not)
+                // units: the instance's own remaining labels (unit k), the `-` labels of one action set, each `+` label of a weakly fair
+                // process (all its copies), the remaining labels of each procedure
+                std::map<std::string, size_t> unit_of_key;
+                for (const auto &l : fair_labels(pr)) {
+                    const std::string cls = !fair ? "" : l.mod == '-' ? "-" : l.mod == '+' && fair == 1 ? "+" + l.src : "";
+                    const std::string key = !fair ? "" : l.section + "|" + cls;   // (an unfair process: one unit, in no conjunct)
+                    size_t u = k;
+                    if (key != "" && key != "|") {
+                        auto it = unit_of_key.find(key);
+                        if (it == unit_of_key.end()) { it = unit_of_key.emplace(key, nunits++).first; of_unit.push_back(0); }
+                        u = it->second;
+                    }
+                    for (size_t gi = 0; gi < groups.size(); gi++) {
+                        const FairGroup &g = groups[gi];
+                        if (std::find(g.labels.begin(), g.labels.end(), l.label) != g.labels.end() && std::find(g.minus.begin(), g.minus.end(), l.label) == g.minus.end())
+                            of_unit[u] |= bit[gi];
+                    }
+                    set_unit(k, l.label, u);
+                }
+            }
+            P.conj_of_unit = of_unit;
+            if (overflow_conj) P.live_refusal_units = std::to_string(64 + overflow_conj) + " fairness conjuncts (at most 64)";
+            else if (nunits > 127) P.live_refusal_units = std::to_string(nunits) + " fairness units (at most 127)";
+        }
         // variables: globals, pc, process locals (the VARIABLES order of the translation)
         int nv = 0;
         auto add_var = [&](const std::string &name, bool array, const std::vector<long long> &ids, char type) {
@@ -2148,6 +2211,7 @@ struct Compiler {
         // ---- the cfg's ACTION_CONSTRAINTs and VIEW
         cur_nv = nv;
         cfg_more();
+        if (!P.view.empty()) P.live_refusal_units = "the cfg has a VIEW (the graph is one of representative states: fairness over it is not the spec's)";
         if (!P.view.empty()) P.live_refusal = P.live_refusal_strong = "the cfg has a VIEW (the graph is one of representative states: fairness over it is not the spec's)";
         // ---- header
         c[mc::VMH_MAGIC] = mc::VM_MAGIC;
@@ -2199,6 +2263,7 @@ std::string compile(const Module &m, const std::string &module_text, const Confi
     const std::string tr = translate(m);
     if (tr.rfind("\\* TRANSLATION ERROR: ", 0) == 0) return tr.substr(strlen("\\* TRANSLATION ERROR: "), tr.size() - strlen("\\* TRANSLATION ERROR: ") - 1);
     out.translated = transpile_text(module_text, m);
+    out.translated_labelfair = transpile_text(module_text, m, true);
     try {
         Compiler cc(m, cfg, out);
         cc.run();
@@ -2314,6 +2379,13 @@ int vm_live_preds(const void *host, int *entries, int cap) {
     const pcal::Program &P = *(const pcal::Program *)host;
     for (int k = 0; entries && k < cap && (size_t)k < P.live_preds.size(); k++) entries[k] = P.live_preds[(size_t)k].entry;
     return (int)P.live_preds.size();
+}
+int vm_live_units(const void *host, int *ninst, int *nlabels, int8_t *unit_out, int cap) {
+    const pcal::Program &P = *(const pcal::Program *)host;
+    if (ninst) *ninst = P.ninst;
+    if (nlabels) *nlabels = P.nlabels;
+    for (size_t k = 0; unit_out && k < P.unit_of.size() && k < (size_t)cap; k++) unit_out[k] = (int8_t)P.unit_of[k];
+    return (int)P.conj_of_unit.size();
 }
 const char *vm_live_pred_text(const void *host, int k) {
     const pcal::Program &P = *(const pcal::Program *)host;

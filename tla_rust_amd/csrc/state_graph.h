@@ -73,12 +73,19 @@ struct StateGraph {
         DevBuf<uint8_t> open;                  // [states] LIVE_ST_*: closed, open or in a final component
         DevBuf<uint32_t> fscc, fsize;          // [states] the refined ids (a closed state: its own index) and, at an id, the size
         DevBuf<uint32_t> wscc, wsize;          // [states] the components of the open subgraph, rounds >= 2
+        // what mc_engine_liveness_units / mc_engine_liveness_check_units add
+        bool last_units = false;               // the last check read proc[] as units: fair / strong are masks of conjuncts
+        bool unit_built = false;
+        DevBuf<int8_t> unit;                   // [edges] beside proc: the edge's unit (k_live_unit<S>), LIVE_TERM for the terminating disjunct
+        DevBuf<uint64_t> of_unit;              // [LIVE_UNIT_TAB] the conjuncts of every unit, as the kernels stage it
+        std::vector<uint64_t> of_unit_host;    // the same, for the counterexample builder
         void release() {
             scc_built = checked = pred_built = proc_built = false;
             toff.reset(); tsrc.reset(); scc.reset(); size.reset(); proc.reset(); taken.reset(); disabled.reset(); done.reset();
             pred.reset(); dist.reset(); masks.clear(); descent.clear();
             enabled.reset(); open.reset(); fscc.reset(); fsize.reset(); wscc.reset(); wsize.reset();
             last_kind = -1; last_mask = nullptr; last_strong = false; strong = 0;
+            last_units = unit_built = false; unit.reset(); of_unit.reset(); of_unit_host.clear();
         }
     } lv;
     void release() { built = false; offsets.reset(); dst.reset(); act.reset(); lv.release(); }
@@ -99,9 +106,12 @@ struct StateGraph {
     int live_check_masked(uint64_t all, uint64_t fair, int kind, int p, int q, hipStream_t stream, std::chrono::steady_clock::time_point started,
                           mc_live_check_info *out);
     // mc_engine_liveness_strong (kind < 0: lout) / mc_engine_liveness_check_strong (cout), after the same preparation as the weak twins
+    // of_unit (mc_engine_liveness_units / mc_engine_liveness_check_units): lv.unit is read in lv.proc's place, the masks are over conjuncts
     int live_check_strong(uint64_t all, uint64_t weak, uint64_t strong, int kind, int p, int q, hipStream_t stream,
-                          std::chrono::steady_clock::time_point started, mc_live_info *lout, mc_live_check_info *cout, mc_live_strong_info *sout);
+                          std::chrono::steady_clock::time_point started, mc_live_info *lout, mc_live_check_info *cout, mc_live_strong_info *sout,
+                          const uint64_t *of_unit = nullptr);
     int live_scc_read(uint64_t first, uint64_t count, uint32_t *scc_out);   // mc_engine_liveness_components
+    int live_unit_read(uint64_t first, uint64_t count, int8_t *unit_out);   // mc_engine_liveness_edge_units
     int live_trace(const std::vector<uint64_t> &level_start, uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout);
 
 private:

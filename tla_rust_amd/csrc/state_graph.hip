@@ -195,6 +195,7 @@ int StateGraph::live_check(uint64_t all, uint64_t fair, hipStream_t stream, std:
     lv.fair = fair;
     lv.strong = 0;
     lv.last_strong = false;
+    lv.last_units = false;
     lv.checked = true;
     lv.last_kind = -1;
     lv.last_mask = nullptr;
@@ -207,6 +208,13 @@ int StateGraph::live_scc_read(uint64_t first, uint64_t count, uint32_t *scc_out)
     if (first > info.states || count > info.states - first) { set_error("mc_engine_liveness_components: range beyond the graph's states"); return MC_EBADCFG; }
     HIP_TRY(hipSetDevice(device));
     if (count) HIP_TRY(hipMemcpy(scc_out, (lv.last_strong ? lv.fscc.p : lv.last_mask ? lv.last_mask->scc.p : lv.scc.p) + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+int StateGraph::live_unit_read(uint64_t first, uint64_t count, int8_t *unit_out) {
+    if (!built || !lv.unit_built) { set_error("mc_engine_liveness_edge_units: no units (mc_engine_liveness_units / mc_engine_liveness_check_units fill them; the next search releases them)"); return MC_ESTATE; }
+    if (first > info.edges || count > info.edges - first) { set_error("mc_engine_liveness_edge_units: range beyond the graph's edges"); return MC_EBADCFG; }
+    HIP_TRY(hipSetDevice(device));
+    if (count) HIP_TRY(hipMemcpy(unit_out, lv.unit.p + first, count * sizeof(int8_t), hipMemcpyDeviceToHost));
     return MC_OK;
 }
 int StateGraph::pred_read(uint64_t first, uint64_t count, uint32_t *bits_out) {
@@ -246,6 +254,7 @@ int StateGraph::live_check_masked(uint64_t all, uint64_t fair, int kind, int p, 
     int rc;
     uint32_t builds = 0;
     lv.checked = false;
+    lv.last_units = false;
     // ---- the components of G[M]: the full graph's for <>[]P, else one build per predicate that masks
     const Live::Masked *mask = nullptr;
     if ((rc = live_mask_components(kind, q, stream, &mask, &builds))) return rc;
@@ -355,15 +364,27 @@ int StateGraph::live_reach_tail(const LiveCheck &ck, const uint32_t *scc, const 
 // Termination (M = all, T = not Done; lout), else the (M, S, T) check of live_check_masked (cout).  Round 1 runs on the components a
 // weak check of the same M uses — lv.scc, or the mask's build, made and kept here as live_check_masked does —, later rounds on builds of
 // the open subgraph into lv.wscc / lv.wsize; nothing a weak check reads is written.  One blocking read per round beside the build's.
+// of_unit (LIVE_UNIT_TAB entries on the host, or null): lv.unit holds the edges' UNITS, the masks are masks of
+// fairness conjuncts, and the table-driven twins of the three kernels that read the edges are launched; null launches what it launched.
 int StateGraph::live_check_strong(uint64_t all, uint64_t weak, uint64_t strong, int kind, int p, int q, hipStream_t stream,
-                                  std::chrono::steady_clock::time_point started, mc_live_info *lout, mc_live_check_info *cout, mc_live_strong_info *sout) {
+                                  std::chrono::steady_clock::time_point started, mc_live_info *lout, mc_live_check_info *cout, mc_live_strong_info *sout,
+                                  const uint64_t *of_unit) {
     const uint64_t n = info.states, cells = n ? n : 1;
-    const bool term = kind < 0;
+    const bool term = kind < 0, units = of_unit != nullptr;
     const LiveCheck ck{term ? LIVE_STABLE : kind, p, q};   // (Termination: every state is in M; the target is the Done flag's, not a predicate's)
-    const char *call = term ? "mc_engine_liveness_strong" : "mc_engine_liveness_check_strong";
+    const char *call = units ? (term ? "mc_engine_liveness_units" : "mc_engine_liveness_check_units")
+                             : (term ? "mc_engine_liveness_strong" : "mc_engine_liveness_check_strong");
     int rc;
     uint32_t builds = 0;
     lv.checked = false;
+    lv.last_units = units;
+    if (units) {
+        lv.of_unit_host.assign(of_unit, of_unit + LIVE_UNIT_TAB);
+        if ((rc = graph_alloc(lv.of_unit, LIVE_UNIT_TAB, "the units' conjuncts", call))) return rc;
+        HIP_TRY(hipMemcpyAsync(lv.of_unit, lv.of_unit_host.data(), LIVE_UNIT_TAB * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    }
+    const uint64_t *d_tab = lv.of_unit.p;
+    const int8_t *edge_class = units ? lv.unit.p : lv.proc.p;   // (the units have an array of their own: proc[] stays what a process-level check reads)
     const Live::Masked *mask = nullptr;
     if (!term && (rc = live_mask_components(kind, q, stream, &mask, &builds))) return rc;
     const uint32_t *pred = term ? nullptr : lv.pred.p;
@@ -394,28 +415,44 @@ int StateGraph::live_check_strong(uint64_t all, uint64_t weak, uint64_t strong, 
         HIP_TRY(hipMemsetAsync(lv.done, 0, cells * sizeof(unsigned), stream));
         HIP_TRY(hipMemsetAsync(lv.enabled, 0, cells * sizeof(unsigned long long), stream));
         HIP_TRY(hipMemsetAsync(&d_sc.p->open, 0, sizeof(unsigned), stream));
-        if (term)
-            live_launch(stream, k_live_reduce<false>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, (const int8_t *)lv.proc.p, scc, size, all,
+        if (units && term)
+            live_launch(stream, k_live_reduce_units<false>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size, all,
+                        lv.taken.p, lv.disabled.p, lv.done.p, pred, ck, d_tab);
+        else if (units)
+            live_launch(stream, k_live_reduce_units<true>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size, all,
+                        lv.taken.p, lv.disabled.p, lv.done.p, pred, ck, d_tab);
+        else if (term)
+            live_launch(stream, k_live_reduce<false>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size, all,
                         lv.taken.p, lv.disabled.p, lv.done.p, pred, ck);
         else
-            live_launch(stream, k_live_reduce<true>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, (const int8_t *)lv.proc.p, scc, size, all,
+            live_launch(stream, k_live_reduce<true>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size, all,
                         lv.taken.p, lv.disabled.p, lv.done.p, pred, ck);
-        live_launch(stream, k_live_enabled, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, (const int8_t *)lv.proc.p, scc, size,
-                    (const uint8_t *)lv.open.p, lv.enabled.p);
+        if (units)
+            live_launch(stream, k_live_enabled_units, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size,
+                        (const uint8_t *)lv.open.p, lv.enabled.p, d_tab);
+        else
+            live_launch(stream, k_live_enabled, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size,
+                        (const uint8_t *)lv.open.p, lv.enabled.p);
         live_launch(stream, k_live_classify, n, scc, size, (const uint8_t *)lv.open.p, (const unsigned long long *)lv.taken.p,
                     (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p, (const unsigned long long *)lv.enabled.p, all, weak, strong, term,
                     d_sc.p);
-        live_launch(stream, k_live_refine, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, (const int8_t *)lv.proc.p, scc, size,
-                    (const unsigned long long *)lv.taken.p, (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p,
-                    (const unsigned long long *)lv.enabled.p, all, weak, strong, term, lv.open.p, lv.fscc.p, lv.fsize.p, term ? (uint32_t *)nullptr : lv.dist.p,
-                    d_sc.p);
+        if (units)
+            live_launch(stream, k_live_refine_units, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size,
+                        (const unsigned long long *)lv.taken.p, (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p,
+                        (const unsigned long long *)lv.enabled.p, all, weak, strong, term, lv.open.p, lv.fscc.p, lv.fsize.p,
+                        term ? (uint32_t *)nullptr : lv.dist.p, d_sc.p, d_tab);
+        else
+            live_launch(stream, k_live_refine, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size,
+                        (const unsigned long long *)lv.taken.p, (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p,
+                        (const unsigned long long *)lv.enabled.p, all, weak, strong, term, lv.open.p, lv.fscc.p, lv.fsize.p, term ? (uint32_t *)nullptr : lv.dist.p,
+                        d_sc.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&sc, d_sc, sizeof sc, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         if (!sc.open) break;
         if (rounds >= bound) {
             set_error(std::string(call) + ": the refinement did not converge after " + std::to_string(rounds) + " rounds (" + std::to_string(bound - 1) +
-                      " strongly fair processes)");
+                      (units ? " strong conjuncts)" : " strongly fair processes)"));
             return MC_ESTATE;
         }
         mc_scc_info si;
@@ -461,7 +498,8 @@ int StateGraph::live_check_strong(uint64_t all, uint64_t weak, uint64_t strong, 
 // lv.descent to the first state of the component —, one BFS level back per step along the transpose: the
 // least source in the previous level (level boundaries: level_start).  cycle: a closed walk inside the component that starts at
 // that state and, for every weakly fair process, takes a real step of it or passes a state where it is disabled; the last entry has an
-// edge back to the first.  Empty = the behaviour stutters in the prefix's last state for ever.
+// edge back to the first.  Empty = the behaviour stutters in the prefix's last state for ever.  After a check by units (DESIGN section
+// 21) "process" reads "conjunct": a step of it is an edge whose unit belongs to it.
 int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout) {
     if (!built || !lv.checked) { set_error("mc_engine_liveness_trace: no liveness check (mc_engine_liveness runs it; the next search releases it)"); return MC_ESTATE; }
     if (!lv.linfo.violated) { set_error("mc_engine_liveness_trace: the property holds: there is no counterexample"); return MC_ESTATE; }
@@ -496,8 +534,10 @@ int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *p
     HIP_TRY(hipMemcpy(scc.data(), lv.last_strong ? lv.fscc.p : prop && lv.last_mask ? lv.last_mask->scc.p : lv.scc.p, scc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (edges) {
         HIP_TRY(hipMemcpy(dst.data(), this->dst.p, dst.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(proc.data(), lv.proc.p, proc.size() * sizeof(int8_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(proc.data(), lv.last_units ? lv.unit.p : lv.proc.p, proc.size() * sizeof(int8_t), hipMemcpyDeviceToHost));
     }
+    const uint64_t *tab = lv.last_units ? lv.of_unit_host.data() : nullptr;
+    auto counts_for = [&](int8_t pr, int p) { return tab ? (live_conjuncts(tab, pr) >> p & 1) != 0 : pr == p; };   // is an edge of pr a step of p
     std::vector<uint32_t> members;
     for (uint64_t v = 0; v < n; ++v) if (scc[(size_t)v] == root) members.push_back((uint32_t)v);
     std::vector<uint32_t> par((size_t)n, ~0u);
@@ -528,7 +568,7 @@ int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *p
         for (size_t mi = 0; mi < members.size() && !found; ++mi) {   // a real step of p inside the component: the first in index order
             const uint32_t u = members[mi];
             for (uint64_t k = off[u]; k < off[u + 1] && !found; ++k)
-                if (proc[(size_t)k] == p && live_real_step(p, u, dst[(size_t)k]) && scc[dst[(size_t)k]] == root) {
+                if (counts_for(proc[(size_t)k], p) && live_real_step(proc[(size_t)k], u, dst[(size_t)k]) && scc[dst[(size_t)k]] == root) {
                     found = true;
                     ok = go(u);
                     cycle.push_back(dst[(size_t)k]);
@@ -539,7 +579,8 @@ int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *p
             const uint32_t u = members[mi];
             uint64_t en = 0, tk = 0;
             bool dn = false;
-            live_state(u, dst.data() + off[u], proc.data() + off[u], off[u + 1] - off[u], scc.data(), &en, &tk, &dn);
+            if (tab) live_state_units(u, dst.data() + off[u], proc.data() + off[u], off[u + 1] - off[u], scc.data(), tab, &en, &tk, &dn);
+            else live_state(u, dst.data() + off[u], proc.data() + off[u], off[u + 1] - off[u], scc.data(), &en, &tk, &dn);
             if (!(en >> p & 1)) { found = true; ok = go(u); }
         }
         if (!found) ok = false;
