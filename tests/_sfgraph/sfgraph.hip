@@ -5,29 +5,11 @@
 
 extern "C" {
 
-// engine.hip's liveness_strong / liveness_check_strong: the masks' conditions, the weak twins' preparation, then the call
-static int sf_masks(uint64_t all, uint64_t weak, uint64_t strong, const char *call) {
-    if ((weak | strong) & ~all) { mc::set_error(std::string(call) + ": a fairness mask names a process instance the program does not have"); return MC_EBADCFG; }
-    if (weak & strong) { mc::set_error(std::string(call) + ": the weak and the strong mask overlap"); return MC_EBADCFG; }
-    return MC_OK;
-}
 int sf_live_strong(void *h, uint64_t all, uint64_t weak, uint64_t strong, mc_live_info *out, mc_live_strong_info *sout) {
-    Sg &s = *(Sg *)h;
-    memset(out, 0, sizeof *out);
-    memset(sout, 0, sizeof *sout);
-    if (int rc = sf_masks(all, weak, strong, "sf_live_strong")) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int rc = prepare(s, true, false, "sf_live_strong")) return rc;
-    return s.g.live_check_strong(all, weak, strong, -1, -1, -1, s.stream, t0, out, nullptr, sout);
+    return check(*(Sg *)h, mc::LiveQuery{"sf_live_strong", all, weak, strong, nullptr, -1, -1, -1, true}, out, nullptr, sout);
 }
 int sf_live_check_strong(void *h, uint64_t all, uint64_t weak, uint64_t strong, int kind, int p, int q, mc_live_check_info *out, mc_live_strong_info *sout) {
-    Sg &s = *(Sg *)h;
-    memset(out, 0, sizeof *out);
-    memset(sout, 0, sizeof *sout);
-    if (int rc = sf_masks(all, weak, strong, "sf_live_check_strong")) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int rc = prepare(s, false, true, "sf_live_check_strong")) return rc;
-    return s.g.live_check_strong(all, weak, strong, kind, p, q, s.stream, t0, nullptr, out, sout);
+    return check(*(Sg *)h, mc::LiveQuery{"sf_live_check_strong", all, weak, strong, nullptr, kind, p, q, true}, nullptr, out, sout);
 }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 // sgraph.hip — a test-only driver of mc::StateGraph (tla_rust_amd/csrc/state_graph.h): it hands the product's state_graph.hip, compiled
 // beside it into a library of its own, CSR arrays that no search of a model produced (tests/sgraph.py, tests/randgraph.py).  No kernel
 // lives here and nothing of libtlamc.so is linked: what runs on the device is engine_live.h alone.  The order of the calls is the
-// engine's (engine.hip: liveness, liveness_check, predicates_build): the components first — StateGraph::scc() releases lv.proc and
-// lv.pred —, then the edges' processes and the predicate bits, uploaded here where the engine enqueues k_live_proc / k_live_pred.
+// engine's (engine.hip: liveness_run, predicates_build): the components first — StateGraph::scc() releases lv.proc and lv.pred —,
+// then the edges' processes and the predicate bits, uploaded here where the engine enqueues k_live_proc / k_live_pred, once per
+// component build; then StateGraph::live_check, whose refusals of a bad query (live_query.h) are the product's own.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -62,23 +63,39 @@ int create(Sg &s, uint64_t n, uint64_t edges, uint64_t init_states, const uint64
     return MC_OK;
 }
 
-// engine.hip's liveness / liveness_check up to the call into StateGraph
-int prepare(Sg &s, bool fresh_proc, bool want_pred, const char *call) {
+int pred_bits(Sg &s) {
+    auto &lv = s.g.lv;
+    if (lv.pred_built) return MC_OK;
+    HIP_TRY(hipSetDevice(s.g.device));
+    if (int rc = upload(lv.pred, s.pred.data(), s.g.info.states, "the predicate bits")) return rc;
+    lv.pred_built = true;
+    lv.npred = mc::LIVE_MAX_PREDS;   // (every bit of a word may be a predicate's)
+    return MC_OK;
+}
+// engine.hip's liveness_run up to the call into StateGraph: the components, then what the query reads and the graph does not hold yet
+int prepare(Sg &s, bool want_pred, const char *call) {
     if (!s.has_proc) { mc::set_error(std::string(call) + ": the graph was created without the edges' processes"); return MC_EBADCFG; }
     if (want_pred && !s.has_pred) { mc::set_error(std::string(call) + ": the graph was created without predicate bits"); return MC_EBADCFG; }
     auto &lv = s.g.lv;
     if (!lv.scc_built) { mc_scc_info si; if (int rc = s.g.scc(s.stream, &si)) return rc; }
-    lv.checked = false;
     HIP_TRY(hipSetDevice(s.g.device));
-    if (fresh_proc || !lv.proc_built) {
+    if (!lv.proc_built) {
         if (int rc = upload(lv.proc, s.proc.data(), s.g.info.edges, "the edges' processes")) return rc;
         lv.proc_built = true;
     }
-    if (want_pred && !lv.pred_built) {
-        if (int rc = upload(lv.pred, s.pred.data(), s.g.info.states, "the predicate bits")) return rc;
-        lv.pred_built = true;
-    }
-    return MC_OK;
+    return want_pred ? pred_bits(s) : MC_OK;
+}
+// one check: the outputs that apply zeroed, the preparation — `more`: what a driver built on this one adds to it —, then the product's
+// one entry (which refuses a bad query)
+int check(Sg &s, const mc::LiveQuery &q, mc_live_info *lout, mc_live_check_info *cout, mc_live_strong_info *sout,
+          int (*more)(Sg &, const mc::LiveQuery &) = nullptr) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (lout) memset(lout, 0, sizeof *lout);
+    if (cout) memset(cout, 0, sizeof *cout);
+    if (sout) memset(sout, 0, sizeof *sout);
+    if (int rc = prepare(s, cout != nullptr, q.call)) return rc;
+    if (more) if (int rc = more(s, q)) return rc;
+    return s.g.live_check(q, s.stream, t0, lout, cout, sout);
 }
 
 }  // namespace
@@ -98,25 +115,15 @@ int sg_scc_read(void *h, uint64_t first, uint64_t count, uint32_t *out) { return
 int sg_live_scc_read(void *h, uint64_t first, uint64_t count, uint32_t *out) { return ((Sg *)h)->g.live_scc_read(first, count, out); }
 
 int sg_live_check(void *h, uint64_t all, uint64_t fair, mc_live_info *out) {
-    Sg &s = *(Sg *)h;
-    memset(out, 0, sizeof *out);
-    if (int rc = prepare(s, true, false, "sg_live_check")) return rc;
-    return s.g.live_check(all, fair, s.stream, std::chrono::steady_clock::now(), out);
+    return check(*(Sg *)h, mc::LiveQuery{"sg_live_check", all, fair, 0, nullptr, -1, -1, -1, false}, out, nullptr, nullptr);
 }
 int sg_live_check_masked(void *h, uint64_t all, uint64_t fair, int kind, int p, int q, mc_live_check_info *out) {
-    Sg &s = *(Sg *)h;
-    memset(out, 0, sizeof *out);
-    if (int rc = prepare(s, false, true, "sg_live_check_masked")) return rc;
-    return s.g.live_check_masked(all, fair, kind, p, q, s.stream, std::chrono::steady_clock::now(), out);
+    return check(*(Sg *)h, mc::LiveQuery{"sg_live_check_masked", all, fair, 0, nullptr, kind, p, q, false}, nullptr, out, nullptr);
 }
 // (as mc_engine_predicates: the bits are there once a check, or this call, has put them there)
 int sg_pred_read(void *h, uint64_t first, uint64_t count, uint32_t *out) {
     Sg &s = *(Sg *)h;
-    if (s.has_pred && !s.g.lv.pred_built) {
-        HIP_TRY(hipSetDevice(s.g.device));
-        if (int rc = upload(s.g.lv.pred, s.pred.data(), s.g.info.states, "the predicate bits")) return rc;
-        s.g.lv.pred_built = true;
-    }
+    if (s.has_pred) if (int rc = pred_bits(s)) return rc;
     return s.g.pred_read(first, count, out);
 }
 int sg_live_trace(void *h, const uint64_t *level_start, size_t nlevels, uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout) {

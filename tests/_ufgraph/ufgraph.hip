@@ -6,26 +6,12 @@
 
 #include <map>
 
-#include "liveness.h"
-
 namespace {
 std::map<void *, std::vector<int8_t>> g_units;   // per handle: the edges' units (uf_set_units), uploaded where the engine enqueues k_live_unit
 }
 
 extern "C" {
 
-// engine.hip's units_prepare: the table's conditions
-static int uf_table(const mc_fair_units *fu, const char *call) {
-    const std::string c(call);
-    if (fu->nunits < 0 || fu->nunits > mc::LIVE_MAX_UNITS) { mc::set_error(c + ": " + std::to_string(fu->nunits) + " units (at most 127)"); return MC_EBADCFG; }
-    if (fu->nconj < 0 || fu->nconj > mc::LIVE_MAX_CONJ) { mc::set_error(c + ": " + std::to_string(fu->nconj) + " conjuncts (at most 64)"); return MC_EBADCFG; }
-    const uint64_t all = mc::live_all_conjuncts(fu->nconj);
-    if ((fu->weak_mask | fu->strong_mask) & ~all) { mc::set_error(c + ": a fairness mask names a conjunct beyond nconj"); return MC_EBADCFG; }
-    if (fu->weak_mask & fu->strong_mask) { mc::set_error(c + ": the weak and the strong mask overlap (a conjunct is WF or SF)"); return MC_EBADCFG; }
-    for (int u = 0; u < mc::LIVE_UNIT_TAB; ++u)
-        if (fu->of_unit[u] & (u < fu->nunits ? ~all : ~0ull)) { mc::set_error(c + ": of_unit[" + std::to_string(u) + "] names a conjunct it cannot"); return MC_EBADCFG; }
-    return MC_OK;
-}
 int uf_set_units(void *h, const int8_t *unit) {
     Sg &s = *(Sg *)h;
     for (uint64_t k = 0; k < s.g.info.edges; ++k)
@@ -34,13 +20,15 @@ int uf_set_units(void *h, const int8_t *unit) {
     return MC_OK;
 }
 void uf_destroy(void *h) { g_units.erase(h); sg_destroy(h); }
-static int uf_prepare(Sg &s, void *h, const mc_fair_units *fu, bool want_pred, const char *call) {
-    if (int rc = uf_table(fu, call)) return rc;
-    auto it = g_units.find(h);
-    if (it == g_units.end()) { mc::set_error(std::string(call) + ": the graph has no units (uf_set_units)"); return MC_EBADCFG; }
+// what sgraph.hip's check does more for a check by units: the edges' units beside the edges' processes (proc[] stays what a
+// process-level check reads).  The query is refused first, and by the product (live_query.h): the look at the units reads a table
+// that is in range.
+static int uf_units(Sg &s, const mc::LiveQuery &q) {
+    if (int rc = mc::live_query_check(q, mc::LIVE_MAX_PREDS)) return rc;
+    auto it = g_units.find((void *)&s);
+    if (it == g_units.end()) { mc::set_error(std::string(q.call) + ": the graph has no units (uf_set_units)"); return MC_EBADCFG; }
     for (int8_t u : it->second)
-        if (u >= fu->nunits) { mc::set_error(std::string(call) + ": an edge's unit is beyond nunits"); return MC_EBADCFG; }
-    if (int rc = prepare(s, false, want_pred, call)) return rc;   // (the components; proc[] stays what a process-level check reads)
+        if (u >= q.fu->nunits) { mc::set_error(std::string(q.call) + ": an edge's unit is beyond nunits"); return MC_EBADCFG; }
     if (!s.g.lv.unit_built) {
         if (int rc = upload(s.g.lv.unit, it->second.data(), s.g.info.edges, "the edges' units")) return rc;
         s.g.lv.unit_built = true;
@@ -48,20 +36,10 @@ static int uf_prepare(Sg &s, void *h, const mc_fair_units *fu, bool want_pred, c
     return MC_OK;
 }
 int uf_live_units(void *h, const mc_fair_units *fu, mc_live_info *out, mc_live_strong_info *sout) {
-    Sg &s = *(Sg *)h;
-    memset(out, 0, sizeof *out);
-    memset(sout, 0, sizeof *sout);
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int rc = uf_prepare(s, h, fu, false, "uf_live_units")) return rc;
-    return s.g.live_check_strong(mc::live_all_conjuncts(fu->nconj), fu->weak_mask, fu->strong_mask, -1, -1, -1, s.stream, t0, out, nullptr, sout, fu->of_unit);
+    return check(*(Sg *)h, mc::live_query_units("uf_live_units", fu, -1, -1, -1), out, nullptr, sout, uf_units);
 }
 int uf_live_check_units(void *h, const mc_fair_units *fu, int kind, int p, int q, mc_live_check_info *out, mc_live_strong_info *sout) {
-    Sg &s = *(Sg *)h;
-    memset(out, 0, sizeof *out);
-    memset(sout, 0, sizeof *sout);
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int rc = uf_prepare(s, h, fu, true, "uf_live_check_units")) return rc;
-    return s.g.live_check_strong(mc::live_all_conjuncts(fu->nconj), fu->weak_mask, fu->strong_mask, kind, p, q, s.stream, t0, nullptr, out, sout, fu->of_unit);
+    return check(*(Sg *)h, mc::live_query_units("uf_live_check_units", fu, kind, p, q), nullptr, out, sout, uf_units);
 }
 
 }  // extern "C"

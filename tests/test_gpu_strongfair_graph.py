@@ -211,10 +211,13 @@ def test_weak_and_strong_checks_do_not_disturb_each_other():
 def test_bad_masks_are_refused(devices):
     case = R.ESCAPE_CASES[3]
     g, weak, strong = R.graph_of(case)
-    for w, s in ((weak | 1 << g.nproc - 1, strong), (weak, strong | 1 << g.nproc)):
+    # (the refusals are the product's, live_query.h's, behind the driver's call name: the driver holds no condition of its own)
+    for w, s, words in ((weak | 1 << g.nproc - 1, strong, "the weak and the strong mask overlap (a strongly fair process is weakly fair already)"),
+                        (weak, strong | 1 << g.nproc, "a fairness mask names a process instance the program does not have")):
         with pytest.raises(sgraph.SgError) as e:
             devices(case).live_strong(all_mask(g), w, s)
         assert e.value.code == -1   # MC_EBADCFG
+        assert str(e.value).startswith("sf_live_strong: " + words), str(e.value)
 
 
 # ---------------------------------------------------------------------------------------------------------------- mutants of the new kernels

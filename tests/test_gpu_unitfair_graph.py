@@ -198,18 +198,22 @@ def test_bad_tables_are_refused(devices):
     ug = R.graph_of(case)
     G = devices(case)
     good = (ug.of_unit, ug.nunits, ug.nconj, ug.weak, ug.strong)
+    # (the refusals are the product's, live_query.h's, behind the driver's call name: the driver holds no condition of the table)
     bad = [
-        (ug.of_unit, ug.nunits, ug.nconj, ug.weak | ug.strong, ug.strong),                                  # the masks overlap
-        (ug.of_unit, ug.nunits, ug.nconj, ug.weak | 1 << ug.nconj, ug.strong),                              # a conjunct bit >= nconj in a mask
-        ([m | 1 << ug.nconj if u == 0 else m for u, m in enumerate(ug.of_unit)], ug.nunits, ug.nconj, ug.weak, ug.strong),   # ... in of_unit[]
-        (ug.of_unit, 128, ug.nconj, ug.weak, ug.strong), (ug.of_unit, ug.nunits, 65, ug.weak, ug.strong),   # counts out of range
-        (ug.of_unit, 1, ug.nconj, ug.weak, ug.strong),                                                      # units beyond nunits
+        ((ug.of_unit, ug.nunits, ug.nconj, ug.weak | ug.strong, ug.strong), "the weak and the strong mask overlap (a conjunct is WF or SF)"),
+        ((ug.of_unit, ug.nunits, ug.nconj, ug.weak | 1 << ug.nconj, ug.strong), "a fairness mask names a conjunct beyond nconj"),
+        (([m | 1 << ug.nconj if u == 0 else m for u, m in enumerate(ug.of_unit)], ug.nunits, ug.nconj, ug.weak, ug.strong),
+         "of_unit[0] names a conjunct beyond nconj"),
+        ((ug.of_unit, 128, ug.nconj, ug.weak, ug.strong), "128 units (at most 127)"),                       # counts out of range
+        ((ug.of_unit, ug.nunits, 65, ug.weak, ug.strong), "65 conjuncts (at most 64)"),
+        ((ug.of_unit, 1, ug.nconj, ug.weak, ug.strong), "names conjuncts for a unit beyond nunits"),        # units beyond nunits
     ]
-    assert ug.nconj < 64
-    for args in bad:
+    assert ug.nconj < 64 and ug.strong
+    for args, words in bad:
         with pytest.raises(sgraph.SgError) as e:
             G.live_units(ufgraph.fair_units(*args))
         assert e.value.code == -1   # MC_EBADCFG
+        assert str(e.value).startswith("uf_live_units: ") and words in str(e.value), str(e.value)
     G.live_units(ufgraph.fair_units(*good))
 
 

@@ -19,10 +19,10 @@ SOURCES = ["engine.hip", "frontend.cpp"]
 # tests/test_engine_layout.py checks the lists against the files' #include lines.
 ENGINE_BASE = ["engine.hip", "hip_owned.h", "engine_kernels.h", "engine_sim.h", "sim_walk.h", "engine_coverage.h", "coverage.h", "engine_violations.h", "violations.h",
                "engine_graph.h",
-               "graph.h", "liveness.h", "state_graph.h", "spec_gen.h", "mc_common.h", "spec_registry.h", "../../include/tlamc.h"]
+               "graph.h", "liveness.h", "live_query.h", "state_graph.h", "spec_gen.h", "mc_common.h", "spec_registry.h", "../../include/tlamc.h"]
 ENGINE_OWN = {0: ["spec_pluscal.h", "spec_raft.h", "spec_ssi.h", "spec_vm.h", "spec_vm_cfg.h", "spec_paxos.h", "engine_pairs.h"], 7: ["spec_paxos.h"], 1: ["spec_pluscal.h"],
               2: ["spec_raft.h"], 3: ["spec_raft.h"], 4: ["spec_raft.h"], 5: ["spec_ssi.h", "engine_pairs.h"], 6: ["spec_vm.h", "spec_vm_cfg.h"]}
-STATE_GRAPH_DEPS = ["state_graph.hip", "state_graph.h", "engine_live.h", "hip_owned.h", "liveness.h", "graph.h", "coverage.h", "mc_common.h", "spec_registry.h",
+STATE_GRAPH_DEPS = ["state_graph.hip", "state_graph.h", "engine_live.h", "hip_owned.h", "liveness.h", "live_query.h", "graph.h", "coverage.h", "mc_common.h", "spec_registry.h",
                     "spec_gen.h", "spec_pluscal.h", "spec_raft.h", "spec_ssi.h", "spec_vm.h", "spec_vm_cfg.h", "spec_paxos.h", "../../include/tlamc.h"]
 
 

@@ -120,14 +120,10 @@ struct EngineBase {
     hipStream_t graph_stream = nullptr;                 // the engine's main stream
     const std::vector<uint64_t> *graph_levels = nullptr;   // the level table of the last search
     virtual int graph(mc_graph_info *out) = 0;
-    virtual int liveness(uint64_t weak_fair_mask, mc_live_info *out) = 0;
     virtual int predicates(uint64_t first, uint64_t count, uint32_t *bits_out) = 0;
-    virtual int liveness_check(uint64_t weak_fair_mask, const mc_live_property *prop, mc_live_check_info *out) = 0;
-    virtual int liveness_strong(uint64_t weak, uint64_t strong, mc_live_info *out, mc_live_strong_info *sout) = 0;
-    virtual int liveness_check_strong(uint64_t weak, uint64_t strong, const mc_live_property *prop, mc_live_check_info *out, mc_live_strong_info *sout) = 0;
-    virtual int liveness_units(const mc_fair_units *fu, mc_live_info *out, mc_live_strong_info *sout) = 0;
-    virtual int liveness_edge_units(uint64_t first, uint64_t count, int8_t *unit_out) = 0;
-    virtual int liveness_check_units(const mc_fair_units *fu, const mc_live_property *prop, mc_live_check_info *out, mc_live_strong_info *sout) = 0;
+    // every liveness check (live_query.h): prop for a property's name and refusal; of the outputs, those the C entry has
+    virtual int liveness_run(const LiveQuery &q, const mc_live_property *prop, mc_live_info *out, mc_live_check_info *check_out, mc_live_strong_info *strong_out) = 0;
+    int liveness_edge_units(uint64_t first, uint64_t count, int8_t *unit_out) { return gr.live_unit_read(first, count, unit_out); }
     int graph_read(uint64_t first, uint64_t count, uint64_t *offsets_out, uint32_t *dst_out, int32_t *action_out, size_t *nedges_inout) {
         return gr.read(first, count, offsets_out, dst_out, action_out, nedges_inout);
     }
@@ -701,35 +697,6 @@ struct Engine : EngineBase {
         return MC_ESTATE;
     }
 
-    // ------------------------------------------------------------------------------- fairness: the lowering's part (LiveProc<S>, k_live_proc<S>)
-    int liveness(uint64_t fair, mc_live_info *out) override {
-        memset(out, 0, sizeof *out);
-        if (cfg.shard_count > 1) { set_error("mc_engine_liveness: not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
-        if constexpr (!LiveProc<S>::HAS) {
-            set_error("mc_engine_liveness: this lowering has no process instances (compiled PlusCal programs only)");
-            return MC_ENOSPEC;
-        } else {
-            if (!fr.have_run || ck.pending || fr.have_viol || fr.hi != fr.lo) {
-                set_error("mc_engine_liveness: needs a search of this engine that finished without a violation and with an empty queue (the complete state graph)");
-                return MC_ESTATE;
-            }
-            const int np = LiveProc<S>::count(prm);
-            if (np > LIVE_MAX_PROCS) { set_error("mc_engine_liveness: at most 64 process instances"); return MC_EBADCFG; }
-            const uint64_t all = np >= 64 ? ~0ull : (1ull << np) - 1;
-            if (fair & ~all) { set_error("mc_engine_liveness: the fairness mask names a process instance the program does not have"); return MC_EBADCFG; }
-            if (!gr.built || !gr.lv.scc_built) { mc_scc_info si; if (int rc = scc(&si)) return rc; }
-            auto &lv = gr.lv;
-            lv.checked = false;
-            const uint64_t edges = gr.info.edges;
-            HIP_TRY(hipSetDevice(cfg.device));
-            const auto t0 = std::chrono::steady_clock::now();
-            if (int rc = graph_alloc(lv.proc, edges, "the edges' processes", "mc_engine_liveness")) return rc;
-            HIP_TRY(hipMemsetAsync(lv.proc, 0xff, (edges ? edges : 1) * sizeof(int8_t), stream));
-            graph_chunks(k_live_proc<S>, 0, fr.lo, (const uint64_t *)gr.offsets.p, lv.proc.p);
-            lv.proc_built = true;
-            return gr.live_check(all, fair, stream, t0, out);
-        }
-    }
     // ------------------------------------------------------------------------------- the predicates of the cfg's temporal properties
     // (LivePred<S>, k_live_pred<S>) and one (M, S, T) check over them
     int predicates_build(const char *call) {
@@ -761,6 +728,7 @@ struct Engine : EngineBase {
                 return MC_ESTATE;
             }
             lv.pred_built = true;
+            lv.npred = tab.n;
             return MC_OK;
         }
     }
@@ -775,120 +743,23 @@ struct Engine : EngineBase {
             return gr.pred_read(first, count, bits_out);
         }
     }
-    int liveness_check(uint64_t fair, const mc_live_property *prop, mc_live_check_info *out) override {
-        memset(out, 0, sizeof *out);
-        if (cfg.shard_count > 1) { set_error("mc_engine_liveness_check: not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
-        if constexpr (!LiveProc<S>::HAS || !LivePred<S>::HAS) {
-            set_error("mc_engine_liveness_check: this lowering has no process instances (compiled PlusCal programs only)");
-            return MC_ENOSPEC;
-        } else {
-            if (!fr.have_run || ck.pending || fr.have_viol || fr.hi != fr.lo) {
-                set_error("mc_engine_liveness_check: needs a search of this engine that finished without a violation and with an empty queue (the complete state graph)");
-                return MC_ESTATE;
-            }
-            const int np = LiveProc<S>::count(prm);
-            if (np > LIVE_MAX_PROCS) { set_error("mc_engine_liveness_check: at most 64 process instances"); return MC_EBADCFG; }
-            const uint64_t all = np >= 64 ? ~0ull : (1ull << np) - 1;
-            if (fair & ~all) { set_error("mc_engine_liveness_check: the fairness mask names a process instance the program does not have"); return MC_EBADCFG; }
-            if (prop->refused) { set_error(std::string("mc_engine_liveness_check: the front end refused ") + prop->name); return MC_EBADCFG; }
-            const int npred = vm_live_preds(prm.host, nullptr, 0);
-            const int kind = prop->kind;
-            if (kind < LIVE_LEADS_TO || kind > LIVE_STABLE) { set_error("mc_engine_liveness_check: unknown kind " + std::to_string(kind)); return MC_EBADCFG; }
-            const bool need_p = kind == LIVE_LEADS_TO || kind == LIVE_STABLE, need_q = kind != LIVE_STABLE;
-            if ((need_p && (prop->p < 0 || prop->p >= npred)) || (need_q && (prop->q < 0 || prop->q >= npred)) || npred > LIVE_MAX_PREDS) {
-                set_error("mc_engine_liveness_check: a predicate index the program does not have (it has " + std::to_string(npred) + " predicates)");
-                return MC_EBADCFG;
-            }
-            const auto t0 = std::chrono::steady_clock::now();
-            if (!gr.built || !gr.lv.scc_built) { mc_scc_info si; if (int rc = scc(&si)) return rc; }
-            auto &lv = gr.lv;
-            lv.checked = false;
-            HIP_TRY(hipSetDevice(cfg.device));
-            if (!lv.proc_built) {
-                const uint64_t edges = gr.info.edges;
-                if (int rc = graph_alloc(lv.proc, edges, "the edges' processes", "mc_engine_liveness_check")) return rc;
-                HIP_TRY(hipMemsetAsync(lv.proc, 0xff, (edges ? edges : 1) * sizeof(int8_t), stream));
-                graph_chunks(k_live_proc<S>, 0, fr.lo, (const uint64_t *)gr.offsets.p, lv.proc.p);
-                lv.proc_built = true;
-            }
-            if (int rc = predicates_build("mc_engine_liveness_check")) return rc;
-            return gr.live_check_masked(all, fair, kind, need_p ? prop->p : -1, need_q ? prop->q : -1, stream, t0, out);
-        }
-    }
 
-    // ------------------------------------------------------------------------------- the same under strong fairness:
-    // the weak twins' conditions and preparation, then StateGraph::live_check_strong
-    int strong_prepare(const char *name, uint64_t weak, uint64_t strong, bool fresh_proc, uint64_t *all_out) {
-        const std::string call(name);
-        if (cfg.shard_count > 1) { set_error(call + ": not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
-        if constexpr (!LiveProc<S>::HAS || !LivePred<S>::HAS) {
-            set_error(call + ": this lowering has no process instances (compiled PlusCal programs only)");
-            return MC_ENOSPEC;
-        } else {
-            if (!fr.have_run || ck.pending || fr.have_viol || fr.hi != fr.lo) {
-                set_error(call + ": needs a search of this engine that finished without a violation and with an empty queue (the complete state graph)");
-                return MC_ESTATE;
-            }
-            const int np = LiveProc<S>::count(prm);
-            if (np > LIVE_MAX_PROCS) { set_error(call + ": at most 64 process instances"); return MC_EBADCFG; }
-            const uint64_t all = np >= 64 ? ~0ull : (1ull << np) - 1;
-            if ((weak | strong) & ~all) { set_error(call + ": a fairness mask names a process instance the program does not have"); return MC_EBADCFG; }
-            if (weak & strong) { set_error(call + ": the weak and the strong mask overlap (a strongly fair process is weakly fair already)"); return MC_EBADCFG; }
-            if (!gr.built || !gr.lv.scc_built) { mc_scc_info si; if (int rc = scc(&si)) return rc; }
-            auto &lv = gr.lv;
-            lv.checked = false;
-            HIP_TRY(hipSetDevice(cfg.device));
-            if (fresh_proc || !lv.proc_built) {
-                const uint64_t edges = gr.info.edges;
-                if (int rc = graph_alloc(lv.proc, edges, "the edges' processes", name)) return rc;
-                HIP_TRY(hipMemsetAsync(lv.proc, 0xff, (edges ? edges : 1) * sizeof(int8_t), stream));
-                graph_chunks(k_live_proc<S>, 0, fr.lo, (const uint64_t *)gr.offsets.p, lv.proc.p);
-                lv.proc_built = true;
-            }
-            *all_out = all;
-            return MC_OK;
-        }
-    }
-    int liveness_strong(uint64_t weak, uint64_t strong, mc_live_info *out, mc_live_strong_info *sout) override {
-        memset(out, 0, sizeof *out);
-        memset(sout, 0, sizeof *sout);
-        const auto t0 = std::chrono::steady_clock::now();
-        uint64_t all = 0;
-        if (int rc = strong_prepare("mc_engine_liveness_strong", weak, strong, true, &all)) return rc;
-        return gr.live_check_strong(all, weak, strong, -1, -1, -1, stream, t0, out, nullptr, sout);
-    }
-    int liveness_check_strong(uint64_t weak, uint64_t strong, const mc_live_property *prop, mc_live_check_info *out, mc_live_strong_info *sout) override {
-        memset(out, 0, sizeof *out);
-        memset(sout, 0, sizeof *sout);
-        if constexpr (!LiveProc<S>::HAS || !LivePred<S>::HAS) {
-            set_error("mc_engine_liveness_check_strong: this lowering has no process instances (compiled PlusCal programs only)");
-            return MC_ENOSPEC;
-        } else {
-            const char *call = "mc_engine_liveness_check_strong";
-            if (prop->refused) { set_error(std::string(call) + ": the front end refused " + prop->name); return MC_EBADCFG; }
-            const int npred = vm_live_preds(prm.host, nullptr, 0);
-            const int kind = prop->kind;
-            if (kind < LIVE_LEADS_TO || kind > LIVE_STABLE) { set_error(std::string(call) + ": unknown kind " + std::to_string(kind)); return MC_EBADCFG; }
-            const bool need_p = kind == LIVE_LEADS_TO || kind == LIVE_STABLE, need_q = kind != LIVE_STABLE;
-            if ((need_p && (prop->p < 0 || prop->p >= npred)) || (need_q && (prop->q < 0 || prop->q >= npred)) || npred > LIVE_MAX_PREDS) {
-                set_error(std::string(call) + ": a predicate index the program does not have (it has " + std::to_string(npred) + " predicates)");
-                return MC_EBADCFG;
-            }
-            const auto t0 = std::chrono::steady_clock::now();
-            uint64_t all = 0;
-            if (int rc = strong_prepare(call, weak, strong, false, &all)) return rc;
-            if (int rc = predicates_build(call)) return rc;
-            return gr.live_check_strong(all, weak, strong, kind, need_p ? prop->p : -1, need_q ? prop->q : -1, stream, t0, nullptr, out, sout);
-        }
-    }
-
-    // ------------------------------------------------------------------------------- the same label by label: the table's
-    // conditions, the strong twins' preparation with k_live_unit<S> in k_live_proc<S>'s place, then StateGraph::live_check_strong
+    // ------------------------------------------------------------------------------- the liveness checks: the lowering's part (LiveProc<S>,
+    // k_live_proc<S>, k_live_unit<S>) of all six C entries (DESIGN sections 16, 17, 19, 21).  Each entry fills a LiveQuery (live_query.h);
+    // here, in ONE order: the outputs zeroed, the engine's conditions, the query's (live_query_error), what the graph lacks built —
+    // components, the edges' processes or units, a property's predicates: once per graph, release() forgets them —, then
+    // StateGraph::live_check.
+    static_assert(LiveProc<S>::HAS == LivePred<S>::HAS, "a lowering with process instances compiles predicates, and no other does");
     DevBuf<int8_t> live_unit_tab;   // the program's (instance, label) -> unit table, as k_live_unit<S> reads it
-    int units_prepare(const char *name, const mc_fair_units *fu, bool fresh_unit, uint64_t *all_out) {
-        const std::string call(name);
+    int liveness_run(const LiveQuery &query, const mc_live_property *prop, mc_live_info *out, mc_live_check_info *check_out, mc_live_strong_info *strong_out) override {
+        LiveQuery q = query;
+        const std::string call(q.call);
+        auto t0 = std::chrono::steady_clock::now();
+        if (out) memset(out, 0, sizeof *out);
+        if (check_out) memset(check_out, 0, sizeof *check_out);
+        if (strong_out) memset(strong_out, 0, sizeof *strong_out);
         if (cfg.shard_count > 1) { set_error(call + ": not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
-        if constexpr (!LiveProc<S>::HAS || !LivePred<S>::HAS) {
+        if constexpr (!LiveProc<S>::HAS) {
             set_error(call + ": this lowering has no process instances (compiled PlusCal programs only)");
             return MC_ENOSPEC;
         } else {
@@ -896,70 +767,43 @@ struct Engine : EngineBase {
                 set_error(call + ": needs a search of this engine that finished without a violation and with an empty queue (the complete state graph)");
                 return MC_ESTATE;
             }
-            if (fu->nunits < 0 || fu->nunits > LIVE_MAX_UNITS) { set_error(call + ": " + std::to_string(fu->nunits) + " units (at most 127)"); return MC_EBADCFG; }
-            if (fu->nconj < 0 || fu->nconj > LIVE_MAX_CONJ) { set_error(call + ": " + std::to_string(fu->nconj) + " conjuncts (at most 64)"); return MC_EBADCFG; }
-            const uint64_t all = live_all_conjuncts(fu->nconj);
-            if ((fu->weak_mask | fu->strong_mask) & ~all) { set_error(call + ": a fairness mask names a conjunct beyond nconj"); return MC_EBADCFG; }
-            if (fu->weak_mask & fu->strong_mask) { set_error(call + ": the weak and the strong mask overlap (a conjunct is WF or SF)"); return MC_EBADCFG; }
-            for (int u = 0; u < LIVE_UNIT_TAB; ++u)
-                if (fu->of_unit[u] & (u < fu->nunits ? ~all : ~0ull)) {
-                    set_error(call + ": of_unit[" + std::to_string(u) + "] names " + (u < fu->nunits ? "a conjunct beyond nconj" : "conjuncts for a unit beyond nunits"));
-                    return MC_EBADCFG;
-                }
+            if (!q.fu) {
+                const int np = LiveProc<S>::count(prm);
+                if (np > LIVE_MAX_PROCS) { set_error(call + ": at most 64 process instances"); return MC_EBADCFG; }
+                q.all = np >= 64 ? ~0ull : (1ull << np) - 1;
+            }
+            if (prop && prop->refused) { set_error(call + ": the front end refused " + prop->name); return MC_EBADCFG; }
+            if (prop && q.term()) { set_error(call + ": " + live_unknown_kind(q.kind)); return MC_EBADCFG; }   // (-1 is no kind of a property)
+            if (int rc = live_query_check(q, prop ? vm_live_preds(prm.host, nullptr, 0) : 0)) return rc;
             int ni = 0, nl = 0;
-            const int nu = vm_live_units(prm.host, &ni, &nl, nullptr, 0);
-            if (fu->nunits < nu) { set_error(call + ": the program has " + std::to_string(nu) + " units, the table " + std::to_string(fu->nunits)); return MC_EBADCFG; }
+            if (q.fu) {   // (after the table's own conditions: a table with nunits < 0 is refused for that)
+                const int nu = vm_live_units(prm.host, &ni, &nl, nullptr, 0);
+                if (q.fu->nunits < nu) { set_error(call + ": the program has " + std::to_string(nu) + " units, the table " + std::to_string(q.fu->nunits)); return MC_EBADCFG; }
+            }
             if (!gr.built || !gr.lv.scc_built) { mc_scc_info si; if (int rc = scc(&si)) return rc; }
             auto &lv = gr.lv;
-            lv.checked = false;
+            const uint64_t edges = gr.info.edges;
             HIP_TRY(hipSetDevice(cfg.device));
-            if (fresh_unit || !lv.unit_built) {
-                const uint64_t edges = gr.info.edges;
+            if (!q.refine && !prop) t0 = std::chrono::steady_clock::now();   // (mc_engine_liveness's seconds leave the components out)
+            if (!q.fu && !lv.proc_built) {
+                if (int rc = graph_alloc(lv.proc, edges, "the edges' processes", q.call)) return rc;
+                HIP_TRY(hipMemsetAsync(lv.proc, 0xff, (edges ? edges : 1) * sizeof(int8_t), stream));
+                graph_chunks(k_live_proc<S>, 0, fr.lo, (const uint64_t *)gr.offsets.p, lv.proc.p);
+                lv.proc_built = true;
+            }
+            if (q.fu && !lv.unit_built) {
                 std::vector<int8_t> tab((size_t)ni * (size_t)nl + 1, (int8_t)LIVE_TERM);
                 vm_live_units(prm.host, &ni, &nl, tab.data(), (int)tab.size());
-                if (int rc = graph_alloc(live_unit_tab, tab.size(), "the units of the labels", name)) return rc;
-                if (int rc = graph_alloc(lv.unit, edges, "the edges' units", name)) return rc;
+                if (int rc = graph_alloc(live_unit_tab, tab.size(), "the units of the labels", q.call)) return rc;
+                if (int rc = graph_alloc(lv.unit, edges, "the edges' units", q.call)) return rc;
                 HIP_TRY(hipMemcpyAsync(live_unit_tab, tab.data(), tab.size() * sizeof(int8_t), hipMemcpyHostToDevice, stream));
                 HIP_TRY(hipMemsetAsync(lv.unit, 0xff, (edges ? edges : 1) * sizeof(int8_t), stream));
                 graph_chunks(k_live_unit<S>, 0, fr.lo, (const uint64_t *)gr.offsets.p, LiveUnitTab{ni, nl, (const int8_t *)live_unit_tab.p}, lv.unit.p);
                 HIP_TRY(hipStreamSynchronize(stream));   // (the host table is read by the copy until here)
                 lv.unit_built = true;
             }
-            *all_out = all;
-            return MC_OK;
-        }
-    }
-    int liveness_edge_units(uint64_t first, uint64_t count, int8_t *unit_out) override { return gr.live_unit_read(first, count, unit_out); }
-    int liveness_units(const mc_fair_units *fu, mc_live_info *out, mc_live_strong_info *sout) override {
-        memset(out, 0, sizeof *out);
-        memset(sout, 0, sizeof *sout);
-        const auto t0 = std::chrono::steady_clock::now();
-        uint64_t all = 0;
-        if (int rc = units_prepare("mc_engine_liveness_units", fu, true, &all)) return rc;
-        return gr.live_check_strong(all, fu->weak_mask, fu->strong_mask, -1, -1, -1, stream, t0, out, nullptr, sout, fu->of_unit);
-    }
-    int liveness_check_units(const mc_fair_units *fu, const mc_live_property *prop, mc_live_check_info *out, mc_live_strong_info *sout) override {
-        memset(out, 0, sizeof *out);
-        memset(sout, 0, sizeof *sout);
-        if constexpr (!LiveProc<S>::HAS || !LivePred<S>::HAS) {
-            set_error("mc_engine_liveness_check_units: this lowering has no process instances (compiled PlusCal programs only)");
-            return MC_ENOSPEC;
-        } else {
-            const char *call = "mc_engine_liveness_check_units";
-            if (prop->refused) { set_error(std::string(call) + ": the front end refused " + prop->name); return MC_EBADCFG; }
-            const int npred = vm_live_preds(prm.host, nullptr, 0);
-            const int kind = prop->kind;
-            if (kind < LIVE_LEADS_TO || kind > LIVE_STABLE) { set_error(std::string(call) + ": unknown kind " + std::to_string(kind)); return MC_EBADCFG; }
-            const bool need_p = kind == LIVE_LEADS_TO || kind == LIVE_STABLE, need_q = kind != LIVE_STABLE;
-            if ((need_p && (prop->p < 0 || prop->p >= npred)) || (need_q && (prop->q < 0 || prop->q >= npred)) || npred > LIVE_MAX_PREDS) {
-                set_error(std::string(call) + ": a predicate index the program does not have (it has " + std::to_string(npred) + " predicates)");
-                return MC_EBADCFG;
-            }
-            const auto t0 = std::chrono::steady_clock::now();
-            uint64_t all = 0;
-            if (int rc = units_prepare(call, fu, false, &all)) return rc;
-            if (int rc = predicates_build(call)) return rc;
-            return gr.live_check_strong(all, fu->weak_mask, fu->strong_mask, kind, need_p ? prop->p : -1, need_q ? prop->q : -1, stream, t0, nullptr, out, sout, fu->of_unit);
+            if (prop) if (int rc = predicates_build(q.call)) return rc;
+            return gr.live_check(q, stream, t0, out, check_out, strong_out);
         }
     }
 
@@ -2570,29 +2414,40 @@ int mc_engine_scc(mc_engine *e, mc_scc_info *out) { return e && out ? e->impl->s
 int mc_engine_scc_read(mc_engine *e, uint64_t first, uint64_t count, uint32_t *scc_out) {
     return e && (scc_out || !count) ? e->impl->scc_read(first, count, scc_out) : MC_EBADCFG;
 }
-int mc_engine_liveness(mc_engine *e, uint64_t weak_fair_mask, mc_live_info *out) { return e && out ? e->impl->liveness(weak_fair_mask, out) : MC_EBADCFG; }
 int mc_engine_predicates(mc_engine *e, uint64_t first, uint64_t count, uint32_t *bits_out) {
     return e && (bits_out || !count) ? e->impl->predicates(first, count, bits_out) : MC_EBADCFG;
 }
+// The six liveness checks: each is its LiveQuery (live_query.h) and the outputs it has.  prop null: Termination; `all` is the engine's to say.
+static LiveQuery live_query_procs(const char *call, uint64_t weak, uint64_t strong, const mc_live_property *prop, bool refine) {
+    return LiveQuery{call, 0, weak, strong, nullptr, prop ? prop->kind : -1, prop ? prop->p : -1, prop ? prop->q : -1, refine};
+}
+int mc_engine_liveness(mc_engine *e, uint64_t weak_fair_mask, mc_live_info *out) {
+    return e && out ? e->impl->liveness_run(live_query_procs("mc_engine_liveness", weak_fair_mask, 0, nullptr, false), nullptr, out, nullptr, nullptr) : MC_EBADCFG;
+}
 int mc_engine_liveness_check(mc_engine *e, uint64_t weak_fair_mask, const mc_live_property *prop, mc_live_check_info *out) {
-    return e && prop && out ? e->impl->liveness_check(weak_fair_mask, prop, out) : MC_EBADCFG;
+    return e && prop && out ? e->impl->liveness_run(live_query_procs("mc_engine_liveness_check", weak_fair_mask, 0, prop, false), prop, nullptr, out, nullptr) : MC_EBADCFG;
 }
 int mc_engine_liveness_strong(mc_engine *e, uint64_t weak_mask, uint64_t strong_mask, mc_live_info *out, mc_live_strong_info *strong_out) {
-    return e && out && strong_out ? e->impl->liveness_strong(weak_mask, strong_mask, out, strong_out) : MC_EBADCFG;
-}
-int mc_engine_liveness_units(mc_engine *e, const mc_fair_units *fu, mc_live_info *out, mc_live_strong_info *strong_out) {
-    return e && fu && out && strong_out ? e->impl->liveness_units(fu, out, strong_out) : MC_EBADCFG;
-}
-int mc_engine_liveness_edge_units(mc_engine *e, uint64_t first_edge, uint64_t count, int8_t *unit_out) {
-    return e && (unit_out || !count) ? e->impl->liveness_edge_units(first_edge, count, unit_out) : MC_EBADCFG;
-}
-int mc_engine_liveness_check_units(mc_engine *e, const mc_fair_units *fu, const mc_live_property *prop, mc_live_check_info *out,
-                                   mc_live_strong_info *strong_out) {
-    return e && fu && prop && out && strong_out ? e->impl->liveness_check_units(fu, prop, out, strong_out) : MC_EBADCFG;
+    return e && out && strong_out ? e->impl->liveness_run(live_query_procs("mc_engine_liveness_strong", weak_mask, strong_mask, nullptr, true), nullptr, out, nullptr, strong_out)
+                                  : MC_EBADCFG;
 }
 int mc_engine_liveness_check_strong(mc_engine *e, uint64_t weak_mask, uint64_t strong_mask, const mc_live_property *prop, mc_live_check_info *out,
                                     mc_live_strong_info *strong_out) {
-    return e && prop && out && strong_out ? e->impl->liveness_check_strong(weak_mask, strong_mask, prop, out, strong_out) : MC_EBADCFG;
+    return e && prop && out && strong_out
+               ? e->impl->liveness_run(live_query_procs("mc_engine_liveness_check_strong", weak_mask, strong_mask, prop, true), prop, nullptr, out, strong_out)
+               : MC_EBADCFG;
+}
+int mc_engine_liveness_units(mc_engine *e, const mc_fair_units *fu, mc_live_info *out, mc_live_strong_info *strong_out) {
+    return e && fu && out && strong_out ? e->impl->liveness_run(live_query_units("mc_engine_liveness_units", fu, -1, -1, -1), nullptr, out, nullptr, strong_out) : MC_EBADCFG;
+}
+int mc_engine_liveness_check_units(mc_engine *e, const mc_fair_units *fu, const mc_live_property *prop, mc_live_check_info *out,
+                                   mc_live_strong_info *strong_out) {
+    return e && fu && prop && out && strong_out
+               ? e->impl->liveness_run(live_query_units("mc_engine_liveness_check_units", fu, prop->kind, prop->p, prop->q), prop, nullptr, out, strong_out)
+               : MC_EBADCFG;
+}
+int mc_engine_liveness_edge_units(mc_engine *e, uint64_t first_edge, uint64_t count, int8_t *unit_out) {
+    return e && (unit_out || !count) ? e->impl->liveness_edge_units(first_edge, count, unit_out) : MC_EBADCFG;
 }
 int mc_engine_liveness_components(mc_engine *e, uint64_t first, uint64_t count, uint32_t *scc_out) {
     return e && (scc_out || !count) ? e->impl->liveness_components(first, count, scc_out) : MC_EBADCFG;

@@ -1,8 +1,9 @@
 // state_graph.h — the state graph of a finished search (mc_engine_graph) and what is computed from its CSR arrays alone: the reads, the
-// strongly connected components (mc_engine_scc), the fairness check (mc_engine_liveness) and its counterexample.  None of it depends on
-// the lowering, so the host half (state_graph.hip) and the kernels (engine_live.h) are compiled once for the library; the engine of
-// every lowering — the one of generated code, built at load time, included — fills the arrays with its own kernels (engine_graph.h:
-// k_graph_index / k_graph_degree / k_graph_fill / k_live_proc) and calls in here.
+// strongly connected components (mc_engine_scc), the liveness checks (mc_engine_liveness and its five siblings: ONE entry, live_check,
+// over a LiveQuery of live_query.h) and their counterexample.  None of it depends on the lowering, so the host half (state_graph.hip)
+// and the kernels (engine_live.h) are compiled once for the library; the engine of every lowering — the one of generated code, built
+// at load time, included — fills the arrays with its own kernels (engine_graph.h: k_graph_index / k_graph_degree / k_graph_fill /
+// k_live_proc / k_live_unit / k_live_pred) and calls in here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,10 +15,10 @@
 
 #include "../../include/tlamc.h"
 #include "hip_owned.h"
+#include "live_query.h"   // LiveQuery: which check; liveness.h: LiveCheck and the LIVE_* bounds
 
 namespace mc {
 
-struct LiveCheck;      // liveness.h
 struct LiveCounters;   // engine_live.h
 
 // `count` elements for a graph array; the message names the call and the array
@@ -46,7 +47,7 @@ struct StateGraph {
     mc_graph_info info{};
     // what mc_engine_scc / mc_engine_liveness add: lives and dies with the graph
     struct Live {
-        bool scc_built = false, checked = false;
+        bool scc_built = false;
         DevBuf<uint64_t> toff;      // [states + 1] rows of the transpose (self loops left out)
         DevBuf<uint32_t> tsrc;      // [edges that are no self loops] the sources
         DevBuf<uint32_t> scc;       // [states] the least arena index of the state's component
@@ -55,37 +56,43 @@ struct StateGraph {
         DevBuf<unsigned long long> taken, disabled;   // [states] at a component's id: the unions over its states
         DevBuf<unsigned> done;      // [states] at a component's id: it holds a Done state
         mc_scc_info sinfo{};
-        mc_live_info linfo{};
-        uint64_t fair = 0, strong = 0;   // of the last check: the weakly / strongly fair processes
         // what mc_engine_predicates / mc_engine_liveness_check add
         bool pred_built = false, proc_built = false;
+        int npred = 0;              // the predicates pred[] has bits of (set with pred_built)
         DevBuf<uint32_t> pred;      // [states] bit k = predicate k of the program's temporal properties holds in the state
         DevBuf<uint32_t> dist;      // [states] the reach pass of the last check
         struct Masked { int q; DevBuf<uint32_t> scc, size; };   // the components of the subgraph induced by ~predicate q: one build per mask
         std::vector<std::unique_ptr<Masked>> masks;
-        // the last check, for the counterexample: -1 = Termination (mc_engine_liveness), else the kind of a property check
-        int last_kind = -1, last_p = -1, last_q = -1;
-        const Masked *last_mask = nullptr;     // its components (null: the full graph's)
-        std::vector<uint32_t> descent;         // from the witness along falling dist to the first state of the component
         // what mc_engine_liveness_strong / mc_engine_liveness_check_strong add
-        bool last_strong = false;              // the last check refined: its components are fscc's
         DevBuf<unsigned long long> enabled;    // [states] at a component's id: the processes enabled in some state of it
         DevBuf<uint8_t> open;                  // [states] LIVE_ST_*: closed, open or in a final component
         DevBuf<uint32_t> fscc, fsize;          // [states] the refined ids (a closed state: its own index) and, at an id, the size
         DevBuf<uint32_t> wscc, wsize;          // [states] the components of the open subgraph, rounds >= 2
         // what mc_engine_liveness_units / mc_engine_liveness_check_units add
-        bool last_units = false;               // the last check read proc[] as units: fair / strong are masks of conjuncts
         bool unit_built = false;
         DevBuf<int8_t> unit;                   // [edges] beside proc: the edge's unit (k_live_unit<S>), LIVE_TERM for the terminating disjunct
         DevBuf<uint64_t> of_unit;              // [LIVE_UNIT_TAB] the conjuncts of every unit, as the kernels stage it
         std::vector<uint64_t> of_unit_host;    // the same, for the counterexample builder
+        // The last check, for mc_engine_liveness_components and the counterexample.  Value-reset where a check starts and in release(),
+        // nowhere else; a check fills it as it goes and sets `checked` last.
+        struct Last {
+            bool checked = false;
+            int kind = -1, p = -1, q = -1;      // -1 = Termination, else the kind of a property check and its (normalised) predicates
+            bool refined = false;               // it ran the refinement: its components are fscc's
+            bool units = false;                 // it read unit[] in proc[]'s place: fair / strong are masks of conjuncts
+            uint64_t fair = 0, strong = 0;      // the weakly / strongly fair processes (conjuncts)
+            const Masked *mask = nullptr;       // the components it judged (null: the full graph's)
+            std::vector<uint32_t> descent;      // from the witness along falling dist to the first state of the component
+            mc_live_info linfo{};               // the verdict: what the trace starts from
+        } last;
         void release() {
-            scc_built = checked = pred_built = proc_built = false;
+            scc_built = pred_built = proc_built = unit_built = false;
+            npred = 0;
             toff.reset(); tsrc.reset(); scc.reset(); size.reset(); proc.reset(); taken.reset(); disabled.reset(); done.reset();
-            pred.reset(); dist.reset(); masks.clear(); descent.clear();
+            pred.reset(); dist.reset(); masks.clear();
             enabled.reset(); open.reset(); fscc.reset(); fsize.reset(); wscc.reset(); wsize.reset();
-            last_kind = -1; last_mask = nullptr; last_strong = false; strong = 0;
-            last_units = unit_built = false; unit.reset(); of_unit.reset(); of_unit_host.clear();
+            unit.reset(); of_unit.reset(); of_unit_host.clear();
+            last = Last{};
         }
     } lv;
     void release() { built = false; offsets.reset(); dst.reset(); act.reset(); lv.release(); }
@@ -95,23 +102,17 @@ struct StateGraph {
     // mc_engine_scc on a built graph, mc_engine_scc_read
     int scc(hipStream_t stream, mc_scc_info *out);
     int scc_read(uint64_t first, uint64_t count, uint32_t *scc_out);
-    // mc_engine_liveness once the components are found and the engine's k_live_proc<S> is enqueued on `stream` (lv.proc): the rule
-    // over `all` process instances, `fair` of them weakly fair.  started: when the call began (mc_live_info.seconds).
-    int live_check(uint64_t all, uint64_t fair, hipStream_t stream, std::chrono::steady_clock::time_point started, mc_live_info *out);
-    // mc_engine_liveness_trace; level_start: the search's level table (arena index of each BFS level's first state)
     // mc_engine_predicates once the engine's k_live_pred<S> has filled lv.pred
     int pred_read(uint64_t first, uint64_t count, uint32_t *bits_out);
-    // mc_engine_liveness_check once the components, lv.proc and lv.pred are there: kind / p / q as in mc_live_property (validated by
-    // the caller against the program's predicates)
-    int live_check_masked(uint64_t all, uint64_t fair, int kind, int p, int q, hipStream_t stream, std::chrono::steady_clock::time_point started,
-                          mc_live_check_info *out);
-    // mc_engine_liveness_strong (kind < 0: lout) / mc_engine_liveness_check_strong (cout), after the same preparation as the weak twins
-    // of_unit (mc_engine_liveness_units / mc_engine_liveness_check_units): lv.unit is read in lv.proc's place, the masks are over conjuncts
-    int live_check_strong(uint64_t all, uint64_t weak, uint64_t strong, int kind, int p, int q, hipStream_t stream,
-                          std::chrono::steady_clock::time_point started, mc_live_info *lout, mc_live_check_info *cout, mc_live_strong_info *sout,
-                          const uint64_t *of_unit = nullptr);
+    // Every liveness check (live_query.h says which), once the components are found and what the query reads is there or enqueued on
+    // `stream`: lv.proc (with q.fu: lv.unit) and, for a property, lv.pred with lv.npred.  Refuses what live_query_error refuses.
+    // started: when the call began (the infos' seconds).  Of the outputs only those that apply may be non-null: lout for Termination,
+    // cout for a property, sout with q.refine.
+    int live_check(const LiveQuery &q, hipStream_t stream, std::chrono::steady_clock::time_point started, mc_live_info *lout, mc_live_check_info *cout,
+                   mc_live_strong_info *sout);
     int live_scc_read(uint64_t first, uint64_t count, uint32_t *scc_out);   // mc_engine_liveness_components
     int live_unit_read(uint64_t first, uint64_t count, int8_t *unit_out);   // mc_engine_liveness_edge_units
+    // mc_engine_liveness_trace; level_start: the search's level table (arena index of each BFS level's first state)
     int live_trace(const std::vector<uint64_t> &level_start, uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout);
 
 private:
@@ -121,9 +122,24 @@ private:
     int scc_components(uint64_t n, hipStream_t stream, int mask_q, DevBuf<uint32_t> &scc_buf, DevBuf<uint32_t> &size_buf, mc_scc_info &info,
                        const uint8_t *open = nullptr);
     int live_mask_components(int kind, int q, hipStream_t stream, const Live::Masked **mask_out, uint32_t *builds);
-    int live_reach_tail(const LiveCheck &ck, const uint32_t *scc, const uint32_t *size, const Live::Masked *mask, uint64_t fair, uint64_t strong,
-                        bool is_strong, uint32_t builds, const LiveCounters *d_lc, uint64_t strong_final, hipStream_t stream,
-                        std::chrono::steady_clock::time_point started, mc_live_check_info *out);
+    // the pieces of live_check (state_graph.hip)
+    int live_single(const LiveQuery &q, hipStream_t stream, std::chrono::steady_clock::time_point started, mc_live_info *lout, mc_live_check_info *cout);
+    int live_refined(const LiveQuery &q, hipStream_t stream, std::chrono::steady_clock::time_point started, mc_live_info *lout, mc_live_check_info *cout,
+                     mc_live_strong_info *sout);
+    int live_arrays(const LiveQuery &q);
+    int live_clear(const LiveQuery &q, hipStream_t stream);
+    void live_reduce(const LiveQuery &q, hipStream_t stream, const uint32_t *scc, const uint32_t *size, const LiveCheck &ck);
+    int live_termination(uint64_t violating, uint32_t first_root, const uint32_t *size, std::chrono::steady_clock::time_point started, mc_live_info *out);
+    int live_reach_tail(const LiveQuery &q, const uint32_t *scc, const uint32_t *size, uint32_t builds, const LiveCounters *d_lc, uint64_t strong_final,
+                        hipStream_t stream, std::chrono::steady_clock::time_point started, mc_live_check_info *out);
 };
+
+// the one refusal of a bad query: live_query_error's words behind the call's name
+inline int live_query_check(const LiveQuery &q, int npred) {
+    const std::string why = live_query_error(q, npred);
+    if (why.empty()) return MC_OK;
+    set_error(std::string(q.call) + ": " + why);
+    return MC_EBADCFG;
+}
 
 }  // namespace mc

@@ -1,7 +1,9 @@
 // state_graph.hip — the HOST half of everything that consumes the state graph's CSR arrays (state_graph.h): the reads, the strongly
-// connected components, the fairness check and its counterexample.  One object in the library: no lowering is named below this line,
+// connected components, the liveness checks and their counterexample.  One object in the library: no lowering is named below this line,
 // and the engines of all of them — the units of engine.hip, the unit of generated code built at load time — call in here.  The
-// kernels and the two device scans are engine_live.h's.
+// kernels and the two device scans are engine_live.h's.  The checks have ONE entry, live_check: it refuses or normalises the query
+// (live_query.h), starts lv.last — what live_trace and live_scc_read know of the last check — afresh, and runs the single pass
+// (live_single) or the refinement (live_refined) over shared pieces: live_arrays, live_clear, live_reduce, live_termination, live_reach_tail.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -158,56 +160,11 @@ int StateGraph::scc_read(uint64_t first, uint64_t count, uint32_t *scc_out) {
     if (count) HIP_TRY(hipMemcpy(scc_out, lv.scc.p + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return MC_OK;
 }
-// After the engine's k_live_proc<S> (enqueued on `stream`, proc[] filled): per state the masks, per component the rule.
-int StateGraph::live_check(uint64_t all, uint64_t fair, hipStream_t stream, std::chrono::steady_clock::time_point started, mc_live_info *out) {
-    const uint64_t n = info.states;
-    DevBuf<LiveCounters> d_lc;
-    int rc;
-    if ((rc = graph_alloc(lv.taken, n, "the components' taken masks", "mc_engine_liveness"))) return rc;
-    if ((rc = graph_alloc(lv.disabled, n, "the components' disabled masks", "mc_engine_liveness"))) return rc;
-    if ((rc = graph_alloc(lv.done, n, "the components' Done flags", "mc_engine_liveness"))) return rc;
-    if ((rc = graph_alloc(d_lc, 1, "the counters", "mc_engine_liveness"))) return rc;
-    LiveCounters lc;
-    memset(&lc, 0, sizeof lc);
-    lc.first_root = ~0u;
-    HIP_TRY(hipMemcpyAsync(d_lc, &lc, sizeof lc, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(lv.taken, 0, (n ? n : 1) * sizeof(unsigned long long), stream));
-    HIP_TRY(hipMemsetAsync(lv.disabled, 0, (n ? n : 1) * sizeof(unsigned long long), stream));
-    HIP_TRY(hipMemsetAsync(lv.done, 0, (n ? n : 1) * sizeof(unsigned), stream));
-    live_launch(stream, k_live_reduce<false>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, (const int8_t *)lv.proc.p, (const uint32_t *)lv.scc.p,
-                (const uint32_t *)lv.size.p, all, lv.taken.p, lv.disabled.p, lv.done.p, (const uint32_t *)nullptr, LiveCheck{});
-    live_launch(stream, k_live_verdict<false>, n, (const uint32_t *)lv.scc.p, (const uint32_t *)lv.size.p, (const unsigned long long *)lv.taken.p,
-                (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p, all, fair, d_lc.p, (const uint32_t *)nullptr, LiveCheck{},
-                (uint32_t *)nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&lc, d_lc, sizeof lc, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    memset(&lv.linfo, 0, sizeof lv.linfo);
-    lv.linfo.violated = lc.fair_components ? 1 : 0;
-    lv.linfo.fair_components = lc.fair_components;
-    if (lc.fair_components) {
-        uint32_t sz = 0;
-        HIP_TRY(hipMemcpy(&sz, lv.size.p + lc.first_root, sizeof sz, hipMemcpyDeviceToHost));
-        lv.linfo.root = lc.first_root;
-        lv.linfo.root_size = sz;
-    }
-    lv.linfo.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count();
-    lv.fair = fair;
-    lv.strong = 0;
-    lv.last_strong = false;
-    lv.last_units = false;
-    lv.checked = true;
-    lv.last_kind = -1;
-    lv.last_mask = nullptr;
-    lv.descent.clear();
-    *out = lv.linfo;
-    return MC_OK;
-}
 int StateGraph::live_scc_read(uint64_t first, uint64_t count, uint32_t *scc_out) {
-    if (!built || !lv.checked || (lv.last_kind < 0 && !lv.last_strong)) { set_error("mc_engine_liveness_components: no property check (mc_engine_liveness_check runs one; the next search releases it)"); return MC_ESTATE; }
+    if (!built || !lv.last.checked || (lv.last.kind < 0 && !lv.last.refined)) { set_error("mc_engine_liveness_components: no property check (mc_engine_liveness_check runs one; the next search releases it)"); return MC_ESTATE; }
     if (first > info.states || count > info.states - first) { set_error("mc_engine_liveness_components: range beyond the graph's states"); return MC_EBADCFG; }
     HIP_TRY(hipSetDevice(device));
-    if (count) HIP_TRY(hipMemcpy(scc_out, (lv.last_strong ? lv.fscc.p : lv.last_mask ? lv.last_mask->scc.p : lv.scc.p) + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (count) HIP_TRY(hipMemcpy(scc_out, (lv.last.refined ? lv.fscc.p : lv.last.mask ? lv.last.mask->scc.p : lv.scc.p) + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return MC_OK;
 }
 int StateGraph::live_unit_read(uint64_t first, uint64_t count, int8_t *unit_out) {
@@ -244,50 +201,122 @@ int StateGraph::live_mask_components(int kind, int q, hipStream_t stream, const 
     *mask_out = mask;
     return MC_OK;
 }
-// One (M, S, T) check over lv.pred: the components of G[M] (kept per mask), the rule per component, the reach pass, the witness; then,
-// on the host and only when violated, the way from the witness into a component (lv.descent), which fixes the component reported.
-int StateGraph::live_check_masked(uint64_t all, uint64_t fair, int kind, int p, int q, hipStream_t stream, std::chrono::steady_clock::time_point started,
-                                  mc_live_check_info *out) {
+// ------------------------------------------------------------------------------- the liveness checks: ONE entry (live_query.h says which)
+// After the engine's k_live_proc<S> / k_live_unit<S> / k_live_pred<S> (enqueued on `stream`): the query refused or normalised, the
+// record of the last check started afresh, then the single pass of the weak entries or the refinement of the strong and unit ones.
+int StateGraph::live_check(const LiveQuery &query, hipStream_t stream, std::chrono::steady_clock::time_point started, mc_live_info *lout,
+                           mc_live_check_info *cout, mc_live_strong_info *sout) {
+    if (int rc = live_query_check(query, lv.npred)) return rc;
+    const LiveQuery q = live_query_normalised(query);
+    lv.last = Live::Last{};
+    lv.last.kind = q.kind;
+    lv.last.p = q.p;
+    lv.last.q = q.q;
+    lv.last.refined = q.refine;
+    lv.last.units = q.fu != nullptr;
+    lv.last.fair = q.weak;
+    lv.last.strong = q.strong;
+    return q.refine ? live_refined(q, stream, started, lout, cout, sout) : live_single(q, stream, started, lout, cout);
+}
+// The arrays a query's passes write, allocated before anything of the check is enqueued (an allocation may wait for the device):
+// taken / disabled / done at a component's id; a refinement's enabled, open states and refined ids; a property's distances.
+int StateGraph::live_arrays(const LiveQuery &q) {
     const uint64_t n = info.states;
-    const LiveCheck ck{kind, p, q};
-    const char *call = "mc_engine_liveness_check";
+    int rc;
+    if ((rc = graph_alloc(lv.taken, n, "the components' taken masks", q.call))) return rc;
+    if ((rc = graph_alloc(lv.disabled, n, "the components' disabled masks", q.call))) return rc;
+    if ((rc = graph_alloc(lv.done, n, q.term() && !q.refine ? "the components' Done flags" : "the components' target flags", q.call))) return rc;
+    if (q.refine) {
+        if ((rc = graph_alloc(lv.enabled, n, "the components' enabled masks", q.call))) return rc;
+        if ((rc = graph_alloc(lv.open, n, "the open states", q.call))) return rc;
+        if ((rc = graph_alloc(lv.fscc, n, "the refined component ids", q.call))) return rc;
+        if ((rc = graph_alloc(lv.fsize, n, "the refined components' sizes", q.call))) return rc;
+    }
+    if (!q.term() && (rc = graph_alloc(lv.dist, n, "the distances", q.call))) return rc;
+    return MC_OK;
+}
+// ... and the per-component ones cleared, before every reduce pass
+int StateGraph::live_clear(const LiveQuery &q, hipStream_t stream) {
+    const uint64_t cells = info.states ? info.states : 1;
+    HIP_TRY(hipMemsetAsync(lv.taken, 0, cells * sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(lv.disabled, 0, cells * sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(lv.done, 0, cells * sizeof(unsigned), stream));
+    if (q.refine) HIP_TRY(hipMemsetAsync(lv.enabled, 0, cells * sizeof(unsigned long long), stream));
+    return MC_OK;
+}
+// The reduce pass over the components scc / size: the one place that picks among k_live_reduce{,_units}<MASKED> — MASKED for a property,
+// _units (lv.unit in lv.proc's place, the staged table behind the arguments) for a check label by label.
+void StateGraph::live_reduce(const LiveQuery &q, hipStream_t stream, const uint32_t *scc, const uint32_t *size, const LiveCheck &ck) {
+    const uint32_t *pred = q.term() ? nullptr : lv.pred.p;
+    const int8_t *edge_class = q.fu ? lv.unit.p : lv.proc.p;   // (the units have an array of their own: proc[] stays what a process-level check reads)
+    auto go = [&](auto kernel, auto... tab) {
+        live_launch(stream, kernel, (uint64_t)info.states, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size, q.all, lv.taken.p,
+                    lv.disabled.p, lv.done.p, pred, ck, tab...);
+    };
+    const uint64_t *tab = lv.of_unit.p;
+    if (q.fu) q.term() ? go(k_live_reduce_units<false>, tab) : go(k_live_reduce_units<true>, tab);
+    else q.term() ? go(k_live_reduce<false>) : go(k_live_reduce<true>);
+}
+// A Termination verdict as mc_live_info: `violating` components without a Done state, the least at first_root; size: at an id, the
+// states of the component (the refined sizes after a refinement).  Ends the check.
+int StateGraph::live_termination(uint64_t violating, uint32_t first_root, const uint32_t *size, std::chrono::steady_clock::time_point started, mc_live_info *out) {
+    mc_live_info &li = lv.last.linfo;
+    memset(&li, 0, sizeof li);
+    li.violated = violating ? 1 : 0;
+    li.fair_components = violating;
+    if (violating) {
+        uint32_t sz = 0;
+        HIP_TRY(hipMemcpy(&sz, size + first_root, sizeof sz, hipMemcpyDeviceToHost));
+        li.root = first_root;
+        li.root_size = sz;
+    }
+    li.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count();
+    lv.last.checked = true;
+    *out = li;
+    return MC_OK;
+}
+// The weak entries: per state the masks, per component the rule, once.  Termination judges the full graph's components; a property is one
+// (M, S, T) check over lv.pred: the components of G[M] (kept per mask), the rule per component, then the reach pass and the witness.
+int StateGraph::live_single(const LiveQuery &q, hipStream_t stream, std::chrono::steady_clock::time_point started, mc_live_info *lout, mc_live_check_info *cout) {
+    const uint64_t n = info.states;
+    const bool term = q.term();
+    const LiveCheck ck = term ? LiveCheck{} : LiveCheck{q.kind, q.p, q.q};
     int rc;
     uint32_t builds = 0;
-    lv.checked = false;
-    lv.last_units = false;
-    // ---- the components of G[M]: the full graph's for <>[]P, else one build per predicate that masks
-    const Live::Masked *mask = nullptr;
-    if ((rc = live_mask_components(kind, q, stream, &mask, &builds))) return rc;
-    const uint32_t *scc = mask ? mask->scc.p : lv.scc.p, *size = mask ? mask->size.p : lv.size.p, *pred = lv.pred.p;
+    // ---- the components of G[M]: the full graph's for Termination and <>[]P, else one build per predicate that masks
+    if (!term && (rc = live_mask_components(q.kind, q.q, stream, &lv.last.mask, &builds))) return rc;
+    const Live::Masked *mask = lv.last.mask;
+    const uint32_t *scc = mask ? mask->scc.p : lv.scc.p, *size = mask ? mask->size.p : lv.size.p, *pred = term ? nullptr : lv.pred.p;
     DevBuf<LiveCounters> d_lc;
-    if ((rc = graph_alloc(lv.taken, n, "the components' taken masks", call))) return rc;
-    if ((rc = graph_alloc(lv.disabled, n, "the components' disabled masks", call))) return rc;
-    if ((rc = graph_alloc(lv.done, n, "the components' target flags", call))) return rc;
-    if ((rc = graph_alloc(lv.dist, n, "the distances", call))) return rc;
-    if ((rc = graph_alloc(d_lc, 1, "the counters", call))) return rc;
+    if ((rc = live_arrays(q))) return rc;
+    if ((rc = graph_alloc(d_lc, 1, "the counters", q.call))) return rc;
+    uint32_t *dist = term ? nullptr : lv.dist.p;
     LiveCounters lc;
     memset(&lc, 0, sizeof lc);
     lc.first_root = ~0u;
     HIP_TRY(hipMemcpyAsync(d_lc, &lc, sizeof lc, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(lv.taken, 0, (n ? n : 1) * sizeof(unsigned long long), stream));
-    HIP_TRY(hipMemsetAsync(lv.disabled, 0, (n ? n : 1) * sizeof(unsigned long long), stream));
-    HIP_TRY(hipMemsetAsync(lv.done, 0, (n ? n : 1) * sizeof(unsigned), stream));
-    live_launch(stream, k_live_reduce<true>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, (const int8_t *)lv.proc.p, scc, size, all, lv.taken.p,
-                lv.disabled.p, lv.done.p, pred, ck);
-    live_launch(stream, k_live_verdict<true>, n, scc, size, (const unsigned long long *)lv.taken.p, (const unsigned long long *)lv.disabled.p,
-                (const unsigned *)lv.done.p, all, fair, d_lc.p, pred, ck, lv.dist.p);
-    live_launch(stream, k_live_reach_init, n, scc, pred, ck, lv.dist.p);
+    if ((rc = live_clear(q, stream))) return rc;
+    live_reduce(q, stream, scc, size, ck);
+    auto verdict = [&](auto kernel) {
+        live_launch(stream, kernel, n, scc, size, (const unsigned long long *)lv.taken.p, (const unsigned long long *)lv.disabled.p,
+                    (const unsigned *)lv.done.p, q.all, q.weak, d_lc.p, pred, ck, dist);
+    };
+    term ? verdict(k_live_verdict<false>) : verdict(k_live_verdict<true>);
+    if (!term) live_launch(stream, k_live_reach_init, n, scc, pred, ck, lv.dist.p);
     HIP_TRY(hipGetLastError());
-    return live_reach_tail(ck, scc, size, mask, fair, 0, false, builds, d_lc.p, 0, stream, started, out);
+    if (!term) return live_reach_tail(q, scc, size, builds, d_lc.p, 0, stream, started, cout);
+    HIP_TRY(hipMemcpyAsync(&lc, d_lc, sizeof lc, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return live_termination(lc.fair_components, lc.first_root, lv.size.p, started, lout);
 }
 // What a property check does once dist[] is 0 on the states of the violating components and LIVE_FAR elsewhere: the reach pass, the
-// witness, the counters, and — when violated — the descent from the witness.  scc / size: the ids and sizes the descent's component is
-// read from (a strong check: the refined ones; fair_components is then the caller's count, d_lc is not read).
-int StateGraph::live_reach_tail(const LiveCheck &ck, const uint32_t *scc, const uint32_t *size, const Live::Masked *mask, uint64_t fair, uint64_t strong,
-                                bool is_strong, uint32_t builds, const LiveCounters *d_lc, uint64_t strong_final, hipStream_t stream,
-                                std::chrono::steady_clock::time_point started, mc_live_check_info *out) {
+// witness, the counters, and — when violated, on the host — the descent from the witness into a component (lv.last.descent), which
+// fixes the component reported.  scc / size: the ids and sizes the descent's component is read from (a refinement: the refined ones;
+// fair_components is then the caller's count, d_lc is not read).  Ends the check.
+int StateGraph::live_reach_tail(const LiveQuery &q, const uint32_t *scc, const uint32_t *size, uint32_t builds, const LiveCounters *d_lc, uint64_t strong_final,
+                                hipStream_t stream, std::chrono::steady_clock::time_point started, mc_live_check_info *out) {
     const uint64_t n = info.states;
-    const int kind = ck.kind, p = ck.p, q = ck.q;
+    const LiveCheck ck{q.kind, q.p, q.q};
     const uint32_t *pred = lv.pred.p;
     DevBuf<LiveCheckCounters> d_cc;
     DevBuf<unsigned> flag;
@@ -316,7 +345,7 @@ int StateGraph::live_reach_tail(const LiveCheck &ck, const uint32_t *scc, const 
     out->mask_states = cc.mask_states;
     out->bad_starts = cc.bad_starts;
     out->scc_builds = builds;
-    lv.descent.clear();
+    std::vector<uint32_t> &descent = lv.last.descent;
     if (out->violated) {
         // from the witness along strictly falling dist inside M, the least such successor each time
         std::vector<uint64_t> off((size_t)n + 1);
@@ -325,7 +354,7 @@ int StateGraph::live_reach_tail(const LiveCheck &ck, const uint32_t *scc, const 
         HIP_TRY(hipMemcpy(dist.data(), lv.dist.p, dist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (info.edges) HIP_TRY(hipMemcpy(d.data(), dst.p, d.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         uint32_t cur = cc.witness;
-        lv.descent.push_back(cur);
+        descent.push_back(cur);
         while (dist[cur] != 0) {
             uint32_t best = ~0u;
             for (uint64_t k = off[cur]; k < off[cur + 1]; ++k) {
@@ -333,7 +362,7 @@ int StateGraph::live_reach_tail(const LiveCheck &ck, const uint32_t *scc, const 
                 if (t < n && t != cur && dist[t] != LIVE_FAR && dist[t] + 1 == dist[cur] && t < best) best = t;   // (a dist at all: the state is in M)
             }
             if (best == ~0u) { set_error("mc_engine_liveness_check: state " + std::to_string(cur) + " has a distance and no successor one step nearer"); return MC_ESTATE; }
-            lv.descent.push_back(best);
+            descent.push_back(best);
             cur = best;
         }
         uint32_t root = 0, sz = 0;
@@ -344,60 +373,44 @@ int StateGraph::live_reach_tail(const LiveCheck &ck, const uint32_t *scc, const 
         out->root_size = sz;
     }
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count();
-    memset(&lv.linfo, 0, sizeof lv.linfo);
-    lv.linfo.violated = out->violated;
-    lv.linfo.fair_components = out->fair_components;
-    lv.linfo.root = out->root;
-    lv.linfo.root_size = out->root_size;
-    lv.linfo.seconds = out->seconds;
-    lv.fair = fair;
-    lv.strong = strong;
-    lv.last_strong = is_strong;
-    lv.last_kind = kind;
-    lv.last_p = p;
-    lv.last_q = q;
-    lv.last_mask = mask;
-    lv.checked = true;
+    mc_live_info &li = lv.last.linfo;
+    memset(&li, 0, sizeof li);
+    li.violated = out->violated;
+    li.fair_components = out->fair_components;
+    li.root = out->root;
+    li.root_size = out->root_size;
+    li.seconds = out->seconds;
+    lv.last.checked = true;
     return MC_OK;
 }
-// A check under strong fairness of the processes of `strong`: liveness.h's refinement, one round per loop.  kind < 0:
-// Termination (M = all, T = not Done; lout), else the (M, S, T) check of live_check_masked (cout).  Round 1 runs on the components a
-// weak check of the same M uses — lv.scc, or the mask's build, made and kept here as live_check_masked does —, later rounds on builds of
-// the open subgraph into lv.wscc / lv.wsize; nothing a weak check reads is written.  One blocking read per round beside the build's.
-// of_unit (LIVE_UNIT_TAB entries on the host, or null): lv.unit holds the edges' UNITS, the masks are masks of
-// fairness conjuncts, and the table-driven twins of the three kernels that read the edges are launched; null launches what it launched.
-int StateGraph::live_check_strong(uint64_t all, uint64_t weak, uint64_t strong, int kind, int p, int q, hipStream_t stream,
-                                  std::chrono::steady_clock::time_point started, mc_live_info *lout, mc_live_check_info *cout, mc_live_strong_info *sout,
-                                  const uint64_t *of_unit) {
+// The strong and unit entries: a check under strong fairness of the processes of q.strong, liveness.h's refinement,
+// one round per loop.  Termination: M = all, T = not Done (lout), else the (M, S, T) check of live_single (cout).  Round 1 runs on the
+// components a weak check of the same M uses — lv.scc, or the mask's build, made and kept here as live_single does —, later rounds on
+// builds of the open subgraph into lv.wscc / lv.wsize; nothing a weak check reads is written.  One blocking read per round beside the
+// build's.  q.fu: lv.unit holds the edges' UNITS, the masks are masks of fairness conjuncts, and the table-driven
+// twins of the three kernels that read the edges are launched.
+int StateGraph::live_refined(const LiveQuery &q, hipStream_t stream, std::chrono::steady_clock::time_point started, mc_live_info *lout, mc_live_check_info *cout,
+                             mc_live_strong_info *sout) {
     const uint64_t n = info.states, cells = n ? n : 1;
-    const bool term = kind < 0, units = of_unit != nullptr;
-    const LiveCheck ck{term ? LIVE_STABLE : kind, p, q};   // (Termination: every state is in M; the target is the Done flag's, not a predicate's)
-    const char *call = units ? (term ? "mc_engine_liveness_units" : "mc_engine_liveness_check_units")
-                             : (term ? "mc_engine_liveness_strong" : "mc_engine_liveness_check_strong");
+    const bool term = q.term(), units = q.fu != nullptr;
+    const uint64_t all = q.all, weak = q.weak, strong = q.strong;
+    const LiveCheck ck{term ? LIVE_STABLE : q.kind, q.p, q.q};   // (Termination: every state is in M; the target is the Done flag's, not a predicate's)
     int rc;
     uint32_t builds = 0;
-    lv.checked = false;
-    lv.last_units = units;
     if (units) {
-        lv.of_unit_host.assign(of_unit, of_unit + LIVE_UNIT_TAB);
-        if ((rc = graph_alloc(lv.of_unit, LIVE_UNIT_TAB, "the units' conjuncts", call))) return rc;
+        lv.of_unit_host.assign(q.fu->of_unit, q.fu->of_unit + LIVE_UNIT_TAB);
+        if ((rc = graph_alloc(lv.of_unit, LIVE_UNIT_TAB, "the units' conjuncts", q.call))) return rc;
         HIP_TRY(hipMemcpyAsync(lv.of_unit, lv.of_unit_host.data(), LIVE_UNIT_TAB * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
     }
     const uint64_t *d_tab = lv.of_unit.p;
-    const int8_t *edge_class = units ? lv.unit.p : lv.proc.p;   // (the units have an array of their own: proc[] stays what a process-level check reads)
-    const Live::Masked *mask = nullptr;
-    if (!term && (rc = live_mask_components(kind, q, stream, &mask, &builds))) return rc;
+    const int8_t *edge_class = units ? lv.unit.p : lv.proc.p;
+    if (!term && (rc = live_mask_components(q.kind, q.q, stream, &lv.last.mask, &builds))) return rc;
+    const Live::Masked *mask = lv.last.mask;
     const uint32_t *pred = term ? nullptr : lv.pred.p;
     DevBuf<LiveStrongCounters> d_sc;
-    if ((rc = graph_alloc(lv.taken, n, "the components' taken masks", call))) return rc;
-    if ((rc = graph_alloc(lv.disabled, n, "the components' disabled masks", call))) return rc;
-    if ((rc = graph_alloc(lv.done, n, "the components' target flags", call))) return rc;
-    if ((rc = graph_alloc(lv.enabled, n, "the components' enabled masks", call))) return rc;
-    if ((rc = graph_alloc(lv.open, n, "the open states", call))) return rc;
-    if ((rc = graph_alloc(lv.fscc, n, "the refined component ids", call))) return rc;
-    if ((rc = graph_alloc(lv.fsize, n, "the refined components' sizes", call))) return rc;
-    if (!term && (rc = graph_alloc(lv.dist, n, "the distances", call))) return rc;
-    if ((rc = graph_alloc(d_sc, 1, "the counters", call))) return rc;
+    if ((rc = live_arrays(q))) return rc;
+    if ((rc = graph_alloc(d_sc, 1, "the counters", q.call))) return rc;
+    uint32_t *dist = term ? nullptr : lv.dist.p;
     LiveStrongCounters sc;
     memset(&sc, 0, sizeof sc);
     sc.first_root = ~0u;
@@ -406,52 +419,33 @@ int StateGraph::live_check_strong(uint64_t all, uint64_t weak, uint64_t strong, 
     if (term) live_launch(stream, k_live_open_init<false>, n, pred, ck, lv.open.p, lv.fscc.p, lv.fsize.p);
     else live_launch(stream, k_live_open_init<true>, n, pred, ck, lv.open.p, lv.fscc.p, lv.fsize.p);
     const uint32_t *scc = mask ? mask->scc.p : lv.scc.p, *size = mask ? mask->size.p : lv.size.p;
+    // the two other passes that read the edges: `tab` is the staged table of the _units twin, or nothing
+    auto enabled = [&](auto kernel, auto... tab) {
+        live_launch(stream, kernel, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size, (const uint8_t *)lv.open.p, lv.enabled.p, tab...);
+    };
+    auto refine = [&](auto kernel, auto... tab) {
+        live_launch(stream, kernel, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size, (const unsigned long long *)lv.taken.p,
+                    (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p, (const unsigned long long *)lv.enabled.p, all, weak, strong, term,
+                    lv.open.p, lv.fscc.p, lv.fsize.p, dist, d_sc.p, tab...);
+    };
     const uint32_t bound = live_strong_rounds(all, strong);
     uint32_t rounds = 0, strong_builds = 0;
     for (;;) {
         ++rounds;
-        HIP_TRY(hipMemsetAsync(lv.taken, 0, cells * sizeof(unsigned long long), stream));
-        HIP_TRY(hipMemsetAsync(lv.disabled, 0, cells * sizeof(unsigned long long), stream));
-        HIP_TRY(hipMemsetAsync(lv.done, 0, cells * sizeof(unsigned), stream));
-        HIP_TRY(hipMemsetAsync(lv.enabled, 0, cells * sizeof(unsigned long long), stream));
+        if ((rc = live_clear(q, stream))) return rc;
         HIP_TRY(hipMemsetAsync(&d_sc.p->open, 0, sizeof(unsigned), stream));
-        if (units && term)
-            live_launch(stream, k_live_reduce_units<false>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size, all,
-                        lv.taken.p, lv.disabled.p, lv.done.p, pred, ck, d_tab);
-        else if (units)
-            live_launch(stream, k_live_reduce_units<true>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size, all,
-                        lv.taken.p, lv.disabled.p, lv.done.p, pred, ck, d_tab);
-        else if (term)
-            live_launch(stream, k_live_reduce<false>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size, all,
-                        lv.taken.p, lv.disabled.p, lv.done.p, pred, ck);
-        else
-            live_launch(stream, k_live_reduce<true>, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size, all,
-                        lv.taken.p, lv.disabled.p, lv.done.p, pred, ck);
-        if (units)
-            live_launch(stream, k_live_enabled_units, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size,
-                        (const uint8_t *)lv.open.p, lv.enabled.p, d_tab);
-        else
-            live_launch(stream, k_live_enabled, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size,
-                        (const uint8_t *)lv.open.p, lv.enabled.p);
+        live_reduce(q, stream, scc, size, ck);
+        units ? enabled(k_live_enabled_units, d_tab) : enabled(k_live_enabled);
         live_launch(stream, k_live_classify, n, scc, size, (const uint8_t *)lv.open.p, (const unsigned long long *)lv.taken.p,
                     (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p, (const unsigned long long *)lv.enabled.p, all, weak, strong, term,
                     d_sc.p);
-        if (units)
-            live_launch(stream, k_live_refine_units, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size,
-                        (const unsigned long long *)lv.taken.p, (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p,
-                        (const unsigned long long *)lv.enabled.p, all, weak, strong, term, lv.open.p, lv.fscc.p, lv.fsize.p,
-                        term ? (uint32_t *)nullptr : lv.dist.p, d_sc.p, d_tab);
-        else
-            live_launch(stream, k_live_refine, n, (const uint64_t *)offsets.p, (const uint32_t *)dst.p, edge_class, scc, size,
-                        (const unsigned long long *)lv.taken.p, (const unsigned long long *)lv.disabled.p, (const unsigned *)lv.done.p,
-                        (const unsigned long long *)lv.enabled.p, all, weak, strong, term, lv.open.p, lv.fscc.p, lv.fsize.p, term ? (uint32_t *)nullptr : lv.dist.p,
-                        d_sc.p);
+        units ? refine(k_live_refine_units, d_tab) : refine(k_live_refine);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&sc, d_sc, sizeof sc, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         if (!sc.open) break;
         if (rounds >= bound) {
-            set_error(std::string(call) + ": the refinement did not converge after " + std::to_string(rounds) + " rounds (" + std::to_string(bound - 1) +
+            set_error(std::string(q.call) + ": the refinement did not converge after " + std::to_string(rounds) + " rounds (" + std::to_string(bound - 1) +
                       (units ? " strong conjuncts)" : " strongly fair processes)"));
             return MC_ESTATE;
         }
@@ -467,47 +461,29 @@ int StateGraph::live_check_strong(uint64_t all, uint64_t weak, uint64_t strong, 
     sout->closed_states = sc.closed;
     sout->final_components = sc.final_components;
     if (term) {
-        memset(&lv.linfo, 0, sizeof lv.linfo);
-        lv.linfo.violated = sc.final_components ? 1 : 0;
-        lv.linfo.fair_components = sc.final_components;
-        if (sc.final_components) {
-            uint32_t sz = 0;
-            HIP_TRY(hipMemcpy(&sz, lv.fsize.p + sc.first_root, sizeof sz, hipMemcpyDeviceToHost));
-            lv.linfo.root = sc.first_root;
-            lv.linfo.root_size = sz;
-        }
-        lv.linfo.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count();
-        lv.fair = weak;
-        lv.strong = strong;
-        lv.last_strong = true;
-        lv.checked = true;
-        lv.last_kind = -1;
-        lv.last_mask = nullptr;
-        lv.descent.clear();
-        *lout = lv.linfo;
-        sout->seconds = lv.linfo.seconds;
+        if ((rc = live_termination(sc.final_components, sc.first_root, lv.fsize.p, started, lout))) return rc;
+        sout->seconds = lout->seconds;
         return MC_OK;
     }
-    if ((rc = live_reach_tail(LiveCheck{kind, p, q}, lv.fscc.p, lv.fsize.p, mask, weak, strong, true, builds, nullptr, sc.final_components, stream, started, cout)))
-        return rc;
+    if ((rc = live_reach_tail(q, lv.fscc.p, lv.fsize.p, builds, nullptr, sc.final_components, stream, started, cout))) return rc;
     sout->seconds = cout->seconds;
     return MC_OK;
 }
 // The counterexample of the last mc_engine_liveness, built on the host from the arrays (deterministic given them).
 // prefix: from an initial state to the chosen component's id (its least state) — after a property check: to the witness, and on along
-// lv.descent to the first state of the component —, one BFS level back per step along the transpose: the
+// lv.last.descent to the first state of the component —, one BFS level back per step along the transpose: the
 // least source in the previous level (level boundaries: level_start).  cycle: a closed walk inside the component that starts at
 // that state and, for every weakly fair process, takes a real step of it or passes a state where it is disabled; the last entry has an
 // edge back to the first.  Empty = the behaviour stutters in the prefix's last state for ever.  After a check by units (DESIGN section
 // 21) "process" reads "conjunct": a step of it is an edge whose unit belongs to it.
 int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *prefix_out, size_t *nprefix_inout, uint32_t *cycle_out, size_t *ncycle_inout) {
-    if (!built || !lv.checked) { set_error("mc_engine_liveness_trace: no liveness check (mc_engine_liveness runs it; the next search releases it)"); return MC_ESTATE; }
-    if (!lv.linfo.violated) { set_error("mc_engine_liveness_trace: the property holds: there is no counterexample"); return MC_ESTATE; }
+    if (!built || !lv.last.checked) { set_error("mc_engine_liveness_trace: no liveness check (mc_engine_liveness runs it; the next search releases it)"); return MC_ESTATE; }
+    if (!lv.last.linfo.violated) { set_error("mc_engine_liveness_trace: the property holds: there is no counterexample"); return MC_ESTATE; }
     HIP_TRY(hipSetDevice(device));
     const uint64_t n = info.states, edges = info.edges;
-    const uint32_t root = (uint32_t)lv.linfo.root;
-    const bool prop = lv.last_kind >= 0 && !lv.descent.empty();
-    const uint32_t target = prop ? lv.descent.front() : root;   // where the way back to an initial state starts
+    const uint32_t root = (uint32_t)lv.last.linfo.root;
+    const bool prop = lv.last.kind >= 0 && !lv.last.descent.empty();
+    const uint32_t target = prop ? lv.last.descent.front() : root;   // where the way back to an initial state starts
     // ---- prefix
     std::vector<uint32_t> prefix{target};
     auto level_of = [&](uint32_t x) { return (size_t)(std::upper_bound(level_start.begin(), level_start.end(), (uint64_t)x) - level_start.begin()) - 1; };
@@ -524,19 +500,19 @@ int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *p
         cur = best;
     }
     std::reverse(prefix.begin(), prefix.end());
-    if (prop) prefix.insert(prefix.end(), lv.descent.begin() + 1, lv.descent.end());
+    if (prop) prefix.insert(prefix.end(), lv.last.descent.begin() + 1, lv.last.descent.end());
     const uint32_t entry = prefix.back();   // where the behaviour enters the component: the cycle starts and ends here
     // ---- cycle
     std::vector<uint64_t> off((size_t)n + 1);
     std::vector<uint32_t> dst((size_t)edges), scc((size_t)n);
     std::vector<int8_t> proc((size_t)edges);
     HIP_TRY(hipMemcpy(off.data(), offsets.p, off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(scc.data(), lv.last_strong ? lv.fscc.p : prop && lv.last_mask ? lv.last_mask->scc.p : lv.scc.p, scc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(scc.data(), lv.last.refined ? lv.fscc.p : prop && lv.last.mask ? lv.last.mask->scc.p : lv.scc.p, scc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (edges) {
         HIP_TRY(hipMemcpy(dst.data(), this->dst.p, dst.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(proc.data(), lv.last_units ? lv.unit.p : lv.proc.p, proc.size() * sizeof(int8_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(proc.data(), lv.last.units ? lv.unit.p : lv.proc.p, proc.size() * sizeof(int8_t), hipMemcpyDeviceToHost));
     }
-    const uint64_t *tab = lv.last_units ? lv.of_unit_host.data() : nullptr;
+    const uint64_t *tab = lv.last.units ? lv.of_unit_host.data() : nullptr;
     auto counts_for = [&](int8_t pr, int p) { return tab ? (live_conjuncts(tab, pr) >> p & 1) != 0 : pr == p; };   // is an edge of pr a step of p
     std::vector<uint32_t> members;
     for (uint64_t v = 0; v < n; ++v) if (scc[(size_t)v] == root) members.push_back((uint32_t)v);
@@ -562,8 +538,8 @@ int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *p
     };
     bool ok = true;
     for (int p = 0; p < 64 && ok; ++p) {
-        if (!((lv.fair | lv.strong) >> p & 1)) continue;
-        const bool sf = lv.strong >> p & 1;   // strongly fair: taken inside, or — the refinement saw to it — disabled everywhere in the component
+        if (!((lv.last.fair | lv.last.strong) >> p & 1)) continue;
+        const bool sf = lv.last.strong >> p & 1;   // strongly fair: taken inside, or — the refinement saw to it — disabled everywhere in the component
         bool found = false;
         for (size_t mi = 0; mi < members.size() && !found; ++mi) {   // a real step of p inside the component: the first in index order
             const uint32_t u = members[mi];
@@ -585,10 +561,10 @@ int StateGraph::live_trace(const std::vector<uint64_t> &level_start, uint32_t *p
         }
         if (!found) ok = false;
     }
-    if (ok && prop && lv.last_kind == LIVE_STABLE) {   // <>[]P: the walk passes a ~P state, the component's least
+    if (ok && prop && lv.last.kind == LIVE_STABLE) {   // <>[]P: the walk passes a ~P state, the component's least
         std::vector<uint32_t> bits((size_t)n);
         HIP_TRY(hipMemcpy(bits.data(), lv.pred.p, bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        const LiveCheck ck{lv.last_kind, lv.last_p, lv.last_q};
+        const LiveCheck ck{lv.last.kind, lv.last.p, lv.last.q};
         bool found = false;
         for (size_t mi = 0; mi < members.size() && !found; ++mi)
             if (live_in_target(ck, bits[members[mi]])) { found = true; ok = go(members[mi]); }
