@@ -560,7 +560,9 @@ int mc_shard_begin(mc_engine *e);                                  /* Init: keep
  * local frontier and holds all prefix fingerprints in its seen-set.  levels_out[0 .. *nlevels) = states per level of the
  * prefix, the last one being the level the sharded rounds continue with (*nlevels in: capacity, out: count).  Only
  * rank 0 reports the prefix's `generated`; distinct_local excludes what another rank already counts.  max_distinct /
- * max_levels (0 = none) are the budgets of the WHOLE job: the prefix stops where a single-GPU run would. */
+ * max_levels (0 = none) are the budgets of the WHOLE job: the prefix stops where a single-GPU run would.
+ * The level it stops at is the FIRST one with at least min_frontier states.  The rank's share lies behind the prefix in its arena
+ * (indices sum(levels_out) ...), each entry a copy (mc_shard_fetch: parent_slot 0xfffc, parent_idx = the original). */
 int mc_shard_begin_replicated(mc_engine *e, uint64_t min_frontier, uint64_t max_distinct, uint64_t max_levels,
                               uint64_t *levels_out, uint32_t *nlevels);
 int mc_shard_level_size(mc_engine *e, uint64_t *frontier_states);  /* local frontier of the current level          */
@@ -575,6 +577,10 @@ int mc_shard_expand_finish(mc_engine *e, uint32_t slot, uint64_t *send_fp, uint6
 int mc_shard_probe(mc_engine *e, const uint64_t *recv_fp, uint64_t n, uint8_t *answers);
 int mc_shard_materialise(mc_engine *e, const uint8_t *answers_back, uint8_t *send_states, uint64_t send_cap,
                          uint64_t *send_counts /* [shard_count] host, in states */);
+/* answers_back: one byte per fingerprint of the slot's send_fp, same positions, non-zero = new.  Owner t's bucket holds the successors
+ * of the positively answered positions of ITS range, in the order of those positions, and the lanes behind its last state are zero;
+ * send_cap is in states.  Neither this call nor mc_shard_keep* consumes the slot's candidates: until the slot's next
+ * mc_shard_expand_launch either may be called again with other answers. */
 int mc_shard_materialise_slot(mc_engine *e, uint32_t slot, const uint8_t *answers_back, uint8_t *send_states,
                               uint64_t send_cap, uint64_t *send_counts);
 int mc_shard_ingest(mc_engine *e, const uint8_t *recv_states, uint64_t n);
@@ -586,7 +592,10 @@ int mc_shard_ingest(mc_engine *e, const uint8_t *recv_states, uint64_t n);
  *       expand kernel with an event and packs owner t's candidates into send_fp[t * cap + 1 ...], count in send_fp[t * cap];
  *   _probe_pack(recv_fp[shard_count * cap], cap, answers[shard_count * cap]): bucket s came from rank s; answers keep the
  *       positions and are 0 outside a bucket's count;
- *   _keep_pack(slot, answers_back[shard_count * cap], cap): the sender materialises its positively answered candidates.
+ *   _keep_pack(slot, answers_back[shard_count * cap], cap): the sender materialises its positively answered candidates, appended
+ *       to its frontier in the order of their positions.  answers_back must be 0 at every count word and behind every bucket's
+ *       count (what _probe_pack writes there): no candidate lies at such a position, and a non-zero byte would be taken for one;
+ *       the bucket of an owner that did not fit (count word 0) holds nothing;
  * cap must be the same on every rank (derive it from the level's frontier sizes, which every rank knows).  A bucket that
  * does not fit is not truncated: the level fails with MC_EROUTE at mc_shard_end_level ("an exchange bucket is full"). */
 int mc_shard_expand_pack(mc_engine *e, uint32_t slot, uint64_t *send_fp, uint64_t cap);

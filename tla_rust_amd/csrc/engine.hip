@@ -1049,7 +1049,9 @@ struct Engine : EngineBase {
                 memset(h_lc, 0, sizeof(LevelCtl));
                 h_lc->lo = lo;
                 h_lc->hi = hi;
-                h_lc->max_states = blind_max;
+                // (a replicated prefix ends BEFORE the first level of stop_frontier states, inside a batch too: k_end_level leaves a batch
+                //  at a level of more than max_states, so that level is the one the loop head hands to the sharded rounds)
+                h_lc->max_states = fr.stop_frontier && fr.stop_frontier - 1 < blind_max ? fr.stop_frontier - 1 : blind_max;
                 h_lc->max_distinct = cfg.max_distinct;
                 h_lc->levels_left = cfg.max_levels ? (unsigned)(cfg.max_levels - level) : 0u;
                 HIP_TRY(hipMemcpyAsync(d_lc, h_lc, sizeof(LevelCtl), hipMemcpyHostToDevice, stream));
