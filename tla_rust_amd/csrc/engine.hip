@@ -556,16 +556,9 @@ struct Engine : EngineBase {
 
     // ------------------------------------------------------------------------------- coverage (engine_coverage.h)
     // All on `stream`, behind the expand kernels of the level they count: the arena rows and trace records they read are final by then.
-    // The states [lo, hi) in the chunks the expand kernel saw: f(c0, c1, ncols), column 0 = the 64-aligned state at or below c0.
+    // The states [lo, hi) in the chunks the expand kernel saw (engine_coverage.h: each_chunk), at this engine's chunk size
     template <class F>
-    void each_chunk(uint64_t lo, uint64_t hi, F &&f) {
-        for (uint64_t c0 = lo; c0 < hi;) {
-            const uint64_t base = c0 & ~63ull;
-            const uint64_t c1 = base + chunk < hi ? base + chunk : hi;
-            f(c0, c1, ((c1 - base) + 63) & ~63ull);
-            c0 = c1;
-        }
-    }
+    void each_chunk(uint64_t lo, uint64_t hi, F &&f) { mc::each_chunk(lo, hi, chunk, f); }
     // generated: the states [lo, hi) a level expanded
     void cov_generated(uint64_t lo, uint64_t hi) {
         each_chunk(lo, hi, [&](uint64_t c0, uint64_t c1, uint64_t ncols) {

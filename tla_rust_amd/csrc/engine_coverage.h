@@ -12,6 +12,19 @@
 
 namespace mc {
 
+// The states [lo, hi) in the chunks the expand kernel saw: f(c0, c1, ncols), column 0 = the 64-aligned state at or below c0.  Host code:
+// how the engine launches every kernel that takes (lo, hi, ncols) — the two here, k_viol_frontier, the graph passes.  chunk: a multiple
+// of 64, at least 64.
+template <class F>
+inline void each_chunk(uint64_t lo, uint64_t hi, uint64_t chunk, F &&f) {
+    for (uint64_t c0 = lo; c0 < hi;) {
+        const uint64_t base = c0 & ~63ull;
+        const uint64_t c1 = base + chunk < hi ? base + chunk : hi;
+        f(c0, c1, ((c1 - base) + 63) & ~63ull);
+        c0 = c1;
+    }
+}
+
 // One bump of the workgroup's histogram by the lanes of a wavefront with `on` set, each for its bin `bin`.  Every lane of the wavefront
 // calls it (the shuffle and the ballots are wavefront operations).  Where the lanes agree on the bin — always when the action is a
 // function of the slot, often otherwise — one lane adds popcount(ballot); else every lane does its own LDS atomic add.
