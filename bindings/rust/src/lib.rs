@@ -82,6 +82,9 @@ pub struct mc_live_strong_info { pub rounds: u32, pub scc_builds: u32, pub close
 // one check a cfg's PROPERTY name became (mc_program_live_property), and what mc_engine_liveness_check* report about it
 #[repr(C)]
 pub struct mc_live_property { pub origin: [c_char; 64], pub name: [c_char; 128], pub kind: i32, pub p: i32, pub q: i32, pub refused: i32, pub reason: [c_char; 256] }
+// one safety part of a cfg's PROPERTY (mc_program_action_property): kind 0 `[][A]_v`, 1 `[]P`, 2 an initial predicate
+#[repr(C)]
+pub struct mc_action_property { pub origin: [c_char; 64], pub kind: i32, pub index: i32, pub text: [c_char; 256] }
 #[repr(C)]
 pub struct mc_live_check_info { pub violated: i32, pub sweeps: u32, pub fair_components: u64, pub witness: u64, pub root: u64, pub root_size: u64,
                                 pub mask_states: u64, pub bad_starts: u64, pub scc_builds: u32, pub pad: u32, pub seconds: f64 }
@@ -166,6 +169,8 @@ extern "C" {
     // the cfg's VIEW (the text of its definition, null without one) and ACTION_CONSTRAINT names (null past the last)
     pub fn mc_program_view(p: *const mc_program) -> *const c_char;
     pub fn mc_program_action_constraint(p: *const mc_program, index: c_int) -> *const c_char;
+    // the safety parts of the cfg's PROPERTYs the search checks (`[][A]_v`, `[]P`, initial predicates): entry `index`, MC_EBADCFG past the last
+    pub fn mc_program_action_property(p: *const mc_program, index: c_int, out: *mut mc_action_property) -> c_int;
     pub fn mc_program_free(p: *mut mc_program);
     pub fn mc_state_bytes(spec: *const mc_spec_desc) -> usize;
     pub fn mc_state_format(spec: *const mc_spec_desc, state: *const u8, buf: *mut c_char, cap: usize) -> c_int;

@@ -827,6 +827,23 @@ const char *mc_program_live_predicate(const mc_program *p, int index);
  * values; which state represents a view value is the one that arrived first — reproducible exactly when equal views imply equal futures. */
 const char *mc_program_view(const mc_program *p);
 const char *mc_program_action_constraint(const mc_program *p, int index);
+/* the SAFETY parts of the cfg's PROPERTYs that the search itself checks, one entry per conjunct, MC_EBADCFG past
+ * the last.  MC_APROP_STEP: `[][A]_v`, evaluated as `A \/ UNCHANGED v` on every successor the search generates — new or seen before,
+ * inside the model or not, refused by an ACTION_CONSTRAINT or not; never on the terminating disjunct or on a successor that is an
+ * error already.  MC_APROP_ALWAYS: `[]P`, one more invariant behind the cfg's INVARIANTs.  MC_APROP_INIT: a state predicate beside a
+ * `[][A]_v` (the shape Init /\ [][Next]_v /\ fairness), checked on the initial states.  A violation is MC_V_INVARIANT with
+ * mc_result.violated_invariant = `index`: the `[]P` entries count among the invariants (mc_invariant_name gives the PROPERTY's name),
+ * a step's and an initial predicate's index lies behind them, which is how a caller tells a property of a step from an invariant.
+ * A successor that breaks an INVARIANT as well reports the invariant: the status word carries one index.  Under MC_F_CONTINUE a step
+ * that breaks a `[][A]_v` is fatal, as the Paxos models' PROPERTY is: the search ends at the end of that level, the entry comes last. */
+enum { MC_APROP_STEP = 0, MC_APROP_ALWAYS = 1, MC_APROP_INIT = 2 };
+typedef struct mc_action_property {
+    char    origin[64];        /* the cfg's PROPERTY name                                            */
+    int32_t kind;              /* MC_APROP_*                                                         */
+    int32_t index;             /* the invariant index a violation reports                            */
+    char    text[256];         /* the conjunct as the module writes it, tokens joined by one blank   */
+} mc_action_property;
+int mc_program_action_property(const mc_program *p, int index, mc_action_property *out);
 void mc_program_free(mc_program *p);
 
 /* ------------------------------------------------------------------ helpers (host only) */

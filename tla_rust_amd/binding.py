@@ -146,6 +146,14 @@ class LiveStrongInfo(C.Structure):
                 ("seconds", C.c_double)]
 
 
+class ActionProperty(C.Structure):
+    """mc_action_property"""
+    _fields_ = [("origin", C.c_char * 64), ("kind", C.c_int32), ("index", C.c_int32), ("text", C.c_char * 256)]
+
+
+APROP_KINDS = ("step", "always", "init")   # MC_APROP_*
+
+
 class LiveProperty(C.Structure):
     """mc_live_property"""
     _fields_ = [("origin", C.c_char * 64), ("name", C.c_char * 128), ("kind", C.c_int32), ("p", C.c_int32), ("q", C.c_int32),
@@ -324,6 +332,7 @@ def lib():
         L.mc_program_view.restype = C.c_char_p
         L.mc_program_action_constraint.argtypes = [C.c_void_p, C.c_int]
         L.mc_program_action_constraint.restype = C.c_char_p
+        L.mc_program_action_property.argtypes = [C.c_void_p, C.c_int, C.POINTER(ActionProperty)]
         L.mc_program_property.argtypes = [C.c_void_p, C.c_int]
         L.mc_program_property.restype = C.c_char_p
         L.mc_program_free.argtypes = [C.c_void_p]
@@ -929,6 +938,12 @@ class Program:
         self.action_constraints = []
         while lib().mc_program_action_constraint(h, len(self.action_constraints)):
             self.action_constraints.append(lib().mc_program_action_constraint(h, len(self.action_constraints)).decode())
+        # the safety parts of the cfg's PROPERTYs that the search checks: `[][A]_v` ("step"), `[]P` ("always"), initial predicates ("init");
+        # index: what mc_result.violated_invariant is when the part is violated
+        self.action_properties = []
+        ap = ActionProperty()
+        while lib().mc_program_action_property(h, len(self.action_properties), C.byref(ap)) == 0:
+            self.action_properties.append(Result(origin=ap.origin.decode(), kind=APROP_KINDS[int(ap.kind)], index=int(ap.index), text=ap.text.decode()))
 
     def translated(self, label_fair=False):
         """the module text after translation; label_fair: Spec's fairness conjuncts label by label, as pcal2tla writes `+` / `-` labels"""
@@ -984,6 +999,13 @@ class ResolvedSpec:
         self.properties = []   # the cfg's PROPERTY names of a compiled PlusCal program: a sharded search names them as NOT checked
         while prog and lib().mc_program_property(prog, len(self.properties)):
             self.properties.append(lib().mc_program_property(prog, len(self.properties)).decode())
+        # ... but those that are safety alone (`[]P`, `[][A]_v`): every rank's search checks them itself
+        lp = LiveProperty()
+        k = 0
+        while prog and lib().mc_program_live_property(prog, k, C.byref(lp)) == 0:
+            if lp.refused and lp.reason.decode().startswith("it has no liveness part") and lp.origin.decode() in self.properties:
+                self.properties.remove(lp.origin.decode())
+            k += 1
 
     def close(self):
         if self._prog:

@@ -2258,7 +2258,7 @@ int mc_make_engine_6(const mc_spec_desc *d, const mc_config *c, mc::EngineBase *
     if (mc::vm_make_params(d->params, d->nparams, p)) return MC_EBADCFG;
     if (hipSetDevice(c->device) != hipSuccess) { mc::set_error("hipSetDevice failed"); return MC_EHIP; }
     mc::DevBuf<int32_t> d_code;
-    const size_t image_words = (size_t)p.code_len + (size_t)mc::VMX_SIZE;   // (with the table behind the image: spec_vm_cfg.h VmExt)
+    const size_t image_words = (size_t)p.code_len + (size_t)mc::vm_ext_words(p);   // (with the table behind the image and the entries behind that: spec_vm_cfg.h VmExt)
     if (d_code.alloc(image_words) != hipSuccess ||
         hipMemcpy(d_code, p.code, image_words * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
         mc::set_error("cannot upload the PlusCal program image");
@@ -2272,7 +2272,7 @@ int mc_make_engine_6(const mc_spec_desc *d, const mc_config *c, mc::EngineBase *
     for (int i = 0; i < 8; i++) mixin((uint32_t)p.inv_entry[i]);
     mixin(p.num_init);
     if (p.code[p.code_len + mc::VMX_NACON] || p.code[p.code_len + mc::VMX_NVIEW])   // the cfg's ACTION_CONSTRAINTs / VIEW (their code is part of the image, their
-        for (int i = 0; i < mc::VMX_SIZE; i++) mixin((uint32_t)p.code[p.code_len + i]);   // table behind it): a checkpoint under one is refused under another
+        for (int i = 0; i < mc::vm_ext_words(p); i++) mixin((uint32_t)p.code[p.code_len + i]);   // table behind it, a PROPERTY's safety entries): a checkpoint under one is refused under another
     p.code = d_code;  // host-side helpers (format, action_of) use p.host only
     const int rc = p.nv <= 16 ? mc::make_engine<mc::SpecVmCfg16>(p, d, c, out)
                  : p.nv <= 32 ? mc::make_engine<mc::SpecVmCfg32>(p, d, c, out)
@@ -2297,7 +2297,7 @@ int mc_make_engine_gen(const mc_spec_desc *d, const mc_config *c, mc::EngineBase
     for (int i = 0; i < 8; i++) mixin((uint32_t)p.inv_entry[i]);
     mixin(p.num_init);
     if (p.code[p.code_len + mc::VMX_NACON] || p.code[p.code_len + mc::VMX_NVIEW])   // the cfg's ACTION_CONSTRAINTs / VIEW (their code is part of the image, their
-        for (int i = 0; i < mc::VMX_SIZE; i++) mixin((uint32_t)p.code[p.code_len + i]);   // table behind it): a checkpoint under one is refused under another
+        for (int i = 0; i < mc::vm_ext_words(p); i++) mixin((uint32_t)p.code[p.code_len + i]);   // table behind it, a PROPERTY's safety entries): a checkpoint under one is refused under another
     p.code = nullptr;   // the device never reads the image: the program IS the kernels
     const int rc = mc::make_engine<mc::SpecGen>(p, d, c, out);
     if (mc::SpecGen::PACKED_ROWS) { mixin(0x7061636bu); mixin((uint32_t)mc::SpecGen::MAX_WORDS); }   // a checkpoint of packed rows is not the interpreter's

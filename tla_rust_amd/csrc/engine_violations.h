@@ -77,7 +77,7 @@ k_viol_stored(typename S::Params prm, const uint64_t *__restrict__ arena, const 
         if constexpr (!ChecksOnExpand<S>::value) p = parent[idx];
         const bool has_parent = p != 0xffffffffu;
         if (!has_parent || p < idx)   // (a parent lies below its successors in the arena; a record that cannot be one is counted nowhere)
-            bin = viol_stored_bin<S>(prm, self, has_parent,
+            bin = viol_stored_bin<S>(prm, self, has_parent, ViolModel<S>::ninv(prm),
                 [&]() -> unsigned {
                     if constexpr (ChecksOnExpand<S>::value) {
                         typename S::Local loc;
@@ -124,7 +124,7 @@ k_viol_frontier(typename S::Params prm, const uint64_t *__restrict__ arena, uint
             uint64_t f = 0;
             const unsigned st = S::eval(prm, loc, s, slot, f);
             if (st & ST_ENABLED) ++gen;
-            r = viol_pair<S>(st);
+            r = viol_pair<S>(st, ViolModel<S>::ninv(prm));   // (an index behind the model's invariants: a property of the step, fatal)
         }
         const unsigned long long key = viol_key(idx, (unsigned)slot, r.kind, r.inv);
         const int column = viol_pair_column(r);

@@ -92,6 +92,16 @@ const char *mc_program_view(const mc_program *p) { return p && !p->prog.view_tex
 const char *mc_program_action_constraint(const mc_program *p, int index) {
     return p && index >= 0 && (size_t)index < p->prog.action_constraints.size() ? p->prog.action_constraints[(size_t)index].c_str() : nullptr;
 }
+int mc_program_action_property(const mc_program *p, int index, mc_action_property *out) {
+    if (!p || !out || index < 0 || (size_t)index >= p->prog.safe_props.size()) return MC_EBADCFG;
+    const auto &sp = p->prog.safe_props[(size_t)index];
+    memset(out, 0, sizeof *out);
+    snprintf(out->origin, sizeof out->origin, "%s", sp.origin.c_str());
+    snprintf(out->text, sizeof out->text, "%s", sp.text.c_str());
+    out->kind = sp.kind;
+    out->index = sp.index;
+    return MC_OK;
+}
 extern "C" long pcal_codegen_text(const pcal::Program *p, char *buf, size_t cap);   // pcal_codegen.cpp
 
 namespace {
@@ -723,7 +733,9 @@ int mc_program_spec(const mc_program *p, mc_spec_desc *out) {
 const char *mc_program_translated(const mc_program *p) { return p ? p->prog.translated.c_str() : ""; }
 long mc_program_codegen(const mc_program *p, char *buf, size_t cap) { return p ? pcal_codegen_text(&p->prog, buf, cap) : (long)MC_EBADCFG; }
 const char *mc_program_invariant(const mc_program *p, int index) {
-    return p && index >= 0 && (size_t)index < p->prog.invariants.size() ? p->prog.invariants[(size_t)index].c_str() : "?";
+    if (p && index >= 0 && (size_t)index < p->prog.invariants.size()) return p->prog.invariants[(size_t)index].c_str();
+    for (size_t k = 0; p && k < p->prog.safe_props.size(); k++) if (p->prog.safe_props[k].index == index) return p->prog.safe_props[k].origin.c_str();
+    return "?";
 }
 int mc_program_assert_pos(const mc_program *p, int index, int *line, int *col) {
     if (!p || index < 0 || (size_t)index >= p->prog.asserts.size()) return MC_EBADCFG;
@@ -734,11 +746,20 @@ int mc_program_assert_pos(const mc_program *p, int index, int *line, int *col) {
 void mc_program_free(mc_program *p) { delete p; }
 
 static const char *invariant_name(const mc_spec_desc *d, int idx);
+// the invariant entries of a compiled program: the cfg's INVARIANTs and the `[]P` conjuncts of its PROPERTYs; an index behind them is a
+// PROPERTY's `[][A]_v` or initial predicate
+static int program_ninv(const mc_program *p) {
+    int n = (int)p->prog.invariants.size();
+    for (const auto &sp : p->prog.safe_props) n += sp.kind == MC_APROP_ALWAYS;
+    return n;
+}
 const char *mc_invariant_name(const mc_spec_desc *spec, int index) { return spec ? invariant_name(spec, index) : "?"; }
 static const char *invariant_name(const mc_spec_desc *d, int idx) {
     if (d->spec_id == MC_SPEC_PCAL) {
         const pcal::Program *P = (const pcal::Program *)(intptr_t)d->params[0];
-        return idx >= 0 && (size_t)idx < P->invariants.size() ? P->invariants[(size_t)idx].c_str() : "?";
+        if (idx >= 0 && (size_t)idx < P->invariants.size()) return P->invariants[(size_t)idx].c_str();
+        for (const auto &sp : P->safe_props) if (sp.index == idx) return sp.origin.c_str();   // a PROPERTY's safety part: the PROPERTY's name
+        return "?";
     }
     if (d->spec_id == MC_SPEC_PCAL_INTRO) return "MoneyInvariant";
     if (d->spec_id == MC_SPEC_RAFT) return idx == 1 ? "CommittedLogStable" : "NoTwoLeaders";
@@ -1357,6 +1378,8 @@ static void put_error_report(Out &o, mc_engine *e, const Resolved &R, int32_t ve
     else if (verdict == MC_V_ASSERT) { /* compiled program: the message names the failing assert, found below */ }
     else if (verdict == MC_V_INVARIANT && d.spec_id == MC_SPEC_PAXOS && violated_invariant == (d.params[0] == 1 ? 1 : 4))
         o.put("Error: Action property %s is violated.\n", invariant_name(&d, violated_invariant));  // the step breaks [Next]_v of the PROPERTY
+    else if (verdict == MC_V_INVARIANT && generic && violated_invariant >= program_ninv(prog))   // a PROPERTY's `[][A]_v` or initial predicate
+        o.put("Error: Action property %s is violated.\n", invariant_name(&d, violated_invariant));   // (the host evaluator's wording for both)
     else if (verdict == MC_V_INVARIANT) o.put("Error: Invariant %s is violated.\n", invariant_name(&d, violated_invariant));
     else if (verdict == MC_V_DEADLOCK) o.put("Error: Deadlock reached.\n");
     else o.put("Error: evaluation error (a function was applied outside its domain).\n");
@@ -1688,6 +1711,8 @@ static int check_files_impl(const char *tla_path, const char *cfg_path, const mc
         for (const auto &name : R.properties) {
             const bool term = name == "Termination";
             if (!term && !seen_names.insert(name).second) continue;
+            // a PROPERTY without a liveness part, every conjunct of it checked by the search itself: nothing to name
+            if (!term && std::find(prog->prog.safety_only.begin(), prog->prog.safety_only.end(), name) != prog->prog.safety_only.end()) continue;
             // the checks a name other than Termination became, or the front end's reason for refusing it
             std::vector<mc_live_property> checks;
             std::string why;

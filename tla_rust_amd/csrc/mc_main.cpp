@@ -264,7 +264,15 @@ static int run_rank(const char *tla, const char *cfgp, mc_config cfg, int rank, 
         const unsigned long long n0 = res.levels ? (unsigned long long)res.level_distinct[0] : 0ull;
         printf("Finished computing initial states: %llu distinct state%s generated.\n", n0, n0 == 1 ? "" : "s");
         // a sharded search keeps no state graph in one place: the cfg's temporal properties are named, never passed over
+        // (a PROPERTY that is safety alone — `[]P`, `[][A]_v` — is checked by every rank's `step`, DESIGN section 22: nothing of it is left to name)
+        auto safety_alone = [&](const char *name) {
+            mc_live_property lp;
+            for (int j = 0; mc_program_live_property(prog, j, &lp) == MC_OK; j++)
+                if (!strcmp(lp.origin, name)) return lp.refused && !strncmp(lp.reason, "it has no liveness part", 23);
+            return false;
+        };
         for (int k = 0; prog && mc_program_property(prog, k); k++) {
+            if (safety_alone(mc_program_property(prog, k))) continue;
             res.unchecked_properties++;
             printf("Warning: temporal property %s NOT checked: the search is sharded over %d engines (-gpus); liveness needs the state graph of one engine.\n",
                    mc_program_property(prog, k), world);

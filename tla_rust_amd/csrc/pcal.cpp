@@ -1119,6 +1119,7 @@ struct TemporalParser {
             EP dom = state(b + 3, colon);
             if (!dom) { out.refusal = "a quantifier whose domain is outside the expression subset"; return; }
             q.push_back({t[b + 1].s, dom});
+            dom_tokens[dom.get()] = {b + 3, colon};
             return formula(colon + 1, e, q);
         }
         if (sym(b, "/\\")) {   // a bulleted conjunction: the items are what stands between the bullets of the first one's column
@@ -1160,13 +1161,129 @@ struct TemporalParser {
             for (size_t at : ands) { formula(from, at, q); from = at + 1; }
             return;
         }
+        for (size_t i = b; i + 1 < e; i++)   // <<A>>_v: an action formula that no safety check decides
+            if (sym(i, ">>") && t[i + 1].t == Tok::IDENT && t[i + 1].s[0] == '_' && t[i + 1].line == t[i].line && t[i + 1].col == t[i].col + 2) {
+                if (out.safety_error.empty()) out.safety_error = "`<<A>>_v` (`" + text(b, e) + "`) is not supported: only `[][A]_v`";
+                return;
+            }
         if (box(b, e) && dia(b + 2, e)) return item(1, 0, 0, b + 4, e, q);
         if (dia(b, e) && box(b + 2, e)) return item(3, b + 4, e, 0, 0, q);
         if (dia(b, e)) return item(2, 0, 0, b + 2, e, q);
-        if (box(b, e)) return refuse("`[]` without `<>` is a safety property (`[]A` is an INVARIANT, `[][A]_v` an action formula)");
+        if (box(b, e) && sym(b + 2, "[")) return step_item(b, e, q);
+        if (box(b, e)) {   // []P: an invariance property
+            state(b + 2, e);
+            if (!out.refusal.empty()) return;
+            if (!primary(b + 2, e))
+                return refuse("the operand of `<>` / `[]` must be parenthesised (a temporal prefix operator binds tighter than every infix operator: `<>A \\/ B` is `(<>A) \\/ B`)");
+            return safety(1, std::vector<Tok>(t.begin() + (long)b + 2, t.begin() + (long)e), q, text(b, e));
+        }
+        // what is checked only beside a `[][A]_v` (the shape Init /\ [][Next]_v /\ fairness): decided when the whole body has been read
         for (size_t i = b; i < e; i++)
-            if (t[i].t == Tok::IDENT && (t[i].s.rfind("WF_", 0) == 0 || t[i].s.rfind("SF_", 0) == 0)) return refuse("a WF_ / SF_ fairness formula inside the property");
-        refuse("not one of <>A, []<>A, <>[]A, A ~> B (under `\\A` over constant sets, and conjunctions of these)");
+            if (t[i].t == Tok::IDENT && (t[i].s.rfind("WF_", 0) == 0 || t[i].s.rfind("SF_", 0) == 0))
+                return pend(-1, b, e, q, "a WF_ / SF_ fairness formula inside the property");
+        for (size_t i = b; i < e; i++)
+            if (dia(i, e) || box(i, e) || leads(i, e) || sym(i, "'"))
+                return refuse("not one of <>A, []<>A, <>[]A, A ~> B (under `\\A` over constant sets, and conjunctions of these)");
+        pend(2, b, e, q, "not one of <>A, []<>A, <>[]A, A ~> B (under `\\A` over constant sets, and conjunctions of these)");
+    }
+
+    // ---- the safety conjuncts
+    std::map<const Expr *, std::pair<size_t, size_t>> dom_tokens;   // the tokens of a quantifier's domain
+    struct Pending { int kind; size_t b, e; Quants q; std::string why; };
+    std::vector<Pending> pending;
+    static Tok tok(Tok::T ty, const std::string &s, const Tok &at) { Tok k; k.t = ty; k.s = s; k.line = at.line; k.col = at.col; return k; }
+    // the expression `\A x \in S : ... : ( body )` of the quantifiers around a conjunct
+    std::vector<Tok> quantified(const std::vector<Tok> &body, const Quants &q) const {
+        std::vector<Tok> r;
+        const Tok &at = body.front();
+        for (const auto &x : q) {
+            r.push_back(tok(Tok::SYM, "\\A", at));
+            r.push_back(tok(Tok::IDENT, x.first, at));
+            r.push_back(tok(Tok::SYM, "\\in", at));
+            const auto rg = dom_tokens.at(x.second.get());
+            r.insert(r.end(), t.begin() + (long)rg.first, t.begin() + (long)rg.second);
+            r.push_back(tok(Tok::SYM, ":", at));
+        }
+        r.push_back(tok(Tok::SYM, "(", at));
+        r.insert(r.end(), body.begin(), body.end());
+        r.push_back(tok(Tok::SYM, ")", body.back()));
+        return r;
+    }
+    static EP parse_tokens(std::vector<Tok> body) {
+        Tok end;
+        end.line = body.back().line;
+        end.col = body.back().col + 1;
+        body.push_back(end);
+        Parser bp(body);
+        try {
+            EP x = bp.expr(0);
+            if (bp.cur().t == Tok::END) return x;
+        } catch (const ParseError &) {
+        }
+        return nullptr;
+    }
+    void safety(int kind, const std::vector<Tok> &body, const Quants &q, const std::string &what, const std::vector<Tok> &unchanged = {}) {
+        std::vector<Tok> all = quantified(body, q);
+        if (!unchanged.empty()) {   // ( \A .. : ( A ) ) \/ UNCHANGED v
+            all.insert(all.begin(), tok(Tok::SYM, "(", body.front()));
+            all.push_back(tok(Tok::SYM, ")", body.back()));
+            all.push_back(tok(Tok::SYM, "\\/", body.back()));
+            all.push_back(tok(Tok::IDENT, "UNCHANGED", body.back()));
+            all.insert(all.end(), unchanged.begin(), unchanged.end());
+        }
+        SafetyItem it;
+        it.kind = kind;
+        it.text = what;
+        it.body = parse_tokens(all);
+        if (!it.body) {
+            if (out.safety_error.empty()) out.safety_error = "`" + what + "` is outside the expression subset";
+            return;
+        }
+        out.safety.push_back(it);
+    }
+    // [][A]_v at [b, e)
+    void step_item(size_t b, size_t e, const Quants &q) {
+        const std::string what = text(b, e);
+        auto bad = [&](const std::string &why) { if (out.safety_error.empty()) out.safety_error = "`" + what + "`: " + why; };
+        int d = 0;
+        size_t c = b + 2;
+        for (; c < e; c++) { d += nest(t[c]); if (d == 0) break; }
+        if (c >= e || c == b + 3) return bad("no action between `[` and `]`");
+        for (size_t i = b + 3; i < c; i++) {
+            if (dia(i, c) || box(i, c) || leads(i, c)) return bad("a temporal operator inside the action");
+            if (t[i].t == Tok::IDENT && (t[i].s.rfind("WF_", 0) == 0 || t[i].s.rfind("SF_", 0) == 0)) return bad("a WF_ / SF_ fairness formula inside the action");
+        }
+        // the subscript: `_x` is one identifier token, `_<<x, y>>` the identifier `_` and a tuple
+        std::vector<Tok> sub;
+        const bool adjacent = c + 1 < e && t[c + 1].t == Tok::IDENT && t[c + 1].s[0] == '_' && t[c + 1].line == t[c].line && t[c + 1].col == t[c].col + 1;
+        if (!adjacent) return bad("the subscript is no variable or tuple of variables (`[][A]_v` needs `_v` or `_<<v, w>>` right behind the `]`)");
+        if (t[c + 1].s.size() > 1) {
+            if (c + 2 != e) return bad("the subscript is no variable or tuple of variables");
+            sub.push_back(tok(Tok::IDENT, t[c + 1].s.substr(1), t[c + 1]));
+        } else {
+            bool ok = c + 4 < e && sym(c + 2, "<<") && sym(e - 1, ">>");
+            for (size_t i = c + 3; ok && i + 1 < e; i++) ok = (i - (c + 3)) % 2 == 0 ? t[i].t == Tok::IDENT : sym(i, ",");
+            ok = ok && (e - 1 - (c + 3)) % 2 == 1;
+            if (!ok) return bad("the subscript is no variable or tuple of variables");
+            sub.assign(t.begin() + (long)c + 2, t.begin() + (long)e);
+        }
+        safety(0, std::vector<Tok>(t.begin() + (long)b + 3, t.begin() + (long)c), q, what, sub);
+    }
+    void pend(int kind, size_t b, size_t e, const Quants &q, const std::string &why) { pending.push_back({kind, b, e, q, why}); }
+    // after formula(): an initial predicate or a fairness conjunct counts beside a `[][A]_v` only; anywhere else it is what it was, a refusal
+    void finish() {
+        if (!out.refusal.empty() || pending.empty()) return;
+        bool step = false;
+        for (const auto &s : out.safety) step |= s.kind == 0;
+        if (!step && out.safety_error.empty()) return refuse(pending[0].why);
+        for (const auto &p : pending) {
+            if (p.kind == 2) {
+                if (!state(p.b, p.e)) return;
+                safety(2, std::vector<Tok>(t.begin() + (long)p.b, t.begin() + (long)p.e), p.q, text(p.b, p.e));
+            } else {
+                out.named.push_back({text(p.b, p.e), p.why});
+            }
+        }
     }
 };
 
@@ -2642,8 +2759,20 @@ std::string parse_module(const std::string &text, Module &m) {
                     td.name = def.name;
                     td.line = def.line;
                     body.pop_back();
-                    TemporalParser{body, td}.formula(0, body.size(), {});
-                    if (!td.refusal.empty()) td.items.clear();
+                    TemporalParser tp{body, td};
+                    tp.formula(0, body.size(), {});
+                    tp.finish();
+                    if (!td.refusal.empty()) { td.items.clear(); td.safety.clear(); td.named.clear(); }
+                    if (!td.named.empty()) td.items.clear();
+                    for (auto &it : td.safety) {   // the checked expression as a definition of the module (no module text can write the name)
+                        it.def = "\001safe" + std::to_string(m.temporal.size()) + "_" + std::to_string(&it - td.safety.data());
+                        Definition sd;
+                        sd.name = it.def;
+                        sd.body = it.body;
+                        sd.line = def.line;
+                        it.body = nullptr;
+                        m.defs.push_back(sd);
+                    }
                     m.temporal.push_back(td);
                 }
                 d.i = j;

@@ -109,11 +109,23 @@ struct LiveItem {
     EP a, b;                                            // the state predicates (null where the shape has none)
     std::string a_text, b_text;                         // their tokens, joined by one blank: what predicates are deduplicated by
 };
+// A SAFETY conjunct of such a definition: `[][A]_v`, `[]P` or an initial predicate.  What is checked is one Boolean
+// expression, kept as the body of a definition of the module under a name no module text can write (`def`): `A \/ UNCHANGED v` with its
+// bounded `\A`s inside for a step, P, or I.  Being a definition, it goes through the record flattener with every other one.
+struct SafetyItem {
+    int kind = 0;                                       // 0 `[][A]_v` (a property of a step), 1 `[]P`, 2 an initial predicate (MC_APROP_* of tlamc.h)
+    std::string def, text;                              // the definition that holds the expression; the conjunct as written
+    EP body;                                            // (until parse_module has made the definition)
+};
 struct TemporalDef {
     std::string name;
     int line = 0;
     std::vector<LiveItem> items;
+    std::vector<SafetyItem> safety;
+    std::vector<std::pair<std::string, std::string>> named;   // conjuncts beside a `[][A]_v` that are neither (WF_ / SF_): (text, why); the liveness items are
+                                                              // then refused with them — they would be checked under another fairness than the property's
     std::string refusal;                                // "" = accepted; else why the body is none of the accepted shapes
+    std::string safety_error;                           // a `[][A]_v` / `<<A>>_v` whose form is refused (a compile error for the cfg that names it)
 };
 struct Macro {
     std::string name;
@@ -264,6 +276,15 @@ struct Program {
     struct ViewComp { int a = 0, n = 0; std::string text; };   // n > 0: the cells a .. a + n - 1 of a variable; n == 0: the code at a (one value)
     std::vector<ViewComp> view;
     std::string view_text;                         // the body of the definition the cfg's VIEW names ("<<c1, ..., ck>>"), or ""
+    // the safety parts of the cfg's PROPERTYs.  kind 1 (`[]P`) is one more invariant entry of the image's header, behind
+    // the cfg's INVARIANTs (`invariants` stays the cfg's names); kind 0 (`[][A]_v`) and kind 2 (an initial predicate) have their entries in the
+    // table behind the image (spec_vm_cfg.h).  index: the invariant index a violation reports (kind 1: its header entry; kind 0: ninv + k;
+    // kind 2: behind those).
+    struct SafeProp { std::string origin, text; int kind = 0, index = 0, entry = 0; };
+    std::vector<SafeProp> safe_props;
+    std::vector<std::string> safety_only;          // PROPERTY names without a liveness part whose every conjunct is checked
+    std::vector<std::pair<std::string, std::string>> named_conjuncts;   // (PROPERTY, "conjunct `text`: why") beside checked safety parts
+    std::vector<int> aprop_entry, initp_entry;     // the entries of kinds 0 and 2, in the order of safe_props
 };
 
 // Returns "" or an error message.

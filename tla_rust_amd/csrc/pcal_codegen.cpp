@@ -718,6 +718,22 @@ std::string codegen(const Program &P, bool pack) {
         for (int k = 0; k < nacon; ++k) o << "        case " << k << ": return acon" << k << "(cur, succ, result);\n";
         o << "        default: return R_ERROR;\n        }\n    }\n";
     }
+    // ---- the safety parts of the cfg's PROPERTYs, again only for a program that has them: the action properties
+    // `[][A]_v` (an action constraint's kind of code) and the initial predicates (an invariant's)
+    if (!P.aprop_entry.empty() || !P.initp_entry.empty()) {
+        const int naprop = (int)P.aprop_entry.size(), ninitp = (int)P.initp_entry.size();
+        for (int k = 0; k < naprop; ++k)
+            o << "    MC_HD static int aprop" << k << "(const Cells &v, const Cells &old, int32_t &result) {\n        constexpr int32_t SELF_ = 0; constexpr int INST = 0; int aux = 0; uint64_t ch = 0;\n        (void)SELF_; (void)INST;\n"
+              << g.body(P.aprop_entry[(size_t)k]) << "    }\n";
+        for (int k = 0; k < ninitp; ++k)
+            o << "    MC_HD static int initp" << k << "(Cells &v, int32_t &result) {\n        constexpr int32_t SELF_ = 0; constexpr int INST = 0; const Cells &old = v; int aux = 0; uint64_t ch = 0;\n        (void)SELF_; (void)INST;\n"
+              << g.body(P.initp_entry[(size_t)k]) << "    }\n";
+        o << "    static constexpr int NAPROP = " << naprop << ", NINITP = " << ninitp << ";\n    // action property k on the step cur -> succ\n    MC_HD static int run_aprop(int k, const Cells &cur, const Cells &succ, int32_t &result) {\n        switch (k) {\n";
+        for (int k = 0; k < naprop; ++k) o << "        case " << k << ": return aprop" << k << "(cur, succ, result);\n";
+        o << "        default: return R_ERROR;\n        }\n    }\n    MC_HD static int run_initp(int k, Cells &v, int32_t &result) {\n        switch (k) {\n";
+        for (int k = 0; k < ninitp; ++k) o << "        case " << k << ": return initp" << k << "(v, result);\n";
+        o << "        default: return R_ERROR;\n        }\n    }\n";
+    }
     if (!P.view.empty()) {
         int nvals = 0, ne = 0;
         std::ostringstream fill;

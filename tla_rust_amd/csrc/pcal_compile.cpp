@@ -723,6 +723,7 @@ struct Compiler {
     // state being expanded and `old` = the successor (spec_vm_cfg.h), and its body is emitted at "old" depth 0 — definitions are inlined
     // WITHOUT the VM_OLD_ON they get elsewhere — so exactly the primed accesses read the successor
     bool in_acon = false;
+    bool in_aprop = false;   // ... of an action property `[][A]_v`: an action constraint's code, with a wider UNCHANGED
     static std::string expr_text(const EP &e) {
         if (!e) return "?";
         switch (e->k) {
@@ -801,7 +802,28 @@ struct Compiler {
     void unchanged(const EP &e) {
         if (!in_acon) cfail("UNCHANGED outside an ACTION_CONSTRAINT", e->pos);
         emit(mc::VM_PUSH, 1);
-        for (const auto &x : e->a) {
+        std::vector<EP> names = e->a;
+        if (in_aprop) {   // the subscript of `[][A]_v`: a variable, a tuple of them, `vars`, or a definition that is one of these (`hv == <<x, y>>`)
+            for (int round = 0; round < 8; round++) {
+                std::vector<EP> next;
+                bool changed = false;
+                for (const auto &x : names) {
+                    const Definition *def = nullptr;
+                    if (x->k == Expr::ID && !is_variable(x)) for (const auto &d : m.defs) if (d.name == x->s && d.params.empty()) def = &d;
+                    if (x->k == Expr::TUPLE) { next.insert(next.end(), x->a.begin(), x->a.end()); changed = true; }
+                    else if (def) { next.push_back(def->body); changed = true; }
+                    else if (x->k == Expr::ID && x->s == "vars" && !is_variable(x)) {
+                        for (const auto &v : P.vars) { auto id = std::make_shared<Expr>(); id->k = Expr::ID; id->s = v.name; id->pos = x->pos; next.push_back(id); }
+                        changed = true;
+                    } else next.push_back(x);
+                }
+                names = next;
+                if (!changed) break;
+            }
+            for (const auto &x : names)
+                if (!is_variable(x)) cfail("the subscript of `[][A]_v` is no variable or tuple of variables: `" + expr_text(x) + "`", e->pos);
+        }
+        for (const auto &x : names) {
             if (!is_variable(x)) cfail("UNCHANGED `" + expr_text(x) + "`: only variable names (and tuples of them) are supported", e->pos);
             const size_t k = (size_t)var_index[x->s];
             for (int i = 0; i < cells_of(k); i++) {
@@ -1854,6 +1876,10 @@ struct Compiler {
                 refused.refusal = is_def ? "it is a state-level formula, not one of <>A, []<>A, <>[]A, A ~> B" : "it is not a definition of the module this front-end can read";
             } else if (!td->refusal.empty()) {
                 refused.refusal = td->refusal;
+            } else if (!td->named.empty()) {       // beside checked safety conjuncts: the conjunct is named, not only the property
+                refused.refusal = "its conjunct `" + td->named[0].first + "`: " + td->named[0].second + " (its safety conjuncts are checked)";
+            } else if (td->items.empty() && !td->safety.empty()) {
+                refused.refusal = "it has no liveness part: `[]` without `<>` is a safety property, and is checked as one (`[]A` as an invariant, `[][A]_v` on every step)";
             }
             if (!refused.refusal.empty()) { P.live_props.push_back(refused); continue; }
             std::vector<Program::LiveProp> got;
@@ -2194,8 +2220,19 @@ struct Compiler {
         if (max_depth > mc::SpecVm::STACK) cfail("an expression is too deeply nested for the interpreter's stack (" + std::to_string(max_depth) + " > " + std::to_string(mc::SpecVm::STACK) + ")");
         // ---- invariants
         if (cfg.invariants.size() + cfg.constraints.size() > 8) cfail("at most 8 invariants + constraints are supported");
+        safety_collect();
         std::vector<int> inv_entry;
-        for (int pass = 0; pass < 2; pass++)  // INVARIANTs, then CONSTRAINTs: both are state predicates named by the cfg
+        for (int pass = 0; pass < 2; pass++) {  // INVARIANTs, then CONSTRAINTs: both are state predicates named by the cfg
+            if (pass == 1)   // between them, the `[]P` conjuncts of the cfg's PROPERTYs: further invariants, reported under the PROPERTY's name
+                for (auto &sp : P.safe_props)
+                    if (sp.kind == 1) {
+                        sp.index = (int)inv_entry.size();
+                        sp.entry = (int)c.size();
+                        inv_entry.push_back(sp.entry);
+                        next_temp = 0;
+                        ex(safety_def(sp)->body);
+                        emit(mc::VM_HALT);
+                    }
             for (const auto &name : pass == 0 ? cfg.invariants : cfg.constraints) {
                 const Definition *def = nullptr;
                 for (const auto &d : m.defs) if (d.name == name && d.params.empty()) def = &d;
@@ -2206,11 +2243,15 @@ struct Compiler {
                 emit(mc::VM_HALT);
                 if (pass == 0) P.invariants.push_back(name);
             }
+        }
+        const int n_always = (int)inv_entry.size() - (int)cfg.invariants.size() - (int)cfg.constraints.size();
         // ---- the predicates of the cfg's other temporal properties: code after the invariants', entries in a table of the program's own
         live_properties();
         // ---- the cfg's ACTION_CONSTRAINTs and VIEW
         cur_nv = nv;
         cfg_more();
+        // ---- the action properties and initial predicates of the cfg's PROPERTYs
+        safety_more((int)cfg.invariants.size() + n_always);
         if (!P.view.empty()) P.live_refusal_units = "the cfg has a VIEW (the graph is one of representative states: fairness over it is not the spec's)";
         if (!P.view.empty()) P.live_refusal = P.live_refusal_strong = "the cfg has a VIEW (the graph is one of representative states: fairness over it is not the spec's)";
         // ---- header
@@ -2221,7 +2262,7 @@ struct Compiler {
         c[mc::VMH_PC_BASE] = P.pc_base;
         c[mc::VMH_DONE] = done;
         c[mc::VMH_INIT_ENTRY] = init_entry;
-        c[mc::VMH_NINV] = (int)cfg.invariants.size();
+        c[mc::VMH_NINV] = (int)cfg.invariants.size() + n_always;
         c[mc::VMH_NCON] = (int)cfg.constraints.size();
         for (size_t k = 0; k < inv_entry.size(); k++) c[(size_t)mc::VMH_INV0 + k] = inv_entry[k];
         c[mc::VMH_LABEL_TAB] = label_tab;
@@ -2237,6 +2278,100 @@ struct Compiler {
         c[x + mc::VMX_NVIEW] = (int)P.view.size();
         for (size_t k = 0; k < P.acon_entry.size(); k++) c[x + mc::VMX_ACON0 + k] = P.acon_entry[k];
         for (size_t k = 0; k < P.view.size(); k++) { c[x + mc::VMX_VIEW_A0 + k] = P.view[k].a; c[x + mc::VMX_VIEW_N0 + k] = P.view[k].n; }
+        // ... and, only for a cfg whose PROPERTYs have them, the entries of the action properties and initial predicates behind that table:
+        // their counts share the word of the action constraints' (spec_vm_cfg.h vm_naprop / vm_ninitp)
+        c[x + mc::VMX_NACON] |= (int)P.aprop_entry.size() << 8 | (int)P.initp_entry.size() << 16;
+        c.insert(c.end(), P.aprop_entry.begin(), P.aprop_entry.end());
+        c.insert(c.end(), P.initp_entry.begin(), P.initp_entry.end());
+    }
+
+    // ---- the safety conjuncts of the cfg's PROPERTYs
+    const Definition *safety_def(const Program::SafeProp &sp) {
+        for (const auto &d : m.defs) if (d.name == safe_def_of[&sp - P.safe_props.data()]) return &d;
+        cfail("PROPERTY " + sp.origin + ": `" + sp.text + "` is outside the expression subset" + why_dropped(safe_def_of[&sp - P.safe_props.data()]));
+    }
+    std::vector<std::string> safe_def_of;   // per entry of P.safe_props: the definition that holds its expression
+    void safety_collect() {
+        std::set<std::string> seen;
+        for (const auto &name : cfg.properties) {
+            if (!seen.insert(name).second) continue;
+            const TemporalDef *td = nullptr;
+            for (const auto &d : m.temporal) if (d.name == name) td = &d;
+            if (!td) continue;
+            if (!td->safety_error.empty()) cfail("PROPERTY " + name + ": " + td->safety_error);
+            if (!td->refusal.empty() || td->safety.empty()) continue;
+            for (const auto &it : td->safety) {
+                Program::SafeProp sp;
+                sp.origin = name;
+                sp.text = it.text;
+                sp.kind = it.kind;
+                P.safe_props.push_back(sp);
+                safe_def_of.push_back(it.def);
+            }
+            if (td->items.empty() && td->named.empty()) P.safety_only.push_back(name);
+            for (const auto &nc : td->named) P.named_conjuncts.push_back({name, "its conjunct `" + nc.first + "`: " + nc.second});
+        }
+        int n[3] = {0, 0, 0};
+        for (const auto &sp : P.safe_props) n[sp.kind]++;
+        if (cfg.invariants.size() + cfg.constraints.size() + (size_t)n[1] > 8) cfail("at most 8 invariants + `[]P` properties + constraints are supported");
+        if (n[0] > mc::VM_MAX_APROP) cfail("at most " + std::to_string(mc::VM_MAX_APROP) + " action properties (`[][A]_v`) per cfg are supported");
+        if (n[2] > mc::VM_MAX_APROP) cfail("at most " + std::to_string(mc::VM_MAX_APROP) + " initial predicates of PROPERTYs per cfg are supported");
+        if (cfg.invariants.size() + (size_t)(n[0] + n[1] + n[2]) > 32)
+            cfail("invariants + `[]P` properties + action properties above 32: the key of a violation has 5 bits for the index");
+    }
+    // does the expression name an action of the translation (Next, a process, a label)?  Those are no definitions of the module text: an
+    // action property's A is written with primed variables
+    std::string names_action(const EP &e, int nest = 0) {
+        if (!e || nest > 16) return "";
+        if (e->k == Expr::ID || e->k == Expr::CALL) {
+            bool bound = false;
+            for (const auto &b : binds) bound |= b.name == e->s;
+            if (!bound && !var_index.count(e->s)) {
+                bool act = e->s == "Next" || e->s == "Spec" || e->s == "Init";
+                for (const auto &p : m.procs) act |= !p.name.empty() && p.name == e->s;
+                auto it = str_id.find(e->s);
+                act |= it != str_id.end() && it->second < P.nlabels && e->s != "Done";
+                bool is_def = false;
+                for (const auto &d : m.defs) if (d.name == e->s) { is_def = true; if (d.params.size() == e->a.size() || e->k == Expr::ID) { const std::string r = names_action(d.body, nest + 1); if (!r.empty()) return r; } }
+                if (act && !is_def) return e->s;
+            }
+        }
+        for (const auto &x : e->a) { const std::string r = names_action(x, nest); if (!r.empty()) return r; }
+        return "";
+    }
+    void safety_more(int ninv) {
+        int k0 = 0, k2 = 0, n0 = 0;
+        for (const auto &sp : P.safe_props) n0 += sp.kind == 0;
+        for (auto &sp : P.safe_props) {
+            if (sp.kind == 1) continue;
+            const Definition *def = safety_def(sp);
+            const std::string act = names_action(def->body);
+            if (!act.empty())
+                cfail("PROPERTY " + sp.origin + ": `" + sp.text + "` names `" + act + "`, an action of the translation (Next, a process, a label): an action property's A is written "
+                      "with primed variables");
+            if (!bool_typed(def->body)) cfail("PROPERTY " + sp.origin + ": `" + sp.text + "` is not a Boolean-valued formula");
+            sp.entry = (int)c.size();
+            next_temp = 0; depth = 0; fallthrough = true;
+            try {
+                if (sp.kind == 0) {
+                    sp.index = ninv + k0++;
+                    P.aprop_entry.push_back(sp.entry);
+                    in_acon = in_aprop = true;
+                    ex(def->body);   // (depth 0: unprimed variables are read from v = the state being expanded, as an action constraint's)
+                    in_acon = in_aprop = false;
+                } else {
+                    sp.index = ninv + n0 + k2++;
+                    P.initp_entry.push_back(sp.entry);
+                    ex(def->body);
+                }
+            } catch (CompileError &ce) {
+                in_acon = in_aprop = false;
+                ce.msg = "PROPERTY " + sp.origin + ": `" + sp.text + "`: " + ce.msg;
+                throw;
+            }
+            emit(mc::VM_HALT);
+        }
+        if (max_depth > mc::SpecVm::STACK) cfail("a PROPERTY's action formula is too deeply nested for the interpreter's stack");
     }
 };
 
@@ -2300,7 +2435,8 @@ int vm_make_params(const int64_t *p, unsigned np, VmParams &o) {
     o.self_tab = c[VMH_SELF_TAB];
     o.code_len = c[VMH_CODE_LEN];
     o.num_init = (uint64_t)(uint32_t)c[VMH_NUM_INIT_LO] | (uint64_t)(uint32_t)c[VMH_NUM_INIT_HI] << 32;
-    if (P->image.size() != (size_t)o.code_len + (size_t)VMX_SIZE) return -1;   // (the table of the cfg's ACTION_CONSTRAINTs / VIEW behind the image)
+    if (P->image.size() < (size_t)o.code_len + (size_t)VMX_SIZE) return -1;   // (the table of the cfg's ACTION_CONSTRAINTs / VIEW behind the image)
+    if (P->image.size() != (size_t)o.code_len + (size_t)vm_ext_words(o)) return -1;   // (... and the entries of its PROPERTYs' safety parts behind that)
     return 0;
 }
 

@@ -26,6 +26,9 @@
 // and, only for a program whose cfg has them:
 //   constexpr int NACON; static int run_acon(int k, const Cells &cur, const Cells &succ, int32_t &result)   // ACTION_CONSTRAINT k on cur -> succ
 //   constexpr int VIEW, VIEW_WORDS; static bool view_words(Cells &v, uint64_t *w)                   // the VIEW's values, two per word
+// and, only for a program whose cfg PROPERTYs have safety parts beyond `[]P`:
+//   constexpr int NAPROP, NINITP; static int run_aprop(int k, const Cells &cur, const Cells &succ, int32_t &result)   // `[][A]_v` number k on cur -> succ
+//   static int run_initp(int k, Cells &v, int32_t &result)                                          // initial predicate k
 #pragma once
 #include "spec_vm.h"
 #include <type_traits>
@@ -52,6 +55,8 @@ struct SpecGenPairs<G, true> {
 // does the generated program carry action constraints / a view?  (members that exist only then)
 template <class G, class = void> struct gen_has_acon : std::false_type {};
 template <class G> struct gen_has_acon<G, std::void_t<decltype(G::NACON)>> : std::true_type {};
+template <class G, class = void> struct gen_has_aprop : std::false_type {};   // ... safety parts of PROPERTYs?
+template <class G> struct gen_has_aprop<G, std::void_t<decltype(G::NAPROP)>> : std::true_type {};
 template <class G, class = void> struct gen_has_view : std::false_type {};
 template <class G> struct gen_has_view<G, std::void_t<decltype(G::VIEW_WORDS)>> : std::true_type {};
 
@@ -105,6 +110,30 @@ struct SpecGenT : SpecGenPairs<G, spec_gen_pairs_ok<G>()> {
                 const int r = G::run_acon(k, cur, v, res);
                 if (r != R_OK) return ST_SPECERR;
                 if (!res) return ST_OUT_OF_MODEL;
+            }
+        }
+        return 0;
+    }
+    // a PROPERTY's `[][A]_v` on the step cur -> v, and its initial predicates: SpecVmCfgT::aprop_status / initp_status
+    MC_HD static unsigned aprop_status(const Cells &cur, const Cells &v) {
+        if constexpr (gen_has_aprop<G>::value) {
+#pragma unroll
+            for (int k = 0; k < G::NAPROP; ++k) {
+                int32_t res = 0;
+                const int r = G::run_aprop(k, cur, v, res);
+                if (r != R_OK) return ST_SPECERR;
+                if (!res) return ST_INVARIANT | (unsigned)(G::NINV + k) << 8;
+            }
+        }
+        return 0;
+    }
+    MC_HD static unsigned initp_status(Cells &v) {
+        if constexpr (gen_has_aprop<G>::value) {
+#pragma unroll
+            for (int k = 0; k < G::NINITP; ++k) {
+                int32_t res = 0;
+                if (G::run_initp(k, v, res) != R_OK) return ST_SPECERR;
+                if (!res) return ST_INVARIANT | (unsigned)(G::NINV + G::NAPROP + k) << 8;
             }
         }
         return 0;
@@ -185,7 +214,9 @@ struct SpecGenT : SpecGenPairs<G, spec_gen_pairs_ok<G>()> {
             uint64_t vw[G::VIEW_WORDS];
             if (!G::view_words(v, vw)) return ST_ENABLED | ST_SPECERR;
         }
-        return ST_ENABLED | inv_status(v);
+        unsigned st = inv_status(v);
+        if constexpr (gen_has_aprop<G>::value) { if (!(st & (ST_INVARIANT | ST_SPECERR))) st |= initp_status(v); }
+        return ST_ENABLED | st;
     }
     template <class Ref>
     MC_HD static void load(const Params &, Ref s, Local &l) { unpack(s, l.v); }
@@ -230,7 +261,10 @@ struct SpecGenT : SpecGenPairs<G, spec_gen_pairs_ok<G>()> {
         if (r == R_ERROR) return ST_ENABLED | ST_SPECERR;
         if (r == R_OVERFLOW) return ST_ENABLED | ST_OVERFLOW;
         unsigned st = ST_ENABLED | inv_status(v);
+        unsigned ap = 0;   // (SpecVmCfgT::step: every generated successor, an INVARIANT first, a refused step too)
+        if constexpr (gen_has_aprop<G>::value) { if (!(st & (ST_SPECERR | ST_INVARIANT))) ap = aprop_status(cur, v); }
         if constexpr (gen_has_acon<G>::value) { if (!(st & (ST_SPECERR | ST_OUT_OF_MODEL))) st |= acon_status(cur, v); }
+        if constexpr (gen_has_aprop<G>::value) { if (!(st & ST_SPECERR)) st |= ap; }
         return st;
     }
     template <class Ref>

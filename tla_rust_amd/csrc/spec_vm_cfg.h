@@ -21,6 +21,15 @@ namespace mc {
 constexpr int VM_MAX_ACON = 4, VM_MAX_VIEW = 16;   // action constraints / view components per cfg (pcal_compile.cpp refuses more)
 enum VmExt : int32_t { VMX_NACON = 0, VMX_NVIEW, VMX_ACON0, VMX_VIEW_A0 = VMX_ACON0 + VM_MAX_ACON, VMX_VIEW_N0 = VMX_VIEW_A0 + VM_MAX_VIEW, VMX_SIZE = VMX_VIEW_N0 + VM_MAX_VIEW };
 MC_HD const int32_t *vm_ext(const VmParams &p) { return p.code + p.code_len; }
+// The safety parts of the cfg's PROPERTYs: the action properties `[][A]_v` (compiled as `A \/ UNCHANGED v`, an action
+// constraint's kind of code) and the initial predicates.  The table above has no spare word and may not grow (a program without them keeps
+// its image), so their counts share the word of the action constraints' count — bits 8..15 and 16..23 of it, zero without them — and their
+// entries FOLLOW the table: VMX_SIZE + k, the initial predicates' behind the action properties'.  (`[]P` is an invariant entry of the header.)
+constexpr int VM_MAX_APROP = 8;
+MC_HD int vm_nacon(const int32_t *x) { return x[VMX_NACON] & 0xff; }
+MC_HD int vm_naprop(const int32_t *x) { return x[VMX_NACON] >> 8 & 0xff; }
+MC_HD int vm_ninitp(const int32_t *x) { return x[VMX_NACON] >> 16 & 0xff; }
+MC_HD int vm_ext_words(const VmParams &p) { const int32_t *x = vm_ext(p); return VMX_SIZE + vm_naprop(x) + vm_ninitp(x); }
 
 template <int MAXV>
 struct SpecVmCfgT : SpecVmT<MAXV> {
@@ -62,12 +71,37 @@ struct SpecVmCfgT : SpecVmT<MAXV> {
     // (the code reads, never stores: `cur` is its v, the successor its `old` — see the head of this file)
     MC_HD static unsigned acon_status(const Params &p, const int32_t *cur, const int32_t *v) {
         const int32_t *x = vm_ext(p);
-        for (int k = 0; k < x[VMX_NACON]; ++k) {
+        for (int k = 0; k < vm_nacon(x); ++k) {
             int32_t res;
             int aux;
             const int r = Base::run(p, x[VMX_ACON0 + k], 0, 0, 0, const_cast<int32_t *>(cur), res, aux, v);
             if (r != R_OK) return ST_SPECERR;
             if (!res) return ST_OUT_OF_MODEL;
+        }
+        return 0;
+    }
+    // A PROPERTY's `[][A]_v` on the step cur -> v (TLC's doNextCheckImplied): property k broken = ST_INVARIANT with the index ninv + k, behind
+    // the invariants' (the `[]P` entries among them).  The code is an action constraint's: `cur` is its v, the successor its `old`.
+    MC_HD static unsigned aprop_status(const Params &p, const int32_t *cur, const int32_t *succ) {
+        const int32_t *x = vm_ext(p);
+        for (int k = 0; k < vm_naprop(x); ++k) {
+            int32_t res;
+            int aux;
+            const int r = Base::run(p, x[VMX_SIZE + k], 0, 0, 0, const_cast<int32_t *>(cur), res, aux, succ);
+            if (r != R_OK) return ST_SPECERR;
+            if (!res) return ST_INVARIANT | (unsigned)(p.ninv + k) << 8;
+        }
+        return 0;
+    }
+    // a PROPERTY's initial predicates on an initial state, indices behind the action properties'
+    MC_HD static unsigned initp_status(const Params &p, int32_t *v) {
+        const int32_t *x = vm_ext(p);
+        const int np = vm_naprop(x);
+        for (int k = 0; k < vm_ninitp(x); ++k) {
+            int32_t res;
+            int aux;
+            if (Base::run(p, x[VMX_SIZE + np + k], 0, 0, 0, v, res, aux) != R_OK) return ST_SPECERR;
+            if (!res) return ST_INVARIANT | (unsigned)(p.ninv + np + k) << 8;
         }
         return 0;
     }
@@ -83,15 +117,23 @@ struct SpecVmCfgT : SpecVmT<MAXV> {
         Base::unpack(p, s, v);
         uint64_t fp;
         if (vm_ext(p)[VMX_NVIEW] && !fp_view(p, v, fp)) return ST_ENABLED | ST_SPECERR;
-        return ST_ENABLED | Base::inv_status(p, v);
+        unsigned st = Base::inv_status(p, v);
+        if (vm_ninitp(vm_ext(p)) && !(st & (ST_INVARIANT | ST_SPECERR))) st |= initp_status(p, v);   // (an INVARIANT comes first: the word carries one index)
+        return ST_ENABLED | st;
     }
     // SpecVmT::step, then the action constraints: never on the terminating disjunct (it reaches no code), never on a successor that is
     // an error or outside a CONSTRAINT already
     MC_HD static unsigned step(const Params &p, const int32_t *cur, int slot, int32_t *v) {
         unsigned st = Base::step(p, cur, slot, v);
-        if (vm_ext(p)[VMX_NACON] && (st & ST_ENABLED) && slot != p.ninst * p.maxch &&
-            !(st & (ST_SPECERR | ST_OUT_OF_MODEL | ST_ASSERT | ST_OVERFLOW)))
+        const int32_t *x = vm_ext(p);
+        if (!x[VMX_NACON] || !(st & ST_ENABLED) || slot == p.ninst * p.maxch) return st;
+        // the action properties: every generated successor, outside a CONSTRAINT or not, stored before or not; an INVARIANT it breaks as
+        // well is what is reported
+        unsigned ap = 0;
+        if (vm_naprop(x) && !(st & (ST_SPECERR | ST_ASSERT | ST_OVERFLOW | ST_INVARIANT))) ap = aprop_status(p, cur, v);
+        if (vm_nacon(x) && !(st & (ST_SPECERR | ST_OUT_OF_MODEL | ST_ASSERT | ST_OVERFLOW)))
             st |= acon_status(p, cur, v);
+        if (!(st & ST_SPECERR)) st |= ap;   // (a refused step is checked too; an evaluation error of the constraint is the error)
         return st;
     }
     template <class Ref>

@@ -58,6 +58,16 @@ MC_HD ViolPair viol_pair(unsigned st) {
     if (ViolChecksStored<S>::value && !(st & ST_SELFLOOP)) { r.what = VIOL_P_FATAL; r.bin = VIOL_BIN_FATAL; }
     return r;
 }
+// ... with the model's number of invariant entries: an index BEHIND them is a property of the step (a compiled PlusCal program's
+// `[][A]_v`), as Paxos' is — fatal whether or not the successor is new, in the model, or the expanded state itself, so
+// that the search ends at the end of the level and the fatal entry, the last one, names it.  (A lowering that checks stored states keeps
+// the rule above.)
+template <class S>
+MC_HD ViolPair viol_pair(unsigned st, int ninv) {
+    ViolPair r = viol_pair<S>(st);
+    if (!ViolChecksStored<S>::value && r.kind == 1u && (int)r.inv >= ninv) { r.what = VIOL_P_FATAL; r.bin = VIOL_BIN_FATAL; }
+    return r;
+}
 // does the pair end the search at the end of its level?  (TLC treats a failed Assert and an evaluation error as fatal under -continue too)
 MC_HD bool viol_ends_search(const ViolPair &r) { return r.what == VIOL_P_FATAL; }
 // the column of the (states | outside) table a pair bumps in its bin, -1 = neither: a successor outside the model is not a stored state
@@ -80,6 +90,13 @@ MC_HD int viol_stored_bin(const typename S::Params &prm, Ref self, bool has_pare
     }
     if (!(st & ST_INVARIANT) || (st & (ST_ASSERT | ST_SPECERR | ST_OUT_OF_MODEL))) return -1;
     return (int)((st >> 8) & 31u);
+}
+// ... with the model's number of invariant entries: no stored state is listed under the index of a property of a step (the pair that
+// found it broke the property; the state itself breaks nothing)
+template <class S, class Ref, class Own, class Ev>
+MC_HD int viol_stored_bin(const typename S::Params &prm, Ref self, bool has_parent, int ninv, Own &&own, Ev &&ev) {
+    const int bin = viol_stored_bin<S>(prm, self, has_parent, own, ev);
+    return !ViolChecksStored<S>::value && bin >= ninv ? -1 : bin;
 }
 
 }  // namespace mc
