@@ -53,6 +53,27 @@ pub struct mc_sim_result {
     pub walks: u64, pub steps: u64, pub generated: u64, pub violating_walk: u64, pub max_depth: u32, pub verdict: i32,
     pub violated_invariant: i32, pub trace_len: u32, pub seconds: f64,
 }
+// recorded behaviours against the model (mc_engine_behaviours): rows are mc_state_bytes(spec) bytes each, `first` has count + 1 offsets
+// into them, `mask` (same width, or null: everything is observed) says which bytes the log records
+pub const MC_BEH_ACCEPTED: i32 = 1;
+pub const MC_BEH_REJECTED: i32 = 2;
+pub const MC_BEH_AMBIGUOUS: i32 = 3;
+pub const MC_BEH_MAX_CANDIDATES: u32 = 64;
+pub const MC_BEH_MAX_INIT: u64 = 65536;
+pub const MC_BEH_F_STUTTER: u32 = 1;
+#[repr(C)]
+pub struct mc_beh_opts {
+    pub count: u64, pub first: *const u64, pub rows: *const u8, pub mask: *const u8, pub flags: u32, pub iters: u32,
+}
+#[repr(C)]
+pub struct mc_beh_verdict {
+    pub verdict: i32, pub step: u32, pub candidates: u32, pub peak: u32, pub generated: u64, pub outside: u64, pub errors: u64,
+}
+#[repr(C)]
+pub struct mc_beh_result {
+    pub accepted: u64, pub rejected: u64, pub ambiguous: u64, pub observations: u64, pub generated: u64, pub first_rejected: u64,
+    pub seconds: f64,
+}
 // one entry of mc_engine_coverage: action id (-1 = Init), the states it was first to find, the successors it generated
 #[repr(C)]
 pub struct mc_action_coverage { pub action: i32, pub pad: u32, pub distinct: u64, pub generated: u64 }
@@ -102,6 +123,11 @@ extern "C" {
     pub fn mc_engine_step(e: *mut mc_engine, levels: u32, out: *mut mc_result) -> c_int;
     pub fn mc_engine_request_stop(e: *mut mc_engine) -> c_int;
     pub fn mc_engine_simulate(e: *mut mc_engine, opts: *const mc_sim_opts, out: *mut mc_sim_result) -> c_int;
+    // one verdict per behaviour of the batch; behaviour_witness: behaviour b once more on the host, one model path through its
+    // candidate sets (slots[k]: the slot into state k, -1 for the first, -2 for a stuttering step); *n_inout: capacity in, states out
+    pub fn mc_engine_behaviours(e: *mut mc_engine, opts: *const mc_beh_opts, out: *mut mc_beh_verdict, result: *mut mc_beh_result) -> c_int;
+    pub fn mc_engine_behaviour_witness(e: *mut mc_engine, opts: *const mc_beh_opts, b: u64, states: *mut u8, slots: *mut i32,
+                                       n_inout: *mut usize) -> c_int;
     pub fn mc_engine_trace(e: *mut mc_engine, states: *mut u8, actions: *mut i32, n_inout: *mut usize) -> c_int;
     // entries for Init and every action of the model, in action-id order; *n_inout: capacity in, count out
     pub fn mc_engine_coverage(e: *mut mc_engine, out: *mut mc_action_coverage, n_inout: *mut usize) -> c_int;
@@ -152,6 +178,10 @@ extern "C" {
     pub fn mc_check_files_dumps(tla: *const c_char, cfg_path: *const c_char, cfg: *const mc_config, report: *mut c_char, report_cap: usize,
                                 out: *mut mc_result, dump_path: *const c_char, dot_path: *const c_char, dot_flags: u32,
                                 recover_path: *const c_char, checkpoint_path: *const c_char) -> c_int;
+    pub fn mc_check_behaviours_files(tla: *const c_char, cfg_path: *const c_char, cfg: *const mc_config, behaviours_path: *const c_char,
+                                     observe: *const c_char, flags: u32, report: *mut c_char, cap: usize, out: *mut mc_beh_result) -> c_int;
+    // the inverse of mc_state_format for a compiled PlusCal program: row and mask (may be null) of mc_state_bytes(spec) bytes
+    pub fn mc_state_parse(spec: *const mc_spec_desc, text: *const c_char, row_out: *mut u8, mask_out: *mut u8) -> c_int;
     pub fn mc_simulate_files(tla: *const c_char, cfg_path: *const c_char, cfg: *const mc_config, opts: *const mc_sim_opts,
                              report: *mut c_char, cap: usize, out: *mut mc_sim_result, interrupt: *const c_int) -> c_int;
     // PlusCal front-end: `pcal2tla` and the compiler to the GPU interpreter (include/tlamc.h)
@@ -166,6 +196,8 @@ extern "C" {
     pub fn mc_program_fairness(p: *const mc_program, weak_fair_mask: *mut u64, refusal: *mut *const c_char) -> c_int;
     pub fn mc_program_fairness_strong(p: *const mc_program, weak_mask: *mut u64, strong_mask: *mut u64, refusal: *mut *const c_char) -> c_int;
     pub fn mc_program_property(p: *const mc_program, index: c_int) -> *const c_char;
+    // the byte mask (mc_beh_opts.mask) of a log that records the named variables (comma-separated) only
+    pub fn mc_program_observe(p: *const mc_program, variables: *const c_char, mask_out: *mut u8, bytes: usize) -> c_int;
     // the cfg's VIEW (the text of its definition, null without one) and ACTION_CONSTRAINT names (null past the last)
     pub fn mc_program_view(p: *const mc_program) -> *const c_char;
     pub fn mc_program_action_constraint(p: *const mc_program, index: c_int) -> *const c_char;

@@ -508,6 +508,58 @@ typedef struct {
 } mc_sim_result;
 int mc_engine_simulate(mc_engine *e, const mc_sim_opts *opts, mc_sim_result *out);
 
+/* ------------------------------------------------------------------ recorded behaviours against the model
+ * "Is every one of these logged executions a behaviour of my spec?"  A behaviour is a sequence of observations o_0 .. o_{T-1}, T >= 1,
+ * each a row of mc_state_bytes(spec) bytes in the layout mc_engine_read_states / mc_state_apply use (what an implementation logs: the
+ * variables' cells).  One byte mask of the same width goes with the batch (NULL: everything is observed); a state s MATCHES o iff
+ * (s ^ o) & mask == 0.  Candidate sets: K_0 = the initial states that match o_0; K_i = the distinct rows that match o_i and are a
+ * successor — through an enabled slot — of a member of K_{i-1}; with MC_BEH_F_STUTTER also the members of K_{i-1} that match o_i
+ * themselves (the stuttering step [Next]_vars allows).  A successor whose evaluation fails (Assert, evaluation error, a full slot array)
+ * is no step and is counted in `errors`; one outside a CONSTRAINT is a step (a CONSTRAINT bounds the search, not the system) and is
+ * counted in `outside` where it matches; invariants are not checked.  Distinct is by row, never by fingerprint (a VIEW).
+ * One GPU wavefront decides one behaviour, one lane per candidate: a set that would pass MC_BEH_MAX_CANDIDATES rows makes the behaviour
+ * MC_BEH_AMBIGUOUS — not decided; no candidate is ever dropped.  Every field of a verdict is a function of the behaviour, the mask and
+ * the flags alone: not of the batch's order, the engine's capacities, `iters` or the device.
+ * Refused (MC_EBADCFG + mc_last_error): an empty behaviour, a model with more than 65536 initial states, a sharded engine, and an
+ * MC_F_JIT engine (its rows are packed and there is no way to import an interpreter's row into them).  The engine's search, if any,
+ * is left as it is. */
+#define MC_BEH_ACCEPTED 1          /* K_{T-1} is not empty: step = T                                              */
+#define MC_BEH_REJECTED 2          /* K_step is empty (step = 0: no initial state matches)                       */
+#define MC_BEH_AMBIGUOUS 3         /* K_step would hold more than MC_BEH_MAX_CANDIDATES rows: not decided        */
+#define MC_BEH_MAX_CANDIDATES 64
+#define MC_BEH_MAX_INIT 65536
+#define MC_BEH_F_STUTTER 1u        /* an observation may repeat the state before it                              */
+typedef struct {
+    uint64_t count;           /* behaviours                                                                 */
+    const uint64_t *first;    /* [count + 1]: behaviour b is observations first[b] .. first[b + 1] - 1 of rows */
+    const uint8_t *rows;      /* first[count] rows of mc_state_bytes(spec) bytes                             */
+    const uint8_t *mask;      /* mc_state_bytes(spec) bytes, or NULL                                         */
+    uint32_t flags;           /* MC_BEH_F_*                                                                  */
+    uint32_t iters;           /* observations a launch advances a behaviour by at most; 0 = the default (16) */
+} mc_beh_opts;
+typedef struct {
+    int32_t verdict;          /* MC_BEH_*                                                                   */
+    uint32_t step;            /* T (accepted), or the observation that decided                              */
+    uint32_t candidates;      /* size of the last non-empty candidate set                                   */
+    uint32_t peak;            /* size of the largest one                                                    */
+    uint64_t generated;       /* initial states built + enabled successors evaluated, the deciding step included */
+    uint64_t outside;         /* matching steps that leave the CONSTRAINTs                                  */
+    uint64_t errors;          /* enabled successors that are no step: Assert, evaluation error, overflow    */
+} mc_beh_verdict;
+typedef struct {
+    uint64_t accepted, rejected, ambiguous;
+    uint64_t observations;    /* observations examined (a behaviour decided at `step` < T: step + 1)        */
+    uint64_t generated;
+    uint64_t first_rejected;  /* least index of a rejected behaviour, ~0 if none                            */
+    double seconds;
+} mc_beh_result;
+int mc_engine_behaviours(mc_engine *e, const mc_beh_opts *opts, mc_beh_verdict *out, mc_beh_result *result);
+/* Why: behaviour b once more, on the host, with parent links.  One model path s_0 .. s_{n-1} through its candidate sets: n = the
+ * verdict's step (the whole behaviour if accepted; 0 if no initial state matches).  states_out: rows, slots_out[k]: the slot from
+ * s_{k-1} to s_k (-1 for s_0, -2 for a stuttering step).  *n_inout: capacity in, n out (MC_EBADCFG with n when too small).  The path
+ * is deterministic: it ends in the least row of the last set, and a row reached in several ways keeps the least slot. */
+int mc_engine_behaviour_witness(mc_engine *e, const mc_beh_opts *opts, uint64_t b, uint8_t *states_out, int32_t *slots_out, size_t *n_inout);
+
 /* Checkpoint / recover — TLC checkpoints a run into its states/ directory ("-- Checkpointing of run states/01-08-03-18-14-01
  * completed.", reference examples/SpecifyingSystems/AdvancedExamples/testout1:10; .gitignore:2) and continues it with -recover.
  * mc_engine_checkpoint: after an mc_engine_run that ended without a violation (normally MC_V_BUDGET), write every distinct
@@ -844,6 +896,9 @@ typedef struct mc_action_property {
     char    text[256];         /* the conjunct as the module writes it, tokens joined by one blank   */
 } mc_action_property;
 int mc_program_action_property(const mc_program *p, int index, mc_action_property *out);
+/* which bytes of a row a log of the named variables observes (mc_beh_opts.mask): `variables` = comma-separated names of the program's
+ * variables; a record stands for its fields; `bytes` = mc_state_bytes of the program's descriptor.  MC_EBADCFG for an unknown name. */
+int mc_program_observe(const mc_program *p, const char *variables, uint8_t *mask_out, size_t bytes);
 void mc_program_free(mc_program *p);
 
 /* ------------------------------------------------------------------ helpers (host only) */
@@ -856,6 +911,12 @@ const char *mc_action_name(const mc_spec_desc *spec, int32_t action);
  * and the successor it produces — what a host needs to print a counterexample it assembled itself (sharded runs) */
 int mc_state_action(const mc_spec_desc *spec, const uint8_t *state, int32_t slot);
 int mc_state_apply(const mc_spec_desc *spec, const uint8_t *state, int32_t slot, uint8_t *successor_out);
+/* the inverse of mc_state_format for MC_SPEC_PCAL (MC_ENOSPEC for the other lowerings): the text `mc -dump` / a TLC trace prints for one
+ * state -> its row.  Conjuncts may be missing: a variable the text does not mention is unobserved — its cells are zero in row_out and
+ * clear in mask_out (mc_state_bytes(spec) bytes each; mask_out may be NULL), the mentioned ones' are 0xff, as mc_program_observe gives
+ * them.  MC_EPARSE (+ mc_last_error) for a text that is no state of the program: an unknown variable, a value of the wrong shape, a
+ * string the program does not know. */
+int mc_state_parse(const mc_spec_desc *spec, const char *text, uint8_t *row_out, uint8_t *mask_out);
 const char *mc_strerror(int code);
 const char *mc_last_error(void);                                    /* detail of the last failure    */
 int mc_device_count(void);
@@ -915,6 +976,15 @@ int mc_check_files_dumps(const char *tla_path, const char *cfg_path, const mc_co
  * simulation between two launches: the report then says so (MC_V_BUDGET). */
 int mc_simulate_files(const char *tla_path, const char *cfg_path, const mc_config *cfg, const mc_sim_opts *opts, char *report, size_t report_cap,
                       mc_sim_result *out, const volatile int *interrupt);
+/* `mc X.tla -behaviours FILE [-observe v1,v2,...] [-stutter]`: the module resolved as mc_check_files resolves it (a compiled PlusCal
+ * program: the file's states are texts, mc_state_parse), FILE read — states as `mc -dump` / a TLC trace prints them, optional
+ * "State k:" headers ignored, a blank line between states, a line of ---- between behaviours — and mc_engine_behaviours run on it.
+ * observe: comma-separated variable names (mc_program_observe), or NULL: the variables every state of the file mentions.  flags:
+ * MC_BEH_F_*.  The report gives the counts, a warning that names the ambiguous behaviours, and for the first rejected behaviour
+ * "Error: Behaviour b is not a behaviour of the model: no step leads to observation i.", the witness in TLC's layout and the
+ * observation.  Behaviours and observations are counted from 1 in the report. */
+int mc_check_behaviours_files(const char *tla_path, const char *cfg_path, const mc_config *cfg, const char *behaviours_path, const char *observe,
+                              unsigned flags, char *report, size_t report_cap, mc_beh_result *out);
 
 #ifdef __cplusplus
 }

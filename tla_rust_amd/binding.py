@@ -182,6 +182,41 @@ class SimResult(C.Structure):
                 ("seconds", C.c_double)]
 
 
+class BehOpts(C.Structure):
+    _fields_ = [("count", C.c_uint64), ("first", C.POINTER(C.c_uint64)), ("rows", C.c_char_p), ("mask", C.c_char_p),
+                ("flags", C.c_uint32), ("iters", C.c_uint32)]
+
+
+class BehVerdict(C.Structure):
+    _fields_ = [("verdict", C.c_int32), ("step", C.c_uint32), ("candidates", C.c_uint32), ("peak", C.c_uint32),
+                ("generated", C.c_uint64), ("outside", C.c_uint64), ("errors", C.c_uint64)]
+
+
+class BehResult(C.Structure):
+    _fields_ = [("accepted", C.c_uint64), ("rejected", C.c_uint64), ("ambiguous", C.c_uint64), ("observations", C.c_uint64),
+                ("generated", C.c_uint64), ("first_rejected", C.c_uint64), ("seconds", C.c_double)]
+
+
+BEH_VERDICTS = {1: "accepted", 2: "rejected", 3: "ambiguous"}   # MC_BEH_*
+MC_BEH_F_STUTTER = 1
+MC_BEH_MAX_CANDIDATES = 64
+BEH_FIELDS = ("verdict", "step", "candidates", "peak", "generated", "outside", "errors")
+
+
+def beh_opts(rows_list, W, mask=None, stutter=False, iters=0):
+    """mc_beh_opts of a batch: rows_list = one list of rows (bytes of W bytes each) per behaviour.  Returns (opts, what must stay alive)"""
+    first = (C.c_uint64 * (len(rows_list) + 1))()
+    for b, rows in enumerate(rows_list):
+        if any(len(r) != W for r in rows):
+            raise ValueError(f"behaviour {b}: every observation is {W} bytes")
+        first[b + 1] = first[b] + len(rows)
+    blob = b"".join(b"".join(rows) for rows in rows_list)
+    if mask is not None and len(mask) != W:
+        raise ValueError(f"the mask is {W} bytes")
+    o = BehOpts(len(rows_list), first, blob, bytes(mask) if mask is not None else None, MC_BEH_F_STUTTER if stutter else 0, iters)
+    return o, (first, blob)
+
+
 SIM_ENDS = {1: "depth", 2: "violation", 3: "deadlock", 4: "out-of-model", 5: "stutter", 6: "overflow"}
 
 
@@ -217,6 +252,11 @@ def lib():
     L.mc_engine_set_progress.argtypes = [C.c_void_p, PROGRESS_FN, C.c_void_p, C.c_double]
     L.mc_engine_request_stop.argtypes = [C.c_void_p]
     L.mc_engine_simulate.argtypes = [C.c_void_p, C.POINTER(SimOpts), C.POINTER(SimResult)]
+    L.mc_engine_behaviours.argtypes = [C.c_void_p, C.POINTER(BehOpts), C.POINTER(BehVerdict), C.POINTER(BehResult)]
+    L.mc_engine_behaviour_witness.argtypes = [C.c_void_p, C.POINTER(BehOpts), C.c_uint64, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]
+    L.mc_state_parse.argtypes = [C.POINTER(SpecDesc), C.c_char_p, C.c_char_p, C.c_char_p]
+    L.mc_check_behaviours_files.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Config), C.c_char_p, C.c_char_p, C.c_uint, C.c_char_p, C.c_size_t,
+                                            C.POINTER(BehResult)]
     L.mc_engine_trace.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]
     L.mc_engine_kernel_stats.argtypes = [C.c_void_p, C.POINTER(KernelStats)]
     L.mc_engine_coverage.argtypes = [C.c_void_p, C.POINTER(ActionCoverage), C.POINTER(C.c_size_t)]
@@ -335,6 +375,7 @@ def lib():
         L.mc_program_action_property.argtypes = [C.c_void_p, C.c_int, C.POINTER(ActionProperty)]
         L.mc_program_property.argtypes = [C.c_void_p, C.c_int]
         L.mc_program_property.restype = C.c_char_p
+        L.mc_program_observe.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t]
         L.mc_program_free.argtypes = [C.c_void_p]
         L.mc_program_free.restype = None
     _lib = L
@@ -386,6 +427,29 @@ def state_apply(spec, params, state: bytes, slot: int):
     out = C.create_string_buffer(lib().mc_state_bytes(C.byref(d)))
     _check(lib().mc_state_apply(C.byref(d), state, slot, out), "mc_state_apply")
     return out.raw
+
+
+def state_parse(spec, params, text: str):
+    """mc_state_parse, the inverse of state_format for a compiled PlusCal program: (row, mask) — a variable the text leaves out is
+    zero in the row and clear in the mask"""
+    d = spec_desc(spec, params)
+    n = lib().mc_state_bytes(C.byref(d))
+    row, mask = C.create_string_buffer(n), C.create_string_buffer(n)
+    _check(lib().mc_state_parse(C.byref(d), text.encode(), row, mask), "mc_state_parse")
+    return row.raw, mask.raw
+
+
+def check_behaviours_files(tla_path, behaviours_path, cfg_path=None, observe=None, stutter=False, device=0, **kw):
+    """`mc X.tla -behaviours FILE [-observe ...] [-stutter]` (mc_check_behaviours_files): (totals, report text)"""
+    flags = 128 if kw.pop("generic", False) else 0   # MC_F_GENERIC
+    cfg = Config(device, flags, kw.pop("table_capacity", 1 << 16), kw.pop("arena_capacity", 1 << 14), kw.pop("chunk_states", 0), 0, 0, 0, 1)
+    report = C.create_string_buffer(1 << 22)
+    r = BehResult()
+    _check(lib().mc_check_behaviours_files(str(tla_path).encode(), str(cfg_path).encode() if cfg_path else None, C.byref(cfg),
+                                           str(behaviours_path).encode(), ",".join(observe).encode() if observe else None,
+                                           MC_BEH_F_STUTTER if stutter else 0, report, len(report), C.byref(r)), "mc_check_behaviours_files")
+    return Result(accepted=r.accepted, rejected=r.rejected, ambiguous=r.ambiguous, observations=r.observations, generated=r.generated,
+                  first_rejected=None if r.first_rejected == (1 << 64) - 1 else r.first_rejected, seconds=r.seconds), report.value.decode()
 
 
 def _result(r: CResult):
@@ -441,6 +505,33 @@ class Engine:
             out["recorded"] = [dict(len=ln[k], end=SIM_ENDS.get(en[k]), slots=[slots[k * depth + s] for s in range(max(ln[k] - 1, 0))])
                                for k in range(record)]
         return out
+
+    def behaviours(self, rows_list, mask=None, stutter=False, iters=0):
+        """mc_engine_behaviours: is every recorded behaviour a behaviour of the model?  rows_list: per behaviour, its observations as
+        rows (bytes, state_bytes each: what read_states / state_apply give); mask: bytes of the same width saying which are observed
+        (None: all), one for the batch; stutter: an observation may repeat the state before it.  Result: the totals, and
+        verdicts = [{verdict: accepted / rejected / ambiguous, step, candidates, peak, generated, outside, errors}]."""
+        W = lib().mc_state_bytes(C.byref(self.desc))
+        o, keep = beh_opts(rows_list, W, mask, stutter, iters)
+        out = (BehVerdict * max(len(rows_list), 1))()
+        r = BehResult()
+        _check(lib().mc_engine_behaviours(self._h, C.byref(o), out, C.byref(r)), "mc_engine_behaviours")
+        return Result(accepted=r.accepted, rejected=r.rejected, ambiguous=r.ambiguous, observations=r.observations, generated=r.generated,
+                      first_rejected=None if r.first_rejected == (1 << 64) - 1 else r.first_rejected, seconds=r.seconds,
+                      verdicts=[Result(verdict=BEH_VERDICTS[v.verdict], **{f: getattr(v, f) for f in BEH_FIELDS[1:]})
+                                for v in out[:len(rows_list)]])
+
+    def behaviour_witness(self, rows_list, b, mask=None, stutter=False):
+        """mc_engine_behaviour_witness: behaviour b of the batch once more on the host; one model path through its candidate sets, as
+        [(slot, row)] — slot -1 for the initial state, -2 for a stuttering step.  The whole behaviour if it is accepted, the states
+        before the deciding observation otherwise."""
+        W = lib().mc_state_bytes(C.byref(self.desc))
+        o, keep = beh_opts(rows_list, W, mask, stutter, 0)
+        cap = C.c_size_t(len(rows_list[b]))
+        states = C.create_string_buffer(W * max(cap.value, 1))
+        slots = (C.c_int32 * max(cap.value, 1))()
+        _check(lib().mc_engine_behaviour_witness(self._h, C.byref(o), b, states, slots, C.byref(cap)), "mc_engine_behaviour_witness")
+        return [(slots[k], states.raw[k * W:(k + 1) * W]) for k in range(cap.value)]
 
     def coverage(self):
         """mc_engine_coverage (TLC's -coverage; an engine created with coverage=True): {action name: (distinct, generated)} for "Init"
@@ -944,6 +1035,13 @@ class Program:
         ap = ActionProperty()
         while lib().mc_program_action_property(h, len(self.action_properties), C.byref(ap)) == 0:
             self.action_properties.append(Result(origin=ap.origin.decode(), kind=APROP_KINDS[int(ap.kind)], index=int(ap.index), text=ap.text.decode()))
+
+    def observe(self, names):
+        """mc_program_observe: the byte mask (Engine.behaviours' mask) of a log that records the named variables only"""
+        n = state_bytes("pcal", self.params)
+        buf = C.create_string_buffer(n)
+        _check(lib().mc_program_observe(self._h, ",".join(names).encode(), buf, n), "mc_program_observe")
+        return buf.raw
 
     def translated(self, label_fair=False):
         """the module text after translation; label_fair: Spec's fairness conjuncts label by label, as pcal2tla writes `+` / `-` labels"""

@@ -17,7 +17,7 @@ SOURCES = ["engine.hip", "frontend.cpp"]
 # (engine.hip includes every spec header through spec_registry.h; a unit's code changes only with its own).  state_graph.hip, the host
 # half of what consumes the state graph's CSR arrays, is one object for all of them: the spec units never see engine_live.h.
 # tests/test_engine_layout.py checks the lists against the files' #include lines.
-ENGINE_BASE = ["engine.hip", "hip_owned.h", "engine_kernels.h", "engine_sim.h", "sim_walk.h", "engine_coverage.h", "coverage.h", "engine_violations.h", "violations.h",
+ENGINE_BASE = ["engine.hip", "hip_owned.h", "engine_kernels.h", "engine_sim.h", "sim_walk.h", "engine_behaviours.h", "behaviour.h", "engine_coverage.h", "coverage.h", "engine_violations.h", "violations.h",
                "engine_graph.h",
                "graph.h", "liveness.h", "live_query.h", "state_graph.h", "spec_gen.h", "mc_common.h", "spec_registry.h", "../../include/tlamc.h"]
 ENGINE_OWN = {0: ["spec_pluscal.h", "spec_raft.h", "spec_ssi.h", "spec_vm.h", "spec_vm_cfg.h", "spec_paxos.h", "engine_pairs.h"], 7: ["spec_paxos.h"], 1: ["spec_pluscal.h"],

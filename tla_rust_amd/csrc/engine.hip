@@ -48,6 +48,7 @@ namespace mc {
 #include "engine_kernels.h"   // namespace mc { ... every kernel ... }
 #include "engine_pairs.h"     // k_expand_pairs: the by-pairs expand + insert + write kernel (specs with S::PAIR_FAMILIES)
 #include "engine_sim.h"       // k_simulate: simulation mode, one lane per random walk (mc_engine_simulate)
+#include "engine_behaviours.h"  // k_behaviours: recorded behaviours against the model, one wavefront per behaviour (mc_engine_behaviours)
 #include "engine_coverage.h"  // k_coverage_generated / k_coverage_distinct: per-action counts (MC_F_COVERAGE, mc_engine_coverage)
 #include "engine_violations.h"  // k_viol_stored / k_viol_frontier: what a flagged level holds (MC_F_CONTINUE, mc_engine_violations)
 #include "engine_graph.h"     // k_graph_index / k_graph_degree / k_graph_fill / k_live_proc: the state graph in CSR form (mc_engine_graph)
@@ -110,6 +111,9 @@ struct EngineBase {
     virtual int shard_restore(const char *path) = 0;
     virtual size_t state_bytes() const = 0;
     virtual int simulate(const mc_sim_opts *opts, mc_sim_result *out) = 0;
+    virtual int behaviours(const mc_beh_opts *opts, mc_beh_verdict *out, mc_beh_result *result) = 0;
+    virtual int behaviours_refused() = 0;   // MC_OK, or why this engine checks no behaviours (mc_last_error says it)
+    virtual const mc_spec_desc *spec_desc() const = 0;
     virtual int coverage(mc_action_coverage *out, size_t *n_inout) = 0;
     virtual int violations(mc_violations_info *info, mc_violation *out, size_t *n_inout) = 0;
     virtual int violation_trace(size_t k, uint8_t *states_out, int32_t *actions_out, size_t *n_inout) = 0;
@@ -337,6 +341,12 @@ struct Engine : EngineBase {
         std::vector<int32_t> trace_acts;   // ... and their action ids
         size_t trace_n = 0;
     } sim;
+    // ---- behaviour checking (mc_engine_behaviours): a round's candidate sets, observations and verdicts, allocated on first use
+    struct Beh {
+        DevBuf<uint64_t> set[2], stage, rows, first, carry, mask;
+        DevBuf<mc_beh_verdict> out;
+        DevBuf<BehCounters> ctr;
+    } beh;
     // ---- coverage (MC_F_COVERAGE, mc_engine_coverage): per-action histograms, bin 0 = Init, bin a + 1 = action id a
     struct Cov {
         bool on = false;
@@ -2160,6 +2170,104 @@ struct Engine : EngineBase {
         *n_inout = n;
         return MC_OK;
     }
+    // ------------------------------------------------------------------------------- behaviours (mc_engine_behaviours; engine_behaviours.h)
+    // The batch runs in rounds of chunk / 64 behaviours (a behaviour takes 64 columns of each of three buffers: a round takes what three
+    // chunks of states take), each round in ceil(longest behaviour / iters) launches, enqueued back to back: a launch is bounded by
+    // `iters` observations per behaviour, and a decided behaviour's wavefront leaves at once.  Nothing of the search is touched.
+    static constexpr uint32_t BEH_ITERS = 16;
+    const mc_spec_desc *spec_desc() const override { return &desc; }
+    int behaviours_refused() override {
+        if (cfg.shard_count > 1) { set_error("behaviours: not available for a sharded engine (shard_count > 1)"); return MC_EBADCFG; }
+        if (PackedRows<S>::value || HasExport<S>::value) {
+            set_error("behaviours: not available for an MC_F_JIT engine: generated code packs its rows, and there is no import_row that turns an observation "
+                      "in the interpreter's layout into one (create the engine without MC_F_JIT)");
+            return MC_EBADCFG;
+        }
+        if (S::num_init(prm) > MC_BEH_MAX_INIT) { set_error("behaviours: the model has more than 65536 initial states"); return MC_EBADCFG; }
+        return MC_OK;
+    }
+    int behaviours(const mc_beh_opts *o, mc_beh_verdict *out, mc_beh_result *res) override {
+        memset(res, 0, sizeof *res);
+        res->first_rejected = ~0ull;
+        if (int rc = behaviours_refused()) return rc;
+        if constexpr (PackedRows<S>::value || HasExport<S>::value) return MC_EBADCFG;
+        else {
+        if (o->count && (!o->first || !o->rows || !out)) { set_error("behaviours: first, rows and the verdict array are needed"); return MC_EBADCFG; }
+        for (uint64_t b = 0; b < o->count; ++b)
+            if (o->first[b + 1] <= o->first[b] || o->first[b + 1] - o->first[b] >= (1ull << 31)) {
+                set_error("behaviours: behaviour " + std::to_string(b) + " is empty (T = 0), or longer than 2^31 - 1 observations");
+                return MC_EBADCFG;
+            }
+        if (!o->count) return MC_OK;
+        HIP_TRY(hipSetDevice(cfg.device));
+        // (an early return leaves no copy into the caller's arrays or out of this frame's in flight)
+        struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{stream};
+        const uint32_t iters = o->iters ? o->iters : BEH_ITERS;
+        const uint64_t R = chunk / 64 < o->count ? chunk / 64 : o->count;   // (chunk >= 256)
+        std::vector<uint64_t> hmask(W, ~0ull);
+        if (o->mask) memcpy(hmask.data(), o->mask, (size_t)W * sizeof(uint64_t));
+        const bool full = beh_mask_full(hmask.data(), W);
+        for (int k = 0; k < 2; ++k) HIP_TRY(beh.set[k].reserve(R * 64 * W));
+        HIP_TRY(beh.stage.reserve(R * 64 * W));
+        HIP_TRY(beh.first.reserve(R + 1));
+        HIP_TRY(beh.carry.reserve(R));
+        HIP_TRY(beh.out.reserve(R));
+        HIP_TRY(beh.ctr.reserve(1));
+        BehCounters c;
+        memset(&c, 0, sizeof c);
+        c.first_rejected = ~0ull;
+        HIP_TRY(hipMemcpyAsync(beh.ctr, &c, sizeof c, hipMemcpyHostToDevice, stream));
+        if (!full) {
+            HIP_TRY(beh.mask.reserve(W));
+            HIP_TRY(hipMemcpyAsync(beh.mask, hmask.data(), (size_t)W * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        }
+        BehArgs a{};
+        a.mask = full ? nullptr : (const uint64_t *)beh.mask;
+        a.flags = o->flags;
+        a.iters = iters;
+        a.ctr = beh.ctr;
+        const size_t lds = ((size_t)2 * W + MC_BEH_MAX_CANDIDATES) * sizeof(uint64_t);
+        std::vector<uint64_t> rel(R + 1);
+        const auto t0 = std::chrono::steady_clock::now();
+        for (uint64_t b0 = 0; b0 < o->count; b0 += R) {
+            const uint64_t n = o->count - b0 < R ? o->count - b0 : R;
+            const uint64_t r0 = o->first[b0], nrows = o->first[b0 + n] - r0;
+            uint64_t longest = 0;
+            for (uint64_t k = 0; k <= n; ++k) rel[k] = o->first[b0 + k] - r0;
+            for (uint64_t k = 0; k < n; ++k) longest = std::max(longest, rel[k + 1] - rel[k]);
+            HIP_TRY(beh.rows.reserve(nrows * W));
+            HIP_TRY(hipMemcpyAsync(beh.rows, o->rows + r0 * W * sizeof(uint64_t), nrows * W * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(beh.first, rel.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemsetAsync(beh.carry, 0, n * sizeof(uint64_t), stream));
+            HIP_TRY(hipMemsetAsync(beh.out, 0, n * sizeof(mc_beh_verdict), stream));
+            a.b0 = b0;
+            a.n = n;
+            a.first = beh.first;
+            a.rows = beh.rows;
+            a.set0 = beh.set[0];
+            a.set1 = beh.set[1];
+            a.stage = beh.stage;
+            a.carry = beh.carry;
+            a.out = beh.out;
+            for (uint64_t l = 0; l < (longest + iters - 1) / iters; ++l) {
+                hipLaunchKernelGGL(k_behaviours<S>, dim3((unsigned)n), dim3(64), lds, stream, prm, a);
+                HIP_TRY(hipGetLastError());
+            }
+            HIP_TRY(hipMemcpyAsync(out + b0, beh.out, n * sizeof(mc_beh_verdict), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));   // (rel and the round's buffers are reused by the next round)
+        }
+        HIP_TRY(hipMemcpy(&c, beh.ctr, sizeof c, hipMemcpyDeviceToHost));
+        res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        res->accepted = c.accepted;
+        res->rejected = c.rejected;
+        res->ambiguous = c.ambiguous;
+        res->observations = c.observations;
+        res->generated = c.generated;
+        res->first_rejected = c.first_rejected;
+        if (c.accepted + c.rejected + c.ambiguous != o->count) { set_error("behaviours: a behaviour was left undecided"); return MC_ESTATE; }
+        return MC_OK;
+        }
+    }
     int kernel_stats(mc_kernel_stats *o) override {
         o->expand = kstat[0];
         o->insert = kstat[1];
@@ -2390,6 +2498,36 @@ int mc_engine_request_stop(mc_engine *e) {
 }
 int mc_engine_trace(mc_engine *e, uint8_t *states_out, int32_t *actions_out, size_t *n_inout) {
     return e && n_inout ? e->impl->trace(states_out, actions_out, n_inout) : MC_EBADCFG;
+}
+int mc_engine_behaviours(mc_engine *e, const mc_beh_opts *opts, mc_beh_verdict *out, mc_beh_result *result) {
+    return e && opts && result ? e->impl->behaviours(opts, out, result) : MC_EBADCFG;
+}
+int mc_engine_behaviour_witness(mc_engine *e, const mc_beh_opts *opts, uint64_t b, uint8_t *states_out, int32_t *slots_out, size_t *n_inout) {
+    if (!e || !opts || !n_inout || !opts->first || !opts->rows || b >= opts->count || opts->first[b + 1] <= opts->first[b]) {
+        mc_set_error_internal("behaviour_witness: no such behaviour");
+        return MC_EBADCFG;
+    }
+    if (int rc = e->impl->behaviours_refused()) return rc;   // (what the batch call refuses)
+    return dispatch_spec(e->impl->spec_desc(), [&](auto s, const auto &prm) {
+        using S = decltype(s);
+        const size_t W = (size_t)S::words(prm);
+        const uint64_t T = opts->first[b + 1] - opts->first[b];
+        std::vector<uint64_t> rows(T * W), mask(W);
+        memcpy(rows.data(), opts->rows + opts->first[b] * W * sizeof(uint64_t), T * W * sizeof(uint64_t));
+        if (opts->mask) memcpy(mask.data(), opts->mask, W * sizeof(uint64_t));
+        mc_beh_verdict v;
+        BehSets sets;
+        beh_check<S>(prm, rows.data(), T, opts->mask ? mask.data() : nullptr, opts->flags, &v, &sets);
+        const size_t n = sets.sets.size();
+        if (n > *n_inout) { *n_inout = n; mc_set_error_internal("behaviour_witness: buffers too small"); return MC_EBADCFG; }
+        *n_inout = n;
+        if (!n) return MC_OK;
+        if (!states_out || !slots_out) { mc_set_error_internal("behaviour_witness: states_out and slots_out are needed"); return MC_EBADCFG; }
+        std::vector<uint64_t> path(n * W);
+        beh_witness(sets, (int)W, path.data(), slots_out);
+        memcpy(states_out, path.data(), n * W * sizeof(uint64_t));
+        return MC_OK;
+    });
 }
 int mc_engine_simulate(mc_engine *e, const mc_sim_opts *opts, mc_sim_result *out) {
     return e && opts && out ? e->impl->simulate(opts, out) : MC_EBADCFG;

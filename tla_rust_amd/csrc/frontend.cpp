@@ -12,6 +12,7 @@
 // hand-lowered spec and its text is fingerprinted so a changed spec is refused, not mis-checked.  A module with a
 // PlusCal algorithm that has no hand lowering is compiled (pcal.cpp, pcal_compile.cpp) and runs through the
 // bytecode interpreter of spec_vm.h; `mc --transpile` is the reference's `pcal2tla` step (Makefile:3-4).
+#include <ctype.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -87,6 +88,255 @@ int mc_program_live_property(const mc_program *p, int index, mc_live_property *o
 }
 const char *mc_program_live_predicate(const mc_program *p, int index) {
     return p && index >= 0 && (size_t)index < p->prog.live_preds.size() ? p->prog.live_preds[(size_t)index].text.c_str() : nullptr;
+}
+// ---- rows of a compiled program as a log sees them (mc_engine_behaviours): which cells a variable has, the mask of named variables,
+// and the inverse of vm_format
+// a variable's cells run from its base to the next variable's (or to nv)
+static void var_cells(const pcal::Program &P, const pcal::VarInfo &v, int &first, int &stop) {
+    first = v.base;
+    stop = P.nv;
+    for (const auto &u : P.vars) if (u.base > v.base && u.base < stop) stop = u.base;
+}
+static void mask_cells(uint8_t *mask, int first, int stop) {
+    for (int c = first; c < stop; ++c) memset(mask + (size_t)c * 4, 0xff, 4);
+}
+// the flattener's variables of the record variable `name`: r_f, r_f_g ... — only where the algorithm's own text declares `name` and no
+// variable of the program is called `name` (a variable that merely begins with "name_" belongs to no record)
+static bool is_record_of(const pcal::Program &P, const std::string &name, const pcal::VarInfo &v) {
+    if (v.name.compare(0, name.size() + 1, name + "_") != 0) return false;
+    for (const auto &u : P.vars) if (u.name == name) return false;
+    // the translation defines `name == [f |-> name_f, ...]` for a flattened record, and for nothing else
+    return P.translated.find("\n" + name + " == [") != std::string::npos;
+}
+int mc_program_observe(const mc_program *p, const char *variables, uint8_t *mask_out, size_t bytes) {
+    if (!p || !variables || !mask_out) return MC_EBADCFG;
+    const auto &vars = p->prog.vars;
+    const size_t need = (size_t)((p->prog.nv + 1) / 2) * 8;
+    if (bytes < need) { mc_set_error_internal("mc_program_observe: the mask is mc_state_bytes(spec) bytes"); return MC_EBADCFG; }
+    memset(mask_out, 0, bytes);
+    std::string names(variables);
+    size_t at = 0;
+    while (at <= names.size()) {
+        size_t end = names.find(',', at);
+        if (end == std::string::npos) end = names.size();
+        std::string name = names.substr(at, end - at);
+        at = end + 1;
+        while (!name.empty() && isspace((unsigned char)name.back())) name.pop_back();
+        while (!name.empty() && isspace((unsigned char)name.front())) name.erase(name.begin());
+        if (name.empty()) continue;
+        bool found = false;
+        for (const auto &v : vars) {
+            if (v.name != name && !is_record_of(p->prog, name, v)) continue;
+            int first, stop;
+            var_cells(p->prog, v, first, stop);
+            mask_cells(mask_out, first, stop);
+            found = true;
+        }
+        if (!found) { mc_set_error_internal(("mc_program_observe: the program has no variable `" + name + "`").c_str()); return MC_EBADCFG; }
+    }
+    return MC_OK;
+}
+
+namespace {
+// a value as vm_format prints it
+struct PVal {
+    enum K { INT, BOOL, STR, DEF, SET, SEQ, FUN, REC } k = INT;
+    long long i = 0;
+    std::string s;
+    std::vector<PVal> el;              // SET / SEQ elements, FUN / REC values
+    std::vector<long long> keys;       // FUN
+    std::vector<std::string> fields;   // REC
+};
+struct PParser {
+    const char *p;
+    std::string err;
+    void ws() { while (*p && isspace((unsigned char)*p)) ++p; }
+    bool eat(const char *t) { ws(); const size_t n = strlen(t); if (strncmp(p, t, n)) return false; p += n; return true; }
+    bool fail(const std::string &m) { if (err.empty()) err = m + " at `" + std::string(p).substr(0, 20) + "`"; return false; }
+    bool ident(std::string &out) {
+        ws();
+        const char *q = p;
+        while (isalnum((unsigned char)*q) || *q == '_') ++q;
+        if (q == p) return fail("a name is expected");
+        out.assign(p, q);
+        p = q;
+        return true;
+    }
+    bool list(PVal &v, const char *close) {   // elements up to `close`
+        if (eat(close)) return true;
+        for (;;) {
+            v.el.emplace_back();
+            if (!value(v.el.back())) return false;
+            if (eat(close)) return true;
+            if (!eat(",")) return fail("`,` is expected");
+        }
+    }
+    bool value(PVal &v) {
+        ws();
+        if (eat("<<")) { v.k = PVal::SEQ; return list(v, ">>"); }
+        if (eat("{")) { v.k = PVal::SET; return list(v, "}"); }
+        if (eat("[")) {
+            v.k = PVal::REC;
+            for (;;) {
+                std::string f;
+                if (!ident(f) || !(eat("|->") || fail("`|->` is expected"))) return false;
+                v.fields.push_back(f);
+                v.el.emplace_back();
+                if (!value(v.el.back())) return false;
+                if (eat("]")) return true;
+                if (!eat(",")) return fail("`,` is expected");
+            }
+        }
+        if (eat("(")) {
+            v.k = PVal::FUN;
+            for (;;) {
+                PVal key;
+                if (!value(key) || key.k != PVal::INT) return fail("a function's key is a number");
+                if (!eat(":>")) return fail("`:>` is expected");
+                v.keys.push_back(key.i);
+                v.el.emplace_back();
+                if (!value(v.el.back())) return false;
+                if (eat(")")) return true;
+                if (!eat("@@")) return fail("`@@` is expected");
+            }
+        }
+        if (*p == '"') {
+            const char *q = strchr(p + 1, '"');
+            if (!q) return fail("an unterminated string");
+            v.k = PVal::STR;
+            v.s.assign(p + 1, q);
+            p = q + 1;
+            return true;
+        }
+        if (*p == '-' || isdigit((unsigned char)*p)) {
+            char *q;
+            v.k = PVal::INT;
+            v.i = strtoll(p, &q, 10);
+            if (q == p || (q == p + 1 && *p == '-')) return fail("a number is expected");
+            p = q;
+            return true;
+        }
+        std::string w;
+        if (!ident(w)) return false;
+        if (w == "TRUE" || w == "FALSE") { v.k = PVal::BOOL; v.i = w == "TRUE"; return true; }
+        if (w == "defaultInitValue") { v.k = PVal::DEF; return true; }
+        return fail("`" + w + "` is no value");
+    }
+};
+// one cell of type `type` ('i' / 'b' / 's') from a scalar value
+bool cell_of(const pcal::Program &P, char type, const PVal &v, int32_t &out, std::string &err) {
+    if (v.k == PVal::DEF) { out = mc::VM_DEFAULT_INIT; return true; }
+    if (type == 'b' && v.k == PVal::BOOL) { out = (int32_t)v.i; return true; }
+    if (type == 'i' && v.k == PVal::INT && v.i >= INT32_MIN && v.i <= INT32_MAX) { out = (int32_t)v.i; return true; }
+    if (type == 's' && v.k == PVal::STR) {
+        for (size_t k = 0; k < P.strings.size(); ++k) if (P.strings[k] == v.s) { out = (int32_t)k; return true; }
+        err = "the program knows no string \"" + v.s + "\"";
+        return false;
+    }
+    err = std::string("a value of the wrong kind where ") + (type == 'b' ? "a boolean" : type == 's' ? "a string" : "a number") + " is expected";
+    return false;
+}
+}  // namespace
+
+// vals[]: the program's cells, zero on entry; returns "" or what is wrong with `text`
+static std::string parse_state_text(const pcal::Program &P, const char *text, std::vector<int32_t> &vals, std::vector<uint8_t> &mask) {
+    PParser ps{text, ""};
+    for (;;) {
+        ps.ws();
+        if (!*ps.p) return "";
+        std::string name;
+        if (!ps.eat("/\\")) return "`/\\ variable = value` is expected at `" + std::string(ps.p).substr(0, 20) + "`";
+        if (!ps.ident(name) || !(ps.eat("=") || ps.fail("`=` is expected"))) return ps.err;
+        const pcal::VarInfo *vi = nullptr;
+        for (const auto &v : P.vars) if (v.name == name) vi = &v;
+        if (!vi) return "the program has no variable `" + name + "`";
+        const pcal::VarInfo &v = *vi;
+        PVal val;
+        if (!ps.value(val)) return name + ": " + ps.err;
+        std::string err;
+        auto seq_to = [&](const PVal &x, int base) {
+            if (x.k != PVal::SEQ || (int)x.el.size() > v.cap) { err = "a sequence of at most " + std::to_string(v.cap) + " elements is expected"; return false; }
+            vals[(size_t)base] = (int32_t)x.el.size();
+            for (size_t k = 0; k < x.el.size(); ++k) if (!cell_of(P, v.type, x.el[k], vals[(size_t)base + 1 + k], err)) return false;
+            return true;
+        };
+        auto one = [&](const PVal &x, int k) {   // element k of the array (or the variable itself)
+            if (v.seq) return seq_to(x, v.base + k * (v.cap + 1));
+            if (!v.set) return cell_of(P, v.type, x, vals[(size_t)(v.base + k)], err);
+            if (x.k != PVal::SET) { err = "a set is expected"; return false; }
+            uint32_t m = 0;
+            for (const auto &e : x.el) {
+                int32_t b = 0;
+                if (!cell_of(P, v.type == 'b' ? 'i' : v.type, e, b, err)) return false;
+                if (b < 0 || b > 31) { err = "a set element outside 0..31"; return false; }
+                m |= 1u << b;
+            }
+            vals[(size_t)(v.base + k)] = (int32_t)m;
+            return true;
+        };
+        bool ok = true;
+        if (v.rset) {
+            if (val.k != PVal::SET || (int)val.el.size() > v.cap) ok = false, err = "a set of at most " + std::to_string(v.cap) + " records is expected";
+            std::vector<std::vector<int32_t>> rows;
+            for (size_t i = 0; ok && i < val.el.size(); ++i) {
+                const PVal &r = val.el[i];
+                std::vector<int32_t> row(v.fields.size());
+                if (r.k != PVal::REC || r.fields.size() != v.fields.size()) { ok = false; err = "a record of " + std::to_string(v.fields.size()) + " fields is expected"; break; }
+                for (size_t f = 0; ok && f < v.fields.size(); ++f) {
+                    size_t at = 0;
+                    while (at < r.fields.size() && r.fields[at] != v.fields[f]) ++at;
+                    if (at == r.fields.size()) { ok = false; err = "the record has no field `" + v.fields[f] + "`"; break; }
+                    ok = cell_of(P, v.ftypes[f], r.el[at], row[f], err);
+                }
+                rows.push_back(row);
+            }
+            if (ok) {   // the stored order: ascending by cells, no duplicates (spec_vm.h VM_RSADD)
+                std::sort(rows.begin(), rows.end());
+                rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+                vals[(size_t)v.base] = (int32_t)rows.size();
+                for (size_t i = 0; i < rows.size(); ++i)
+                    for (size_t f = 0; f < v.fields.size(); ++f) vals[(size_t)v.base + 1 + f * (size_t)v.cap + i] = rows[i][f];
+            }
+        } else if (!v.array) ok = one(val, 0);
+        else if (val.k == PVal::SEQ) {   // a function over 1..n prints as a tuple
+            if (val.el.size() != v.ids.size()) ok = false, err = "a tuple of " + std::to_string(v.ids.size()) + " elements is expected";
+            for (size_t j = 0; ok && j < val.el.size(); ++j) {
+                size_t k = 0;
+                while (k < v.ids.size() && v.ids[k] != (long long)j + 1) ++k;
+                if (k == v.ids.size()) ok = false, err = "the variable's domain is not 1..n";
+                else ok = one(val.el[j], (int)k);
+            }
+        } else if (val.k == PVal::FUN) {
+            if (val.keys.size() != v.ids.size()) ok = false, err = "a function over " + std::to_string(v.ids.size()) + " keys is expected";
+            for (size_t j = 0; ok && j < val.keys.size(); ++j) {
+                size_t k = 0;
+                while (k < v.ids.size() && v.ids[k] != val.keys[j]) ++k;
+                if (k == v.ids.size()) ok = false, err = "key " + std::to_string(val.keys[j]) + " is outside the variable's domain";
+                else ok = one(val.el[j], (int)k);
+            }
+        } else ok = false, err = "a function is expected";
+        if (!ok) return name + ": " + err;
+        int first, stop;
+        var_cells(P, v, first, stop);
+        mask_cells(mask.data(), first, stop);
+    }
+}
+int mc_state_parse(const mc_spec_desc *spec, const char *text, uint8_t *row_out, uint8_t *mask_out) {
+    if (!spec || !text || !row_out) return MC_EBADCFG;
+    if (spec->spec_id != MC_SPEC_PCAL || spec->nparams < 1 || !spec->params[0])
+    {
+        mc_set_error_internal("mc_state_parse: only the rows of a compiled PlusCal program (MC_SPEC_PCAL) have a text parser");
+        return MC_ENOSPEC;
+    }
+    const pcal::Program &P = ((const mc_program *)(intptr_t)spec->params[0])->prog;
+    const size_t bytes = (size_t)((P.nv + 1) / 2) * 8;
+    std::vector<int32_t> vals(bytes / 4, 0);
+    std::vector<uint8_t> mask(bytes, 0);
+    const std::string err = parse_state_text(P, text, vals, mask);
+    if (!err.empty()) { mc_set_error_internal(("mc_state_parse: " + err).c_str()); return MC_EPARSE; }
+    memcpy(row_out, vals.data(), bytes);
+    if (mask_out) memcpy(mask_out, mask.data(), bytes);
+    return MC_OK;
 }
 const char *mc_program_view(const mc_program *p) { return p && !p->prog.view_text.empty() ? p->prog.view_text.c_str() : nullptr; }
 const char *mc_program_action_constraint(const mc_program *p, int index) {
@@ -1918,6 +2168,121 @@ int mc_simulate_files(const char *tla_path, const char *cfg_path, const mc_confi
     o.put("The number of states generated: %llu\n", (unsigned long long)res->generated);
     o.put("Simulation using seed %llu: %llu walks completed, %llu states checked, the longest walk has %u states.\n",
           (unsigned long long)opts->seed, (unsigned long long)res->walks, (unsigned long long)res->steps, res->max_depth);
+    mc_engine_destroy(e);
+    return MC_OK;
+}
+
+// `mc X.tla -behaviours FILE`: the file's states parsed (mc_state_parse), the batch decided on the GPU (mc_engine_behaviours), the first
+// rejected behaviour explained with a model path up to the observation nothing leads to (mc_engine_behaviour_witness)
+int mc_check_behaviours_files(const char *tla_path, const char *cfg_path, const mc_config *cfg, const char *behaviours_path, const char *observe,
+                              unsigned flags, char *report, size_t report_cap, mc_beh_result *res) {
+    if (!tla_path || !cfg || !behaviours_path || !report || !report_cap || !res) return MC_EBADCFG;
+    report[0] = 0;
+    memset(res, 0, sizeof *res);
+    if (no_behavior_cfg(tla_path, cfg_path)) return fe_fail(MC_ENOSPEC, "%s: -behaviours needs a behaviour spec", tla_path);
+    Resolved R;
+    int rc = resolve_files(tla_path, cfg_path, cfg->flags, R);
+    if (rc == MC_ENOSPEC && !R.module.empty() && !lowered_family(R.module, R.tla))
+        return fe_fail(MC_ENOSPEC, "%s: -behaviours needs a GPU lowering (the module is evaluated on the host)", R.module.c_str());
+    if (rc) return rc;
+    const mc_spec_desc &d = R.d;
+    if (!R.prog || d.spec_id != MC_SPEC_PCAL)
+        return fe_fail(MC_ENOSPEC, "%s: -behaviours reads states as text, which only a compiled PlusCal program can parse (hand lowerings take rows: mc_engine_behaviours)", R.module.c_str());
+    std::ifstream f(behaviours_path, std::ios::binary);
+    if (!f) return fe_fail(MC_EPARSE, "cannot read %s", behaviours_path);
+    const size_t W = mc_state_bytes(&d);
+    std::vector<uint64_t> first(1, 0);
+    std::vector<uint8_t> rows, common(W, 0xff), row(W), mask(W);
+    std::vector<std::string> texts;
+    std::string line, text;
+    size_t lineno = 0, in_beh = 0;
+    auto end_state = [&]() -> int {
+        if (text.empty()) return MC_OK;
+        if (mc_state_parse(&d, text.c_str(), row.data(), mask.data()))
+            return fe_fail(MC_EPARSE, "%s: the state that ends at line %zu (behaviour %zu): %s", behaviours_path, lineno, first.size(), mc_last_error());
+        rows.insert(rows.end(), row.begin(), row.end());
+        for (size_t k = 0; k < W; ++k) common[k] &= mask[k];
+        texts.push_back(text);
+        text.clear();
+        ++in_beh;
+        return MC_OK;
+    };
+    auto end_behaviour = [&]() {
+        if (in_beh) first.push_back(first.back() + in_beh);
+        in_beh = 0;
+    };
+    while (std::getline(f, line)) {
+        ++lineno;
+        while (!line.empty() && isspace((unsigned char)line.back())) line.pop_back();
+        size_t b = 0;
+        while (b < line.size() && isspace((unsigned char)line[b])) ++b;
+        const bool rule = line.size() - b >= 4 && line.find_first_not_of('-', b) == std::string::npos;
+        if (b == line.size() || rule || line.compare(b, 6, "State ") == 0) {   // a blank line, a separator, a "State k: <...>" header
+            if ((rc = end_state())) return rc;
+            if (rule) end_behaviour();
+            continue;
+        }
+        text += line.substr(b) + "\n";
+    }
+    if ((rc = end_state())) return rc;
+    end_behaviour();
+    const uint64_t count = first.size() - 1;
+    if (!count) return fe_fail(MC_EPARSE, "%s holds no state", behaviours_path);
+    if (observe) {
+        if ((rc = mc_program_observe(R.prog, observe, mask.data(), W))) return rc;
+        for (size_t k = 0; k < W; ++k)
+            if (mask[k] & ~common[k]) return fe_fail(MC_EPARSE, "%s: a state does not mention every variable of -observe %s", behaviours_path, observe);
+    } else mask = common;
+    bool any = false;
+    for (uint8_t m : mask) any = any || m;
+    if (!any) return fe_fail(MC_EPARSE, "%s: no variable is mentioned by every state (name the observed ones with -observe)", behaviours_path);
+    mc_config c = *cfg;
+    c.flags &= ~(unsigned)(MC_F_JIT | MC_F_COVERAGE | MC_F_CONTINUE | MC_F_TIMING);
+    c.shard_count = 1;
+    c.shard_rank = 0;
+    mc_engine *e = nullptr;
+    if ((rc = mc_engine_create(&d, &c, &e))) return rc;
+    mc_beh_opts o;
+    memset(&o, 0, sizeof o);
+    o.count = count;
+    o.first = first.data();
+    o.rows = rows.data();
+    o.mask = mask.data();
+    o.flags = flags;
+    std::vector<mc_beh_verdict> v(count);
+    if ((rc = mc_engine_behaviours(e, &o, v.data(), res))) { mc_engine_destroy(e); return rc; }
+    Out out{report, report_cap, 0};
+    if (!R.warning.empty()) out.put("%s", R.warning.c_str());
+    out.put("Checking %llu recorded behaviours (%llu observations) of %s against the model%s.\n", (unsigned long long)count,
+            (unsigned long long)first.back(), behaviours_path, flags & MC_BEH_F_STUTTER ? ", stuttering steps allowed" : "");
+    if (res->ambiguous) {
+        out.put("Warning: %llu behaviours are ambiguous (more than %d states of the model fit the observations; observe more variables), not decided:",
+                (unsigned long long)res->ambiguous, MC_BEH_MAX_CANDIDATES);
+        for (uint64_t b = 0; b < count; ++b) if (v[b].verdict == MC_BEH_AMBIGUOUS) out.put(" %llu (at observation %u)", (unsigned long long)b + 1, v[b].step + 1);
+        out.put("\n");
+    }
+    if (res->first_rejected != ~0ull) {
+        const uint64_t b = res->first_rejected;
+        out.put("Error: Behaviour %llu is not a behaviour of the model: no step leads to observation %u.\n", (unsigned long long)b + 1, v[b].step + 1);
+        size_t n = v[b].step ? v[b].step : 1;
+        std::vector<uint8_t> states(n * W);
+        std::vector<int32_t> slots(n);
+        if (mc_engine_behaviour_witness(e, &o, b, states.data(), slots.data(), &n) == MC_OK && n) {
+            out.put("Error: The behavior of the model up to this point is:\n");
+            std::vector<char> txt(1 << 16);
+            for (size_t k = 0; k < n; ++k) {
+                mc_state_format(&d, &states[k * W], txt.data(), txt.size());
+                if (slots[k] == -1) out.put("State %zu: <Initial predicate>\n%s\n\n", k + 1, txt.data());
+                else if (slots[k] < 0) out.put("State %zu: <Stuttering>\n%s\n\n", k + 1, txt.data());
+                else out.put("State %zu: <Action %s of module %s>\n%s\n\n", k + 1, mc_action_name(&d, mc_state_action(&d, &states[(k - 1) * W], slots[k])),
+                             R.module.c_str(), txt.data());
+            }
+        } else out.put("No initial state of the model matches it.\n");
+        out.put("The observation is:\n%s\n", texts[(size_t)(first[b] + v[b].step)].c_str());
+    }
+    out.put("%llu behaviours checked: %llu accepted, %llu rejected, %llu ambiguous.\n", (unsigned long long)count, (unsigned long long)res->accepted,
+            (unsigned long long)res->rejected, (unsigned long long)res->ambiguous);
+    out.put("The number of states generated: %llu\n", (unsigned long long)res->generated);
     mc_engine_destroy(e);
     return MC_OK;
 }

@@ -7,6 +7,7 @@
 //            [-checkpoint FILE] [-recover FILE] [-gpus P [-samedevice | -torch] [-exchange exact|measured|packed] [-fanout N]] [-noprogress] [-I DIR]
 //            [-coverage [MINUTES]] [-strongfair] [-labelfair] [-continue]
 //   mc X.tla -simulate [num=N] [-depth D] [-seed S] [-config X.cfg] [-deadlock] [-jit] [-device D] [-noprogress] [-I DIR]
+//   mc X.tla -behaviours FILE [-observe v1,v2,...] [-stutter] [-config X.cfg] [-device D] [-I DIR]
 //   mc --transpile X.tla [Y.tla ...]      the `pcal2tla *tla` of the reference's Makefile:3-4: inserts (or
 //                                         replaces) the TLA+ translation of the PlusCal algorithm in place,
 //                                         the previous text is kept as X.old
@@ -50,6 +51,13 @@
 //             depth give the same walks and the same report.  The report has the error and its behaviour as the search's has, "The
 //             number of states generated: G" and the walks, but no distinct-state count or search depth: nothing was searched
 //             exhaustively.  -gpus, -dump, -checkpoint and -recover do not apply; a module without a GPU lowering is refused.
+// -behaviours FILE [-observe v1,v2,...] [-stutter]: is every execution recorded in FILE a behaviour of the model (a PlusCal module)?
+//             FILE holds states as `mc -dump` / a TLC trace prints them ("State k:" headers are ignored), a blank line between states, a
+//             line of ---- between behaviours; a state may leave variables out.  -observe names the variables that count (default: those
+//             every state of the file mentions); -stutter lets an observation repeat the state before it.  One GPU wavefront decides one
+//             behaviour (mc_engine_behaviours).  The report counts the verdicts, names the ambiguous behaviours in a warning, and for
+//             the first rejected one prints a behaviour of the model up to the observation no step leads to.  Exit status 12 if a
+//             behaviour is rejected.  Not with -simulate, -gpus, -recover, -checkpoint, -dump, -coverage or -continue.
 // -continue: TLC's -continue: a violated invariant or a deadlock no longer ends the search (MC_F_CONTINUE).  The report prints the first
 //             error with its behaviour as ever, then one line per invariant of the model (and one for deadlock): the distinct states
 //             that break it — each state under its FIRST violated invariant only —, the violating successors outside the model, the
@@ -354,8 +362,26 @@ static int run_simulation(const char *tla, const char *cfgp, const mc_config &cf
     return res.verdict == MC_V_DEADLOCK ? 11 : 12;
 }
 
+// ---- mc X.tla -behaviours FILE
+static int run_behaviours(const char *tla, const char *cfgp, const mc_config &cfg, const char *file, const char *observe, bool stutter) {
+    std::vector<char> report(1 << 22);
+    mc_beh_result res;
+    const int rc = mc_check_behaviours_files(tla, cfgp, &cfg, file, observe, stutter ? MC_BEH_F_STUTTER : 0u, report.data(), report.size(), &res);
+    if (rc) {
+        fprintf(stderr, "mc: %s: %s\n", mc_strerror(rc), mc_last_error());
+        return 1;
+    }
+    fputs(report.data(), stdout);
+    return res.rejected ? 12 : 0;
+}
+
 int main(int argc, char **argv) {
     setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", 0);   // (RCCL between processes needs dmabuf IPC on this driver; read when the HSA runtime starts)
+    for (int i = 1; i < argc; i++)   // (before anything else looks at the options)
+        if (!strcmp(argv[i], "-behaviours"))
+            for (int j = 1; j < argc; j++)
+                for (const char *other : {"-simulate", "-gpus", "-recover", "-checkpoint", "-dump", "-coverage", "-continue"})
+                    if (!strcmp(argv[j], other)) { fprintf(stderr, "mc: %s is not available with -behaviours\n", other); return 1; }
     int gpus = 0;
     bool torch_door = false;
     for (int i = 1; i < argc; i++) {
@@ -397,7 +423,8 @@ int main(int argc, char **argv) {
     }
     const char *tla = nullptr, *cfgp = nullptr, *dump = nullptr, *recover = nullptr, *ckpt = nullptr, *dot = nullptr;
     unsigned dot_flags = 0;
-    bool simulate = false, have_seed = false, have_depth = false;
+    bool simulate = false, have_seed = false, have_depth = false, stutter = false;
+    const char *beh_file = nullptr, *observe = nullptr;
     mc_sim_opts sim;
     memset(&sim, 0, sizeof sim);
     sim.depth = 100;   // TLC's default -depth
@@ -434,6 +461,9 @@ int main(int argc, char **argv) {
             if (i + 1 < argc && parse_u64(argv[i + 1], &minutes)) ++i;
         }
         else if (!strcmp(argv[i], "-continue")) cfg.flags |= MC_F_CONTINUE;
+        else if (arg("-behaviours")) beh_file = argv[++i];
+        else if (arg("-observe")) observe = argv[++i];
+        else if (!strcmp(argv[i], "-stutter")) stutter = true;
         else if (!strcmp(argv[i], "-deadlock")) cfg.flags &= ~MC_F_DEADLOCK;
         else if (arg("-dump") && (!strcmp(argv[i + 1], "dot") || !strncmp(argv[i + 1], "dot,", 4))) {   // TLC: -dump dot[,actionlabels][,colorize] FILE
             for (const char *s = argv[++i] + 3; *s;) {
@@ -510,11 +540,19 @@ int main(int argc, char **argv) {
                 "                that is depends on the order of arrival within a level, and the counts may differ from run to run; a temporal\n"
                 "                property under a VIEW is named as NOT checked\n"
                 "       mc X.tla -simulate [num=N] [-depth D] [-seed S] [...]                             random walks like `tlc -simulate`\n"
+                "       mc X.tla -behaviours FILE [-observe v1,v2,...] [-stutter]                         is every execution recorded in FILE a behaviour of the model?\n"
                 "       mc --transpile X.tla [Y.tla ...]                                                  translate like `pcal2tla`\n"
                 "exit status: 0 no error, 12 invariant / assertion violated, 11 deadlock, 13 a temporal property violated, 1 anything else\n");
         return 1;
     }
     if (!simulate && (have_depth || have_seed)) { fprintf(stderr, "mc: %s needs -simulate\n", have_depth ? "-depth" : "-seed"); return 1; }
+    if (!beh_file && (observe || stutter)) { fprintf(stderr, "mc: %s needs -behaviours\n", observe ? "-observe" : "-stutter"); return 1; }
+    if (beh_file) {
+        cfg.flags &= ~(unsigned)MC_F_PROGRESS;
+        cfg.table_capacity = 1ull << 16;   // (no search runs: the seen-set and the arena stay empty)
+        cfg.arena_capacity = 1ull << 14;
+        return run_behaviours(tla, cfgp, cfg, beh_file, observe, stutter);
+    }
     if (simulate) return run_simulation(tla, cfgp, cfg, sim, have_seed, dump || dot ? "-dump" : ckpt ? "-checkpoint" : recover ? "-recover" : nullptr);
     if (gpus) {  // one rank of `mc X.tla -gpus P`
         if (dump || dot) { fprintf(stderr, "mc: -dump is not available with -gpus\n"); return 1; }
