@@ -20,10 +20,12 @@ SOURCES = ["engine.hip", "frontend.cpp"]
 ENGINE_BASE = ["engine.hip", "hip_owned.h", "engine_kernels.h", "engine_sim.h", "sim_walk.h", "engine_behaviours.h", "behaviour.h", "engine_coverage.h", "coverage.h", "engine_violations.h", "violations.h",
                "engine_graph.h",
                "graph.h", "liveness.h", "live_query.h", "state_graph.h", "spec_gen.h", "mc_common.h", "spec_registry.h", "../../include/tlamc.h"]
-ENGINE_OWN = {0: ["spec_pluscal.h", "spec_raft.h", "spec_ssi.h", "spec_vm.h", "spec_vm_cfg.h", "spec_paxos.h", "engine_pairs.h"], 7: ["spec_paxos.h"], 1: ["spec_pluscal.h"],
-              2: ["spec_raft.h"], 3: ["spec_raft.h"], 4: ["spec_raft.h"], 5: ["spec_ssi.h", "engine_pairs.h"], 6: ["spec_vm.h", "spec_vm_cfg.h"]}
+ENGINE_OWN = {0: ["spec_pluscal.h", "spec_raft.h", "spec_raft_packed.h", "spec_ssi.h", "spec_vm.h", "spec_vm_cfg.h", "spec_paxos.h", "engine_pairs.h"], 7: ["spec_paxos.h"], 1: ["spec_pluscal.h"],
+              2: ["spec_raft.h"], 3: ["spec_raft.h"], 4: ["spec_raft.h"], 5: ["spec_ssi.h", "engine_pairs.h"], 6: ["spec_vm.h", "spec_vm_cfg.h"],
+              # raft with 2 / 3 servers over packed rows (spec_raft_packed.h): one unit per instantiation (9 is the unit of generated code, built at load time)
+              12: ["spec_raft.h", "spec_raft_packed.h"], 13: ["spec_raft.h", "spec_raft_packed.h"]}
 STATE_GRAPH_DEPS = ["state_graph.hip", "state_graph.h", "engine_live.h", "hip_owned.h", "liveness.h", "live_query.h", "graph.h", "coverage.h", "mc_common.h", "spec_registry.h",
-                    "spec_gen.h", "spec_pluscal.h", "spec_raft.h", "spec_ssi.h", "spec_vm.h", "spec_vm_cfg.h", "spec_paxos.h", "../../include/tlamc.h"]
+                    "spec_gen.h", "spec_pluscal.h", "spec_raft.h", "spec_raft_packed.h", "spec_ssi.h", "spec_vm.h", "spec_vm_cfg.h", "spec_paxos.h", "../../include/tlamc.h"]
 
 
 def _stale(target, deps):
@@ -50,7 +52,7 @@ def build(force=False, verbose=False):
     if os.environ.get("TLAMC_PHASE_PROF"):   # per-phase cycle counters inside k_expand_family (profiles/phase_prof.py): a profiling build
         common.append("-DMC_PHASE_PROF")
     jobs, objs = [], []
-    for tu in range(8):
+    for tu in sorted(ENGINE_OWN):
         obj = OUT / f"engine_tu{tu}.o"
         objs.append(obj)
         if force or _stale(obj, [CSRC / h for h in ENGINE_BASE + ENGINE_OWN[tu]]):

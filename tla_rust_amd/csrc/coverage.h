@@ -67,6 +67,17 @@ struct CovAction<SpecRaft<N>> {
         return action;
     }
 };
+template <int N>
+struct CovAction<SpecRaftPacked<N>> : CovAction<SpecRaft<N>> {   // (spec_raft_packed.h: its compute() reads the stored row through the view)
+    using S = SpecRaftPacked<N>;
+    template <class Ref>
+    MC_HD static int of(const RaftParams &p, const typename S::Local &l, Ref s, int slot) {
+        typename S::Delta d;
+        int action = -1;
+        S::compute(p, l, s, slot, d, action);
+        return action;
+    }
+};
 template <>
 struct CovAction<SpecSsi> {
     static constexpr bool BY_SLOT = false;

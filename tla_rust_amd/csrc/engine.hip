@@ -110,6 +110,8 @@ struct EngineBase {
     virtual int shard_checkpoint(const char *path) = 0;
     virtual int shard_restore(const char *path) = 0;
     virtual size_t state_bytes() const = 0;
+    virtual int narrow_rows() const = 0;
+    mc_config created_with;   // make_engine: what mc_engine_create was given (an engine is made again from it: shard_side)
     virtual int simulate(const mc_sim_opts *opts, mc_sim_result *out) = 0;
     virtual int behaviours(const mc_beh_opts *opts, mc_beh_verdict *out, mc_beh_result *result) = 0;
     virtual int behaviours_refused() = 0;   // MC_OK, or why this engine checks no behaviours (mc_last_error says it)
@@ -178,6 +180,17 @@ template <class S, class = void>
 struct HasExport : std::false_type {};
 template <class S>
 struct HasExport<S, decltype((void)S::EXPORT_WORDS)> : std::true_type {};
+// ... with a public width that depends on the model's constants, and rows that come IN through S::import_row (spec_raft_packed.h)
+template <class S, class = void>
+struct RaftPacked : std::false_type {};
+template <class S>
+struct RaftPacked<S, decltype((void)S::RAFT_PACKED)> : std::true_type {};
+template <class S>
+static size_t export_words_of(const typename S::Params &prm, int W) {
+    if constexpr (RaftPacked<S>::value) return (size_t)S::export_words(prm);
+    else if constexpr (HasExport<S>::value) return (size_t)S::EXPORT_WORDS;
+    else return (size_t)W;
+}
 template <class S, class = void>
 struct PackedRows : std::false_type {};
 template <class S>
@@ -1449,8 +1462,8 @@ struct Engine : EngineBase {
     int trace_out(const std::vector<uint64_t> &words, const std::vector<int32_t> &acts, uint8_t *states_out, int32_t *actions_out, size_t *n_inout) {
         const size_t n = acts.size();
         if (n > *n_inout) { *n_inout = n; set_error("trace buffer too small"); return MC_EBADCFG; }
-        if constexpr (HasExport<S>::value) {  // rows leave the engine in the spec's PUBLIC layout (generated code: the interpreter's row)
-            for (size_t k = 0; k < n; ++k) S::export_row(prm, &words[k * W], (uint64_t *)states_out + k * (size_t)S::EXPORT_WORDS);
+        if constexpr (HasExport<S>::value || RaftPacked<S>::value) {  // rows leave the engine in the spec's PUBLIC layout (generated code: the interpreter's row)
+            for (size_t k = 0; k < n; ++k) S::export_row(prm, &words[k * W], (uint64_t *)states_out + k * export_words_of<S>(prm, W));
         } else
         memcpy(states_out, words.data(), n * W * sizeof(uint64_t));
         memcpy(actions_out, acts.data(), n * sizeof(int32_t));
@@ -1468,12 +1481,12 @@ struct Engine : EngineBase {
             const uint64_t n = count - off < piece ? count - off : piece;
             hipLaunchKernelGGL(k_gather_states, dim3((unsigned)((n * W + 255) / 256)), dim3(256), 0, stream, d_arena, W, first + off, n, tmp);
             hipError_t e1, e2;
-            if constexpr (HasExport<S>::value) {
+            if constexpr (HasExport<S>::value || RaftPacked<S>::value) {
                 std::vector<uint64_t> rows((size_t)n * W);
                 e1 = hipMemcpyAsync(rows.data(), tmp, n * W * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
                 e2 = hipStreamSynchronize(stream);
                 if (e1 == hipSuccess && e2 == hipSuccess)
-                    for (uint64_t k = 0; k < n; ++k) S::export_row(prm, &rows[(size_t)k * W], (uint64_t *)out + (size_t)(off + k) * (size_t)S::EXPORT_WORDS);
+                    for (uint64_t k = 0; k < n; ++k) S::export_row(prm, &rows[(size_t)k * W], (uint64_t *)out + (size_t)(off + k) * export_words_of<S>(prm, W));
             } else {
                 e1 = hipMemcpyAsync(out + off * W * sizeof(uint64_t), tmp, n * W * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
                 e2 = hipStreamSynchronize(stream);
@@ -1548,7 +1561,14 @@ struct Engine : EngineBase {
     // generated code with packed rows serves one GPU: its rows cannot travel between ranks
     static int refuse_packed() {
         if constexpr (PackedRows<S>::value) { set_error("this engine of generated code stores rows packed to its program's cell ranges and serves ONE GPU: create a sharded engine with shard_count > 1 (or $TLAMC_JIT_PACK=0)"); return MC_EBADCFG; }
+        // (a raft engine that has not searched yet never gets here: the mc_shard_* entries re-create it with the rows the step calls exchange)
+        if constexpr (RaftPacked<S>::value) { set_error("this raft engine has searched with its rows stored in fewer words (one GPU) and cannot go on in sharded steps: create the engine with shard_count > 1, make the mc_shard_* call before the first search, or set $TLAMC_RAFT_PACK=0"); return MC_EBADCFG; }
         return MC_OK;
+    }
+    // 0: the engine stores the rows the C ABI hands out; 1: narrower ones, and nothing has been searched, restored or simulated yet; 2: narrower ones, in use
+    int narrow_rows() const override {
+        if constexpr (!RaftPacked<S>::value) return 0;
+        return !fr.have_run && !ck.pending && !sim.trace_n && fr.last_distinct == 0 ? 1 : 2;
     }
     // a sharded run that failed mid-level (a full route bucket, MC_ETABLEFULL ...) leaves its slots as they were: the remedy the
     // error message names — run the same engine again with a larger allowance — must not trip over an expand "still in flight"
@@ -2162,8 +2182,8 @@ struct Engine : EngineBase {
     int sim_trace_out(uint8_t *states_out, int32_t *actions_out, size_t *n_inout) {
         const size_t n = sim.trace_n;
         if (n > *n_inout) { *n_inout = n; set_error("trace buffer too small"); return MC_EBADCFG; }
-        if constexpr (HasExport<S>::value) {  // rows leave the engine in the spec's PUBLIC layout, as the BFS's traces do
-            for (size_t k = 0; k < n; ++k) S::export_row(prm, &sim.trace_rows[k * W], (uint64_t *)states_out + k * (size_t)S::EXPORT_WORDS);
+        if constexpr (HasExport<S>::value || RaftPacked<S>::value) {  // rows leave the engine in the spec's PUBLIC layout, as the BFS's traces do
+            for (size_t k = 0; k < n; ++k) S::export_row(prm, &sim.trace_rows[k * W], (uint64_t *)states_out + k * export_words_of<S>(prm, W));
         } else
         memcpy(states_out, sim.trace_rows.data(), n * W * sizeof(uint64_t));
         memcpy(actions_out, sim.trace_acts.data(), n * sizeof(int32_t));
@@ -2204,9 +2224,16 @@ struct Engine : EngineBase {
         struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{stream};
         const uint32_t iters = o->iters ? o->iters : BEH_ITERS;
         const uint64_t R = chunk / 64 < o->count ? chunk / 64 : o->count;   // (chunk >= 256)
-        std::vector<uint64_t> hmask(W, ~0ull);
-        if (o->mask) memcpy(hmask.data(), o->mask, (size_t)W * sizeof(uint64_t));
-        const bool full = beh_mask_full(hmask.data(), W);
+        // observations and the mask arrive in the PUBLIC layout; a lowering that stores narrower rows takes them through import_row
+        const size_t PW = export_words_of<S>(prm, W);
+        std::vector<uint64_t> hmask(PW, ~0ull), imported;
+        if (o->mask) memcpy(hmask.data(), o->mask, PW * sizeof(uint64_t));
+        const bool full = beh_mask_full(hmask.data(), (int)PW);
+        if constexpr (RaftPacked<S>::value) {
+            std::vector<uint64_t> pm(hmask);
+            hmask.assign(W, 0);
+            S::import_row(prm, pm.data(), hmask.data());
+        }
         for (int k = 0; k < 2; ++k) HIP_TRY(beh.set[k].reserve(R * 64 * W));
         HIP_TRY(beh.stage.reserve(R * 64 * W));
         HIP_TRY(beh.first.reserve(R + 1));
@@ -2236,6 +2263,11 @@ struct Engine : EngineBase {
             for (uint64_t k = 0; k <= n; ++k) rel[k] = o->first[b0 + k] - r0;
             for (uint64_t k = 0; k < n; ++k) longest = std::max(longest, rel[k + 1] - rel[k]);
             HIP_TRY(beh.rows.reserve(nrows * W));
+            if constexpr (RaftPacked<S>::value) {
+                imported.resize(nrows * W);   // (read by the copy until the round's synchronisation below)
+                for (uint64_t k = 0; k < nrows; ++k) S::import_row(prm, (const uint64_t *)o->rows + (r0 + k) * PW, &imported[k * W]);
+                HIP_TRY(hipMemcpyAsync(beh.rows, imported.data(), nrows * W * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+            } else
             HIP_TRY(hipMemcpyAsync(beh.rows, o->rows + r0 * W * sizeof(uint64_t), nrows * W * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
             HIP_TRY(hipMemcpyAsync(beh.first, rel.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
             HIP_TRY(hipMemsetAsync(beh.carry, 0, n * sizeof(uint64_t), stream));
@@ -2302,6 +2334,7 @@ static int make_engine(const typename S::Params &prm, const mc_spec_desc *spec, 
     e->prm = prm;
     e->desc = *spec;
     e->cfg = *cfg;
+    e->created_with = *cfg;
     const int r = e->alloc();
     if (r) { delete e; return r; }
     *out = e;
@@ -2316,6 +2349,8 @@ int mc_make_engine_4(const mc_spec_desc *, const mc_config *, mc::EngineBase **)
 int mc_make_engine_5(const mc_spec_desc *, const mc_config *, mc::EngineBase **);
 int mc_make_engine_6(const mc_spec_desc *, const mc_config *, mc::EngineBase **);
 int mc_make_engine_7(const mc_spec_desc *, const mc_config *, mc::EngineBase **);
+int mc_make_engine_2p(const mc_spec_desc *, const mc_config *, mc::EngineBase **);   // raft with 2 / 3 servers over narrower stored rows (spec_raft_packed.h)
+int mc_make_engine_3p(const mc_spec_desc *, const mc_config *, mc::EngineBase **);
 void *mc_jit_factory_opts(const void *program, int pack);   // pcal_codegen.cpp: the factory of the engine library built from the program's generated code, or null
 #if MC_TU == 1 || MC_TU == -1
 int mc_make_engine_1(const mc_spec_desc *d, const mc_config *c, mc::EngineBase **out) {
@@ -2343,6 +2378,20 @@ MC_RAFT_FACTORY(3, SpecRaft3)
 #endif
 #if MC_TU == 4 || MC_TU == -1
 MC_RAFT_FACTORY(4, SpecRaft5)
+#endif
+// ... over the packed rows: units of their own (the by-family kernels are instantiated once more)
+#define MC_RAFT_PACKED_FACTORY(K, NSRV)                                                            \
+    int mc_make_engine_##K##p(const mc_spec_desc *d, const mc_config *c, mc::EngineBase **out) {   \
+        mc::RaftParams p;                                                                          \
+        if (mc::SpecRaftPacked<NSRV>::make_params(d->params, d->nparams, p)) return MC_EBADCFG;    \
+        if (!mc::SpecRaftPacked<NSRV>::packable(p) || c->shard_count > 1) return MC_EBADCFG;       \
+        return mc::make_engine<mc::SpecRaftPacked<NSRV>>(p, d, c, out);                            \
+    }
+#if MC_TU == 12 || MC_TU == -1
+MC_RAFT_PACKED_FACTORY(2, 2)
+#endif
+#if MC_TU == 13 || MC_TU == -1
+MC_RAFT_PACKED_FACTORY(3, 3)
 #endif
 #if MC_TU == 5 || MC_TU == -1
 int mc_make_engine_5(const mc_spec_desc *d, const mc_config *c, mc::EngineBase **out) {
@@ -2424,6 +2473,36 @@ struct mc_engine {
     EngineBase *impl;
 };
 
+// raft on ONE GPU stores its rows in fewer words where the model's constants let it (spec_raft_packed.h); $TLAMC_RAFT_PACK=0 = A/B: the rows of
+// every other engine.  Engines of a sharded job (shard_count > 1) exchange rows between ranks and keep the public layout (include/tlamc.h).
+static bool raft_rows_packed(const mc_spec_desc *spec, const mc_config *cfg) {
+    const char *ep = getenv("TLAMC_RAFT_PACK");
+    if ((ep && *ep == '0') || cfg->shard_count > 1 || spec->spec_id != MC_SPEC_RAFT || spec->nparams < 5) return false;
+    RaftParams p;
+    if (spec->params[0] == 2) return !SpecRaft2::make_params(spec->params, spec->nparams, p) && SpecRaftPacked<2>::packable(p);
+    if (spec->params[0] == 3) return !SpecRaft3::make_params(spec->params, spec->nparams, p) && SpecRaftPacked<3>::packable(p);
+    return false;
+}
+static int make_impl(const mc_spec_desc *spec, const mc_config *cfg, bool pack, EngineBase **impl);
+// The engine the mc_shard_* calls act on.  A one-GPU raft engine that stores narrow rows and has not searched yet is made again with the
+// rows the step calls exchange, behind its handle; one that has searched refuses the call (Engine::refuse_packed).
+static EngineBase *shard_side(mc_engine *e) {
+    if (e->impl->narrow_rows() != 1) return e->impl;
+    const mc_spec_desc desc = *e->impl->spec_desc();
+    const mc_config cfg = e->impl->created_with;
+    mc_progress_fn fn = e->impl->progress_fn;
+    void *user = e->impl->progress_user;
+    const double interval = e->impl->progress_interval;
+    EngineBase *impl = nullptr;
+    if (make_impl(&desc, &cfg, false, &impl) != MC_OK) return e->impl;   // (no room for both for a moment: the call is refused, Engine::refuse_packed says how to go on)
+    delete e->impl;
+    impl->progress_fn = fn;
+    impl->progress_user = user;
+    impl->progress_interval = interval;
+    e->impl = impl;
+    return impl;
+}
+
 extern "C" {
 
 int mc_device_count(void) {
@@ -2451,12 +2530,20 @@ int mc_engine_create(const mc_spec_desc *spec, const mc_config *cfg, mc_engine *
         cfg = &with_trace;
     }
     EngineBase *impl = nullptr;
+    const int rc = make_impl(spec, cfg, raft_rows_packed(spec, cfg), &impl);
+    if (rc == MC_OK) *out = new mc_engine{impl};
+    else if (rc == MC_EBADCFG && g_last_error.empty()) set_error("unknown spec id or constants out of range");
+    return rc;
+}
+}  // extern "C"
+static int make_impl(const mc_spec_desc *spec, const mc_config *cfg, bool pack, EngineBase **out) {
+    EngineBase *impl = nullptr;
     const int group = spec_group(spec);
     int rc = MC_EBADCFG;
     switch (group) {
     case 1: rc = mc_make_engine_1(spec, cfg, &impl); break;
-    case 2: rc = mc_make_engine_2(spec, cfg, &impl); break;
-    case 3: rc = mc_make_engine_3(spec, cfg, &impl); break;
+    case 2: rc = pack ? mc_make_engine_2p(spec, cfg, &impl) : mc_make_engine_2(spec, cfg, &impl); break;
+    case 3: rc = pack ? mc_make_engine_3p(spec, cfg, &impl) : mc_make_engine_3(spec, cfg, &impl); break;
     case 4: rc = mc_make_engine_4(spec, cfg, &impl); break;
     case 5: rc = mc_make_engine_5(spec, cfg, &impl); break;
     case 6: {
@@ -2478,10 +2565,10 @@ int mc_engine_create(const mc_spec_desc *spec, const mc_config *cfg, mc_engine *
     case 7: rc = mc_make_engine_7(spec, cfg, &impl); break;
     default: break;
     }
-    if (rc == MC_OK) *out = new mc_engine{impl};
-    else if (rc == MC_EBADCFG && g_last_error.empty()) set_error("unknown spec id or constants out of range");
+    if (rc == MC_OK) *out = impl;
     return rc;
 }
+extern "C" {
 int mc_engine_run(mc_engine *e, mc_result *out) { return e && out ? e->impl->run(out) : MC_EBADCFG; }
 int mc_engine_step(mc_engine *e, uint32_t levels, mc_result *out) { return e && out ? e->impl->step(levels, out) : MC_EBADCFG; }
 int mc_engine_set_progress(mc_engine *e, mc_progress_fn fn, void *user, double min_interval_seconds) {
@@ -2678,69 +2765,69 @@ int mc_engine_debug_phases(mc_engine *e, uint64_t *out48, int reset) { return e 
 int mc_engine_debug_flags(mc_engine *e, uint32_t set, uint32_t clear) { return e ? e->impl->debug_flags(set, clear) : MC_EBADCFG; }
 int mc_engine_seen_layout(mc_engine *e, uint64_t *buckets, uint32_t *slots) { return e && buckets && slots ? e->impl->seen_layout(buckets, slots) : MC_EBADCFG; }
 // ---- sharded (multi-GPU) step API
-int mc_shard_begin(mc_engine *e) { return e ? e->impl->shard_begin() : MC_EBADCFG; }
+int mc_shard_begin(mc_engine *e) { return e ? shard_side(e)->shard_begin() : MC_EBADCFG; }
 int mc_shard_begin_replicated(mc_engine *e, uint64_t min_frontier, uint64_t max_distinct, uint64_t max_levels, uint64_t *levels_out,
                               uint32_t *nlevels) {
-    return e && levels_out && nlevels ? e->impl->shard_begin_replicated(min_frontier, max_distinct, max_levels, levels_out, nlevels) : MC_EBADCFG;
+    return e && levels_out && nlevels ? shard_side(e)->shard_begin_replicated(min_frontier, max_distinct, max_levels, levels_out, nlevels) : MC_EBADCFG;
 }
-int mc_shard_level_size(mc_engine *e, uint64_t *n) { return e && n ? e->impl->shard_level_size(n) : MC_EBADCFG; }
+int mc_shard_level_size(mc_engine *e, uint64_t *n) { return e && n ? shard_side(e)->shard_level_size(n) : MC_EBADCFG; }
 int mc_shard_info(mc_engine *e, void **main_stream_out, uint64_t *chunk_states_out, int32_t *traced_out) {
-    return e ? e->impl->shard_info(main_stream_out, chunk_states_out, traced_out) : MC_EBADCFG;
+    return e ? shard_side(e)->shard_info(main_stream_out, chunk_states_out, traced_out) : MC_EBADCFG;
 }
-size_t mc_engine_state_bytes_internal(mc_engine *e) { return e ? e->impl->state_bytes() : 0; }
+size_t mc_engine_state_bytes_internal(mc_engine *e) { return e ? shard_side(e)->state_bytes() : 0; }
 int mc_shard_expand(mc_engine *e, uint64_t first, uint64_t count, uint64_t *send_fp, uint64_t send_cap, uint64_t *send_counts) {
     if (!e || !send_counts) return MC_EBADCFG;
-    const int rc = e->impl->shard_expand_launch(0, first, count, send_cap);
-    return rc ? rc : e->impl->shard_expand_finish(0, send_fp, send_cap, send_counts);
+    const int rc = shard_side(e)->shard_expand_launch(0, first, count, send_cap);
+    return rc ? rc : shard_side(e)->shard_expand_finish(0, send_fp, send_cap, send_counts);
 }
-int mc_shard_set_stream(mc_engine *e, void *hip_stream, int enable) { return e ? e->impl->shard_set_stream(hip_stream, enable) : MC_EBADCFG; }
+int mc_shard_set_stream(mc_engine *e, void *hip_stream, int enable) { return e ? shard_side(e)->shard_set_stream(hip_stream, enable) : MC_EBADCFG; }
 int mc_shard_expand_launch(mc_engine *e, uint32_t slot, uint64_t first, uint64_t count, uint64_t send_cap) {
-    return e ? e->impl->shard_expand_launch(slot, first, count, send_cap) : MC_EBADCFG;
+    return e ? shard_side(e)->shard_expand_launch(slot, first, count, send_cap) : MC_EBADCFG;
 }
 int mc_shard_expand_finish(mc_engine *e, uint32_t slot, uint64_t *send_fp, uint64_t send_cap, uint64_t *send_counts) {
-    return e && send_counts ? e->impl->shard_expand_finish(slot, send_fp, send_cap, send_counts) : MC_EBADCFG;
+    return e && send_counts ? shard_side(e)->shard_expand_finish(slot, send_fp, send_cap, send_counts) : MC_EBADCFG;
 }
 int mc_shard_probe(mc_engine *e, const uint64_t *recv_fp, uint64_t n, uint8_t *answers) {
-    return e ? e->impl->shard_probe(recv_fp, n, answers) : MC_EBADCFG;
+    return e ? shard_side(e)->shard_probe(recv_fp, n, answers) : MC_EBADCFG;
 }
 int mc_shard_materialise(mc_engine *e, const uint8_t *answers_back, uint8_t *send_states, uint64_t send_cap, uint64_t *send_counts) {
-    return e && send_counts ? e->impl->shard_materialise(0, answers_back, send_states, send_cap, send_counts) : MC_EBADCFG;
+    return e && send_counts ? shard_side(e)->shard_materialise(0, answers_back, send_states, send_cap, send_counts) : MC_EBADCFG;
 }
 int mc_shard_materialise_slot(mc_engine *e, uint32_t slot, const uint8_t *answers_back, uint8_t *send_states, uint64_t send_cap,
                               uint64_t *send_counts) {
-    return e && send_counts ? e->impl->shard_materialise(slot, answers_back, send_states, send_cap, send_counts) : MC_EBADCFG;
+    return e && send_counts ? shard_side(e)->shard_materialise(slot, answers_back, send_states, send_cap, send_counts) : MC_EBADCFG;
 }
-int mc_shard_ingest(mc_engine *e, const uint8_t *recv_states, uint64_t n) { return e ? e->impl->shard_ingest(recv_states, n) : MC_EBADCFG; }
-int mc_shard_expand_pack(mc_engine *e, uint32_t slot, uint64_t *send_fp, uint64_t cap) { return e && send_fp ? e->impl->shard_expand_pack(slot, send_fp, cap) : MC_EBADCFG; }
+int mc_shard_ingest(mc_engine *e, const uint8_t *recv_states, uint64_t n) { return e ? shard_side(e)->shard_ingest(recv_states, n) : MC_EBADCFG; }
+int mc_shard_expand_pack(mc_engine *e, uint32_t slot, uint64_t *send_fp, uint64_t cap) { return e && send_fp ? shard_side(e)->shard_expand_pack(slot, send_fp, cap) : MC_EBADCFG; }
 int mc_shard_probe_pack(mc_engine *e, const uint64_t *recv_fp, uint64_t cap, uint8_t *answers) {
-    return e && recv_fp && answers ? e->impl->shard_probe_pack(recv_fp, cap, answers) : MC_EBADCFG;
+    return e && recv_fp && answers ? shard_side(e)->shard_probe_pack(recv_fp, cap, answers) : MC_EBADCFG;
 }
 int mc_shard_keep_pack(mc_engine *e, uint32_t slot, const uint8_t *answers_back, uint64_t cap) {
-    return e && answers_back ? e->impl->shard_keep_pack(slot, answers_back, cap) : MC_EBADCFG;
+    return e && answers_back ? shard_side(e)->shard_keep_pack(slot, answers_back, cap) : MC_EBADCFG;
 }
-int mc_shard_wait_keep(mc_engine *e, uint32_t slot) { return e ? e->impl->shard_wait_keep(slot) : MC_EBADCFG; }
-int mc_shard_keep(mc_engine *e, const uint8_t *answers_back, uint64_t *n_new) { return e && n_new ? e->impl->shard_keep(0, answers_back, n_new) : MC_EBADCFG; }
+int mc_shard_wait_keep(mc_engine *e, uint32_t slot) { return e ? shard_side(e)->shard_wait_keep(slot) : MC_EBADCFG; }
+int mc_shard_keep(mc_engine *e, const uint8_t *answers_back, uint64_t *n_new) { return e && n_new ? shard_side(e)->shard_keep(0, answers_back, n_new) : MC_EBADCFG; }
 int mc_shard_keep_slot(mc_engine *e, uint32_t slot, const uint8_t *answers_back, uint64_t *n_new) {
-    return e ? e->impl->shard_keep(slot, answers_back, n_new) : MC_EBADCFG;
+    return e ? shard_side(e)->shard_keep(slot, answers_back, n_new) : MC_EBADCFG;
 }
-int mc_shard_end_level(mc_engine *e, uint64_t *new_local) { return e && new_local ? e->impl->shard_end_level(new_local) : MC_EBADCFG; }
+int mc_shard_end_level(mc_engine *e, uint64_t *new_local) { return e && new_local ? shard_side(e)->shard_end_level(new_local) : MC_EBADCFG; }
 int mc_shard_counters(mc_engine *e, uint64_t *generated, uint64_t *distinct_local, int32_t *verdict) {
-    return e && generated && distinct_local && verdict ? e->impl->shard_counters(generated, distinct_local, verdict) : MC_EBADCFG;
+    return e && generated && distinct_local && verdict ? shard_side(e)->shard_counters(generated, distinct_local, verdict) : MC_EBADCFG;
 }
-int mc_shard_check_frontier(mc_engine *e) { return e ? e->impl->shard_check_frontier() : MC_EBADCFG; }
-int mc_shard_materialise_parents(mc_engine *e, uint32_t slot, uint64_t *send_parents) { return e ? e->impl->shard_materialise_parents(slot, send_parents) : MC_EBADCFG; }
+int mc_shard_check_frontier(mc_engine *e) { return e ? shard_side(e)->shard_check_frontier() : MC_EBADCFG; }
+int mc_shard_materialise_parents(mc_engine *e, uint32_t slot, uint64_t *send_parents) { return e ? shard_side(e)->shard_materialise_parents(slot, send_parents) : MC_EBADCFG; }
 int mc_shard_ingest_parents(mc_engine *e, const uint64_t *recv_parents, uint64_t n, uint32_t src_rank) {
-    return e ? e->impl->shard_ingest_parents(recv_parents, n, src_rank) : MC_EBADCFG;
+    return e ? shard_side(e)->shard_ingest_parents(recv_parents, n, src_rank) : MC_EBADCFG;
 }
 int mc_shard_violation(mc_engine *e, int32_t *found, uint64_t *idx, uint32_t *slot, int32_t *verdict, int32_t *invariant) {
-    return e && found && idx && slot && verdict && invariant ? e->impl->shard_violation(found, idx, slot, verdict, invariant) : MC_EBADCFG;
+    return e && found && idx && slot && verdict && invariant ? shard_side(e)->shard_violation(found, idx, slot, verdict, invariant) : MC_EBADCFG;
 }
-int mc_shard_note_levels(mc_engine *e, const uint64_t *levels, uint32_t n, int32_t verdict) { return e && (levels || !n) ? e->impl->shard_note_levels(levels, n, verdict) : MC_EBADCFG; }
-int mc_shard_resume(mc_engine *e, uint64_t *levels_out, uint32_t *nlevels) { return e && levels_out && nlevels ? e->impl->shard_resume(levels_out, nlevels) : MC_EBADCFG; }
-int mc_shard_checkpoint(mc_engine *e, const char *path) { return e && path ? e->impl->shard_checkpoint(path) : MC_EBADCFG; }
-int mc_shard_restore(mc_engine *e, const char *path) { return e && path ? e->impl->shard_restore(path) : MC_EBADCFG; }
+int mc_shard_note_levels(mc_engine *e, const uint64_t *levels, uint32_t n, int32_t verdict) { return e && (levels || !n) ? shard_side(e)->shard_note_levels(levels, n, verdict) : MC_EBADCFG; }
+int mc_shard_resume(mc_engine *e, uint64_t *levels_out, uint32_t *nlevels) { return e && levels_out && nlevels ? shard_side(e)->shard_resume(levels_out, nlevels) : MC_EBADCFG; }
+int mc_shard_checkpoint(mc_engine *e, const char *path) { return e && path ? shard_side(e)->shard_checkpoint(path) : MC_EBADCFG; }
+int mc_shard_restore(mc_engine *e, const char *path) { return e && path ? shard_side(e)->shard_restore(path) : MC_EBADCFG; }
 int mc_shard_fetch(mc_engine *e, uint64_t idx, uint8_t *state_out, uint32_t *parent_rank, uint64_t *parent_idx, uint32_t *parent_slot) {
-    return e && state_out && parent_rank && parent_idx && parent_slot ? e->impl->shard_fetch(idx, state_out, parent_rank, parent_idx, parent_slot) : MC_EBADCFG;
+    return e && state_out && parent_rank && parent_idx && parent_slot ? shard_side(e)->shard_fetch(idx, state_out, parent_rank, parent_idx, parent_slot) : MC_EBADCFG;
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include "spec_paxos.h"
 #include "spec_pluscal.h"
 #include "spec_raft.h"
+#include "spec_raft_packed.h"   // the same lowering over narrower stored rows: an engine's choice (engine.hip), never dispatch_spec's
 #include "spec_ssi.h"
 #include "spec_vm.h"
 #include "spec_vm_cfg.h"

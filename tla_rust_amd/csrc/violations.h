@@ -30,6 +30,7 @@ struct ViolModel;
 template <> struct ViolModel<SpecAtomicAdd> { MC_HD static int ninv(const SpecAtomicAdd::Params &) { return 0; } };
 template <> struct ViolModel<SpecPcalIntro> { MC_HD static int ninv(const SpecPcalIntro::Params &) { return 1; } };
 template <int N> struct ViolModel<SpecRaft<N>> { MC_HD static int ninv(const RaftParams &) { return 2; } };
+template <int N> struct ViolModel<SpecRaftPacked<N>> : ViolModel<SpecRaft<N>> {};
 template <> struct ViolModel<SpecSsi> { MC_HD static int ninv(const SsiParams &) { return 8; } };   // seven invariants + the `find` predicate
 // (the Paxos family's PROPERTY has an index of its own behind these — 1 / 4 — but no row: it is a property of a step, which no stored state
 //  shows; viol_pair makes a pair that breaks it fatal, and the fatal entry names it)
