@@ -61,6 +61,9 @@ pub const MC_BEH_AMBIGUOUS: i32 = 3;
 pub const MC_BEH_MAX_CANDIDATES: u32 = 64;
 pub const MC_BEH_MAX_INIT: u64 = 65536;
 pub const MC_BEH_F_STUTTER: u32 = 1;
+pub const MC_BEH_MAX_HIDDEN: u32 = 255;
+/// flags bits 8..15: up to `h` model steps that change no observed cell may lie between two observations
+pub const fn mc_beh_f_hidden(h: u32) -> u32 { (h & 0xff) << 8 }
 #[repr(C)]
 pub struct mc_beh_opts {
     pub count: u64, pub first: *const u64, pub rows: *const u8, pub mask: *const u8, pub flags: u32, pub iters: u32,
@@ -128,6 +131,10 @@ extern "C" {
     pub fn mc_engine_behaviours(e: *mut mc_engine, opts: *const mc_beh_opts, out: *mut mc_beh_verdict, result: *mut mc_beh_result) -> c_int;
     pub fn mc_engine_behaviour_witness(e: *mut mc_engine, opts: *const mc_beh_opts, b: u64, states: *mut u8, slots: *mut i32,
                                        n_inout: *mut usize) -> c_int;
+    // the witness with the unlogged steps in it (mc_beh_f_hidden in opts.flags, which behaviour_witness refuses): obs[k] = the
+    // observation state k stands at, a hidden state repeats the one before it; at most (h + 1) * step states
+    pub fn mc_engine_behaviour_path(e: *mut mc_engine, opts: *const mc_beh_opts, b: u64, states: *mut u8, slots: *mut i32, obs: *mut u32,
+                                    n_inout: *mut usize) -> c_int;
     pub fn mc_engine_trace(e: *mut mc_engine, states: *mut u8, actions: *mut i32, n_inout: *mut usize) -> c_int;
     // entries for Init and every action of the model, in action-id order; *n_inout: capacity in, count out
     pub fn mc_engine_coverage(e: *mut mc_engine, out: *mut mc_action_coverage, n_inout: *mut usize) -> c_int;

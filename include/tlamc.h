@@ -522,13 +522,21 @@ int mc_engine_simulate(mc_engine *e, const mc_sim_opts *opts, mc_sim_result *out
  * the flags alone: not of the batch's order, the engine's capacities, `iters` or the device.
  * Refused (MC_EBADCFG + mc_last_error): an empty behaviour, a model with more than 65536 initial states, a sharded engine, and an
  * MC_F_JIT engine (its rows are packed and there is no way to import an interpreter's row into them).  The engine's search, if any,
- * is left as it is. */
-#define MC_BEH_ACCEPTED 1          /* K_{T-1} is not empty: step = T                                              */
+ * is left as it is.
+ * Unlogged steps: with MC_BEH_F_HIDDEN(H) in flags, up to H model steps that leave every observed cell unchanged may lie between
+ * o_{i-1} and o_i (an implementation logs when something it shows changes; the model also steps through labels that move only pc or a
+ * local).  K_i is then built from the closure C of K_{i-1}: K_{i-1} plus, depth by depth up to H, the distinct successors that still
+ * match o_{i-1}.  Every member of C is evaluated once (`generated`); its successors join K_i where they match o_i.  A closure that would
+ * pass MC_BEH_MAX_CANDIDATES rows makes the behaviour ambiguous like a K_i that does; `peak` covers the closures.  No hidden step comes
+ * before o_0, and what follows the last observation does not matter.  H = 0 is the rule above, field for field. */
+#define MC_BEH_ACCEPTED 1         /* K_{T-1} is not empty: step = T                                              */
 #define MC_BEH_REJECTED 2          /* K_step is empty (step = 0: no initial state matches)                       */
 #define MC_BEH_AMBIGUOUS 3         /* K_step would hold more than MC_BEH_MAX_CANDIDATES rows: not decided        */
 #define MC_BEH_MAX_CANDIDATES 64
 #define MC_BEH_MAX_INIT 65536
 #define MC_BEH_F_STUTTER 1u        /* an observation may repeat the state before it                              */
+#define MC_BEH_F_HIDDEN(h) (((h) & 0xffu) << 8)   /* up to h unlogged steps between two observations (flags bits 8..15) */
+#define MC_BEH_MAX_HIDDEN 255
 typedef struct {
     uint64_t count;           /* behaviours                                                                 */
     const uint64_t *first;    /* [count + 1]: behaviour b is observations first[b] .. first[b + 1] - 1 of rows */
@@ -559,6 +567,11 @@ int mc_engine_behaviours(mc_engine *e, const mc_beh_opts *opts, mc_beh_verdict *
  * s_{k-1} to s_k (-1 for s_0, -2 for a stuttering step).  *n_inout: capacity in, n out (MC_EBADCFG with n when too small).  The path
  * is deterministic: it ends in the least row of the last set, and a row reached in several ways keeps the least slot. */
 int mc_engine_behaviour_witness(mc_engine *e, const mc_beh_opts *opts, uint64_t b, uint8_t *states_out, int32_t *slots_out, size_t *n_inout);
+/* The same with unlogged steps (MC_BEH_F_HIDDEN in opts->flags, which mc_engine_behaviour_witness refuses: its path has one state per
+ * observation): obs_out[k] = the observation state k stands at; a hidden state repeats the index of the observation before it.
+ * n <= (H + 1) * the verdict's step.  A closure member keeps the link of its least depth, then least slot, then least parent. */
+int mc_engine_behaviour_path(mc_engine *e, const mc_beh_opts *opts, uint64_t b, uint8_t *states_out, int32_t *slots_out, uint32_t *obs_out,
+                             size_t *n_inout);
 
 /* Checkpoint / recover — TLC checkpoints a run into its states/ directory ("-- Checkpointing of run states/01-08-03-18-14-01
  * completed.", reference examples/SpecifyingSystems/AdvancedExamples/testout1:10; .gitignore:2) and continues it with -recover.
@@ -976,13 +989,15 @@ int mc_check_files_dumps(const char *tla_path, const char *cfg_path, const mc_co
  * simulation between two launches: the report then says so (MC_V_BUDGET). */
 int mc_simulate_files(const char *tla_path, const char *cfg_path, const mc_config *cfg, const mc_sim_opts *opts, char *report, size_t report_cap,
                       mc_sim_result *out, const volatile int *interrupt);
-/* `mc X.tla -behaviours FILE [-observe v1,v2,...] [-stutter]`: the module resolved as mc_check_files resolves it (a compiled PlusCal
+/* `mc X.tla -behaviours FILE [-observe v1,v2,...] [-stutter] [-hidden H]`: the module resolved as mc_check_files resolves it (a compiled PlusCal
  * program: the file's states are texts, mc_state_parse), FILE read — states as `mc -dump` / a TLC trace prints them, optional
  * "State k:" headers ignored, a blank line between states, a line of ---- between behaviours — and mc_engine_behaviours run on it.
  * observe: comma-separated variable names (mc_program_observe), or NULL: the variables every state of the file mentions.  flags:
  * MC_BEH_F_*.  The report gives the counts, a warning that names the ambiguous behaviours, and for the first rejected behaviour
  * "Error: Behaviour b is not a behaviour of the model: no step leads to observation i.", the witness in TLC's layout and the
- * observation.  Behaviours and observations are counted from 1 in the report. */
+ * observation.  With MC_BEH_F_HIDDEN(H) the first line says "up to H unlogged steps between observations", the error "no step, and no
+ * step after up to H unlogged ones, leads to observation i", and the witness (mc_engine_behaviour_path) marks the states the log does
+ * not have with "(not logged)".  Behaviours and observations are counted from 1 in the report. */
 int mc_check_behaviours_files(const char *tla_path, const char *cfg_path, const mc_config *cfg, const char *behaviours_path, const char *observe,
                               unsigned flags, char *report, size_t report_cap, mc_beh_result *out);
 

@@ -200,10 +200,18 @@ class BehResult(C.Structure):
 BEH_VERDICTS = {1: "accepted", 2: "rejected", 3: "ambiguous"}   # MC_BEH_*
 MC_BEH_F_STUTTER = 1
 MC_BEH_MAX_CANDIDATES = 64
+MC_BEH_MAX_HIDDEN = 255
+
+
+def beh_flags(stutter=False, hidden=0):
+    """mc_beh_opts.flags: MC_BEH_F_STUTTER | MC_BEH_F_HIDDEN(hidden)"""
+    if not 0 <= hidden <= MC_BEH_MAX_HIDDEN:
+        raise ValueError(f"hidden: 0 .. {MC_BEH_MAX_HIDDEN} unlogged steps between observations")
+    return (MC_BEH_F_STUTTER if stutter else 0) | hidden << 8
 BEH_FIELDS = ("verdict", "step", "candidates", "peak", "generated", "outside", "errors")
 
 
-def beh_opts(rows_list, W, mask=None, stutter=False, iters=0):
+def beh_opts(rows_list, W, mask=None, stutter=False, iters=0, hidden=0):
     """mc_beh_opts of a batch: rows_list = one list of rows (bytes of W bytes each) per behaviour.  Returns (opts, what must stay alive)"""
     first = (C.c_uint64 * (len(rows_list) + 1))()
     for b, rows in enumerate(rows_list):
@@ -213,7 +221,7 @@ def beh_opts(rows_list, W, mask=None, stutter=False, iters=0):
     blob = b"".join(b"".join(rows) for rows in rows_list)
     if mask is not None and len(mask) != W:
         raise ValueError(f"the mask is {W} bytes")
-    o = BehOpts(len(rows_list), first, blob, bytes(mask) if mask is not None else None, MC_BEH_F_STUTTER if stutter else 0, iters)
+    o = BehOpts(len(rows_list), first, blob, bytes(mask) if mask is not None else None, beh_flags(stutter, hidden), iters)
     return o, (first, blob)
 
 
@@ -255,6 +263,8 @@ def lib():
     L.mc_engine_behaviours.argtypes = [C.c_void_p, C.POINTER(BehOpts), C.POINTER(BehVerdict), C.POINTER(BehResult)]
     L.mc_engine_behaviour_witness.argtypes = [C.c_void_p, C.POINTER(BehOpts), C.c_uint64, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]
     L.mc_state_parse.argtypes = [C.POINTER(SpecDesc), C.c_char_p, C.c_char_p, C.c_char_p]
+    L.mc_engine_behaviour_path.argtypes = [C.c_void_p, C.POINTER(BehOpts), C.c_uint64, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_size_t)]
     L.mc_check_behaviours_files.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Config), C.c_char_p, C.c_char_p, C.c_uint, C.c_char_p, C.c_size_t,
                                             C.POINTER(BehResult)]
     L.mc_engine_trace.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]
@@ -439,15 +449,15 @@ def state_parse(spec, params, text: str):
     return row.raw, mask.raw
 
 
-def check_behaviours_files(tla_path, behaviours_path, cfg_path=None, observe=None, stutter=False, device=0, **kw):
-    """`mc X.tla -behaviours FILE [-observe ...] [-stutter]` (mc_check_behaviours_files): (totals, report text)"""
+def check_behaviours_files(tla_path, behaviours_path, cfg_path=None, observe=None, stutter=False, device=0, hidden=0, **kw):
+    """`mc X.tla -behaviours FILE [-observe ...] [-stutter] [-hidden H]` (mc_check_behaviours_files): (totals, report text)"""
     flags = 128 if kw.pop("generic", False) else 0   # MC_F_GENERIC
     cfg = Config(device, flags, kw.pop("table_capacity", 1 << 16), kw.pop("arena_capacity", 1 << 14), kw.pop("chunk_states", 0), 0, 0, 0, 1)
     report = C.create_string_buffer(1 << 22)
     r = BehResult()
     _check(lib().mc_check_behaviours_files(str(tla_path).encode(), str(cfg_path).encode() if cfg_path else None, C.byref(cfg),
                                            str(behaviours_path).encode(), ",".join(observe).encode() if observe else None,
-                                           MC_BEH_F_STUTTER if stutter else 0, report, len(report), C.byref(r)), "mc_check_behaviours_files")
+                                           beh_flags(stutter, hidden), report, len(report), C.byref(r)), "mc_check_behaviours_files")
     return Result(accepted=r.accepted, rejected=r.rejected, ambiguous=r.ambiguous, observations=r.observations, generated=r.generated,
                   first_rejected=None if r.first_rejected == (1 << 64) - 1 else r.first_rejected, seconds=r.seconds), report.value.decode()
 
@@ -506,13 +516,14 @@ class Engine:
                                for k in range(record)]
         return out
 
-    def behaviours(self, rows_list, mask=None, stutter=False, iters=0):
+    def behaviours(self, rows_list, mask=None, stutter=False, iters=0, hidden=0):
         """mc_engine_behaviours: is every recorded behaviour a behaviour of the model?  rows_list: per behaviour, its observations as
         rows (bytes, state_bytes each: what read_states / state_apply give); mask: bytes of the same width saying which are observed
-        (None: all), one for the batch; stutter: an observation may repeat the state before it.  Result: the totals, and
+        (None: all), one for the batch; stutter: an observation may repeat the state before it; hidden: up to that many model steps
+        that change no observed cell may lie between two observations.  Result: the totals, and
         verdicts = [{verdict: accepted / rejected / ambiguous, step, candidates, peak, generated, outside, errors}]."""
         W = lib().mc_state_bytes(C.byref(self.desc))
-        o, keep = beh_opts(rows_list, W, mask, stutter, iters)
+        o, keep = beh_opts(rows_list, W, mask, stutter, iters, hidden)
         out = (BehVerdict * max(len(rows_list), 1))()
         r = BehResult()
         _check(lib().mc_engine_behaviours(self._h, C.byref(o), out, C.byref(r)), "mc_engine_behaviours")
@@ -521,17 +532,29 @@ class Engine:
                       verdicts=[Result(verdict=BEH_VERDICTS[v.verdict], **{f: getattr(v, f) for f in BEH_FIELDS[1:]})
                                 for v in out[:len(rows_list)]])
 
-    def behaviour_witness(self, rows_list, b, mask=None, stutter=False):
+    def behaviour_witness(self, rows_list, b, mask=None, stutter=False, hidden=0):
         """mc_engine_behaviour_witness: behaviour b of the batch once more on the host; one model path through its candidate sets, as
         [(slot, row)] — slot -1 for the initial state, -2 for a stuttering step.  The whole behaviour if it is accepted, the states
-        before the deciding observation otherwise."""
+        before the deciding observation otherwise.  Refused with hidden > 0: behaviour_path gives the longer path."""
         W = lib().mc_state_bytes(C.byref(self.desc))
-        o, keep = beh_opts(rows_list, W, mask, stutter, 0)
+        o, keep = beh_opts(rows_list, W, mask, stutter, 0, hidden)
         cap = C.c_size_t(len(rows_list[b]))
         states = C.create_string_buffer(W * max(cap.value, 1))
         slots = (C.c_int32 * max(cap.value, 1))()
         _check(lib().mc_engine_behaviour_witness(self._h, C.byref(o), b, states, slots, C.byref(cap)), "mc_engine_behaviour_witness")
         return [(slots[k], states.raw[k * W:(k + 1) * W]) for k in range(cap.value)]
+
+    def behaviour_path(self, rows_list, b, mask=None, stutter=False, hidden=0):
+        """mc_engine_behaviour_path: the witness with the unlogged steps in it, as [(slot, row, obs)] — obs = the observation the state
+        stands at; a hidden state repeats the index of the observation before it.  At most (hidden + 1) * step states."""
+        W = lib().mc_state_bytes(C.byref(self.desc))
+        o, keep = beh_opts(rows_list, W, mask, stutter, 0, hidden)
+        cap = C.c_size_t(len(rows_list[b]) * (hidden + 1))
+        states = C.create_string_buffer(W * max(cap.value, 1))
+        slots = (C.c_int32 * max(cap.value, 1))()
+        obs = (C.c_uint32 * max(cap.value, 1))()
+        _check(lib().mc_engine_behaviour_path(self._h, C.byref(o), b, states, slots, obs, C.byref(cap)), "mc_engine_behaviour_path")
+        return [(slots[k], states.raw[k * W:(k + 1) * W], obs[k]) for k in range(cap.value)]
 
     def coverage(self):
         """mc_engine_coverage (TLC's -coverage; an engine created with coverage=True): {action name: (distinct, generated)} for "Init"

@@ -2253,7 +2253,9 @@ struct Engine : EngineBase {
         a.flags = o->flags;
         a.iters = iters;
         a.ctr = beh.ctr;
-        const size_t lds = ((size_t)2 * W + MC_BEH_MAX_CANDIDATES) * sizeof(uint64_t);
+        // unlogged steps (MC_BEH_F_HIDDEN): the instantiation that closes a set under hidden steps, with LDS for it; without, the plain one
+        const bool hidden = beh_hidden(o->flags) != 0;
+        const size_t lds = beh_lds_words(W, hidden) * sizeof(uint64_t);
         std::vector<uint64_t> rel(R + 1);
         const auto t0 = std::chrono::steady_clock::now();
         for (uint64_t b0 = 0; b0 < o->count; b0 += R) {
@@ -2282,7 +2284,8 @@ struct Engine : EngineBase {
             a.carry = beh.carry;
             a.out = beh.out;
             for (uint64_t l = 0; l < (longest + iters - 1) / iters; ++l) {
-                hipLaunchKernelGGL(k_behaviours<S>, dim3((unsigned)n), dim3(64), lds, stream, prm, a);
+                if (hidden) hipLaunchKernelGGL((k_behaviours<S, 0, true>), dim3((unsigned)n), dim3(64), lds, stream, prm, a);
+                else hipLaunchKernelGGL(k_behaviours<S>, dim3((unsigned)n), dim3(64), lds, stream, prm, a);
                 HIP_TRY(hipGetLastError());
             }
             HIP_TRY(hipMemcpyAsync(out + b0, beh.out, n * sizeof(mc_beh_verdict), hipMemcpyDeviceToHost, stream));
@@ -2589,9 +2592,47 @@ int mc_engine_trace(mc_engine *e, uint8_t *states_out, int32_t *actions_out, siz
 int mc_engine_behaviours(mc_engine *e, const mc_beh_opts *opts, mc_beh_verdict *out, mc_beh_result *result) {
     return e && opts && result ? e->impl->behaviours(opts, out, result) : MC_EBADCFG;
 }
+// the witness with (obs_out) or without the unlogged steps: one host run of the rule with links, one walk back through them
+static int behaviour_path(const char *who, mc_engine *e, const mc_beh_opts *opts, uint64_t b, uint8_t *states_out, int32_t *slots_out, uint32_t *obs_out,
+                          size_t *n_inout) {
+    const std::string w(who);
+    if (!e || !opts || !n_inout || !opts->first || !opts->rows || b >= opts->count || opts->first[b + 1] <= opts->first[b]) {
+        mc_set_error_internal((w + ": no such behaviour").c_str());
+        return MC_EBADCFG;
+    }
+    if (int rc = e->impl->behaviours_refused()) return rc;   // (what the batch call refuses)
+    return dispatch_spec(e->impl->spec_desc(), [&](auto s, const auto &prm) {
+        using S = decltype(s);
+        const size_t W = (size_t)S::words(prm);
+        const uint64_t T = opts->first[b + 1] - opts->first[b];
+        std::vector<uint64_t> rows(T * W), mask(W);
+        memcpy(rows.data(), opts->rows + opts->first[b] * W * sizeof(uint64_t), T * W * sizeof(uint64_t));
+        if (opts->mask) memcpy(mask.data(), opts->mask, W * sizeof(uint64_t));
+        mc_beh_verdict v;
+        BehSets sets;
+        beh_check<S>(prm, rows.data(), T, opts->mask ? mask.data() : nullptr, opts->flags, &v, &sets);
+        const BehPath path = beh_path(sets, (int)W);
+        const size_t n = path.slots.size();
+        if (n > *n_inout) { *n_inout = n; mc_set_error_internal((w + ": buffers too small").c_str()); return MC_EBADCFG; }
+        *n_inout = n;
+        if (!n) return MC_OK;
+        if (!states_out || !slots_out || !obs_out) { mc_set_error_internal((w + ": states_out, slots_out and obs_out are needed").c_str()); return MC_EBADCFG; }
+        memcpy(states_out, path.states.data(), n * W * sizeof(uint64_t));
+        memcpy(slots_out, path.slots.data(), n * sizeof(int32_t));
+        memcpy(obs_out, path.obs.data(), n * sizeof(uint32_t));
+        return MC_OK;
+    });
+}
+int mc_engine_behaviour_path(mc_engine *e, const mc_beh_opts *opts, uint64_t b, uint8_t *states_out, int32_t *slots_out, uint32_t *obs_out, size_t *n_inout) {
+    return behaviour_path("behaviour_path", e, opts, b, states_out, slots_out, obs_out, n_inout);
+}
 int mc_engine_behaviour_witness(mc_engine *e, const mc_beh_opts *opts, uint64_t b, uint8_t *states_out, int32_t *slots_out, size_t *n_inout) {
     if (!e || !opts || !n_inout || !opts->first || !opts->rows || b >= opts->count || opts->first[b + 1] <= opts->first[b]) {
         mc_set_error_internal("behaviour_witness: no such behaviour");
+        return MC_EBADCFG;
+    }
+    if (beh_hidden(opts->flags)) {
+        mc_set_error_internal("behaviour_witness: with unlogged steps (MC_BEH_F_HIDDEN) a path is longer than the log: call mc_engine_behaviour_path");
         return MC_EBADCFG;
     }
     if (int rc = e->impl->behaviours_refused()) return rc;   // (what the batch call refuses)

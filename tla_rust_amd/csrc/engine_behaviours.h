@@ -15,6 +15,8 @@
 // K_0: the lanes stride over k < num_init.  A launch advances a behaviour by at most `iters` observations; the carry between launches
 // is one word per behaviour (behaviour.h beh_carry), the verdict record accumulates in place.  Totals: one atomic of each kind per
 // wavefront and launch.
+// With unlogged steps (MC_BEH_F_HIDDEN) the host launches k_behaviours<S, 0, true>: the closure of the current set under hidden steps
+// fills the lanes behind it (see above the kernel).  The plain instantiation compiles none of that.
 #ifndef TLAMC_ENGINE_BEHAVIOURS_H
 #define TLAMC_ENGINE_BEHAVIOURS_H
 
@@ -49,7 +51,7 @@ __device__ __forceinline__ bool beh_append(int W, bool mine, uint64_t fp, const 
     __builtin_amdgcn_wave_barrier();
     const CWordRef my{stage_blk + lane, 64};
     // the members the set already holds
-    if (mine)
+    if (mine && mutant != 4)
         for (unsigned j = 0; j < nnext; ++j)
             if (s_fp[j] == fp && beh_same_row(my, CWordRef{next_blk + j, 64}, W)) { mine = false; break; }
     // ... and what a lower lane of this round brings
@@ -76,7 +78,18 @@ __device__ __forceinline__ bool beh_append(int W, bool mine, uint64_t fp, const 
 
 // MUTANT: 0 in the product.  tests/_behshim/behshim.hip also builds 1 (no dedup across the lanes of one round), 2 (the last word of the
 // mask skipped) and 3 (lane 64 and beyond dropped in place of AMBIGUOUS): kernels that the device tests must tell from this one.
-template <class S, unsigned MUTANT = 0>
+// tests/_behshim/behgap.hip builds the HIDDEN kernel at 4 (no dedup of the closure against the current set), 5 (the depth bound off by
+// one) and 6 (the match against the observation before skipped); each stays inside its 64 columns and its H (+ 1) depths.
+//
+// HIDDEN: the instantiation for MC_BEH_F_HIDDEN(H) (behaviour.h: unlogged steps).  The closure C of K_{i-1} is appended to the current
+// set's own block, behind K_{i-1}; a depth's frontier is the column range [lo, hi) and lane l takes column lo + l; every lane calls
+// beh_append twice per slot from the same staging column, towards C (only below depth H, when the successor still matches o_{i-1}) and
+// towards K_i.  The rows one lane appends to C and another loads in the next depth are ordered by beh_append's closing fence +
+// wave_barrier.  LDS: beh_lds_words(W, true) — o_{i-1} and the fingerprints of C on top of the plain kernel's.  HIDDEN = false
+// compiles none of it: the kernel DESIGN section 23 measured.
+__host__ __device__ constexpr size_t beh_lds_words(int W, bool hidden) { return (size_t)2 * W + MC_BEH_MAX_CANDIDATES + (hidden ? (size_t)W + MC_BEH_MAX_CANDIDATES : 0); }
+
+template <class S, unsigned MUTANT = 0, bool HIDDEN = false>
 __global__ void __launch_bounds__(64)
 k_behaviours(typename S::Params prm, BehArgs a) {
     extern __shared__ uint64_t beh_lds[];
@@ -124,6 +137,64 @@ k_behaviours(typename S::Params prm, BehArgs a) {
                 }
                 fits = beh_append(W, mine, fp, stage_blk, next_blk, s_fp, nnext, MUTANT) && fits;
             }
+        } else if constexpr (HIDDEN) {
+            uint64_t *const s_prev = beh_lds + 2 * W + MC_BEH_MAX_CANDIDATES, *const s_cfp = s_prev + W;
+            const unsigned H = beh_hidden(a.flags), HD = MUTANT == 5 ? H + 1 : H;   // the depth below which a successor may join C
+            for (int w = lane; w < W; w += 64) s_prev[w] = a.rows[(o0 + step - 1) * W + w];
+            if (lane < ncur) s_cfp[lane] = S::fp_of(prm, CWordRef{cur_blk + lane, 64});
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            const uint64_t pfp = full ? S::fp_of(prm, CWordRef{s_prev, 1}) : 0;
+            unsigned nclo = ncur, lo = 0;
+            bool cfits = true;
+            for (unsigned d = 0; d <= HD && cfits && lo < nclo; ++d) {   // (at d == HD nothing joins C: the loop ends there at the latest)
+                const unsigned hi = nclo;   // hi - lo <= 64: C never passes 64 columns
+                const bool have = lo + lane < hi;
+                const CWordRef cur{cur_blk + (have ? lo + lane : 0), 64};
+                typename S::Local loc;
+                int ns = 0;
+                if (have) {
+                    S::load(prm, cur, loc);
+                    ns = S::nslots(prm, loc);
+                }
+                if (a.flags & MC_BEH_F_STUTTER) {
+                    const bool mine = have && beh_match(cur, s_obs, s_mask, WM);
+                    uint64_t fp = 0;
+                    if (mine) {
+                        for (int w = 0; w < W; ++w) stage.set(w, cur.get(w));
+                        fp = s_cfp[lo + lane];
+                    }
+                    fits = beh_append(W, mine, fp, stage_blk, next_blk, s_fp, nnext, MUTANT < 4 ? MUTANT : 0) && fits;
+                }
+                const int wns = (int)wave_max_u32((unsigned)ns);
+                for (int slot = 0; slot < wns; ++slot) {
+                    bool to_next = false, to_clo = false;
+                    uint64_t fp = 0;
+                    if (have && slot < ns) {
+                        uint64_t f = 0;
+                        const unsigned st = S::eval(prm, loc, cur, slot, f);
+                        const unsigned kind = beh_step_kind(st);
+                        if (kind != BEH_NO_STEP) ++gen;
+                        if (kind == BEH_ERROR) ++errors;
+                        if (kind == BEH_STEP || kind == BEH_STEP_OUTSIDE) {
+                            const bool known = beh_fp_known(st);
+                            if (!(full && known && f != ofp && f != pfp)) {
+                                if (st & ST_SELFLOOP) { for (int w = 0; w < W; ++w) stage.set(w, cur.get(w)); }
+                                else S::apply(prm, cur, slot, stage);
+                                to_next = beh_match(cstage, s_obs, s_mask, WM);
+                                to_clo = d < HD && (MUTANT == 6 || beh_match(cstage, s_prev, s_mask, WM));
+                                if (to_next && kind == BEH_STEP_OUTSIDE) ++outside;
+                                if (to_next || to_clo) fp = known ? f : S::fp_of(prm, cstage);
+                            }
+                        }
+                    }
+                    cfits = beh_append(W, to_clo, fp, stage_blk, cur_blk, s_cfp, nclo, MUTANT == 4 ? 4 : 0) && cfits;
+                    fits = beh_append(W, to_next, fp, stage_blk, next_blk, s_fp, nnext, MUTANT < 4 ? MUTANT : 0) && fits;
+                }
+                lo = hi;
+            }
+            if (!cfits) fits = false;
+            if (fits) peak = peak > nclo ? peak : nclo;
         } else {
             const bool have = lane < ncur;
             const CWordRef cur{cur_blk + lane, 64};

@@ -2173,7 +2173,8 @@ int mc_simulate_files(const char *tla_path, const char *cfg_path, const mc_confi
 }
 
 // `mc X.tla -behaviours FILE`: the file's states parsed (mc_state_parse), the batch decided on the GPU (mc_engine_behaviours), the first
-// rejected behaviour explained with a model path up to the observation nothing leads to (mc_engine_behaviour_witness)
+// rejected behaviour explained with a model path up to the observation nothing leads to (mc_engine_behaviour_path: with -hidden H the
+// states the log does not have are in it, marked "(not logged)")
 int mc_check_behaviours_files(const char *tla_path, const char *cfg_path, const mc_config *cfg, const char *behaviours_path, const char *observe,
                               unsigned flags, char *report, size_t report_cap, mc_beh_result *res) {
     if (!tla_path || !cfg || !behaviours_path || !report || !report_cap || !res) return MC_EBADCFG;
@@ -2253,8 +2254,11 @@ int mc_check_behaviours_files(const char *tla_path, const char *cfg_path, const 
     if ((rc = mc_engine_behaviours(e, &o, v.data(), res))) { mc_engine_destroy(e); return rc; }
     Out out{report, report_cap, 0};
     if (!R.warning.empty()) out.put("%s", R.warning.c_str());
-    out.put("Checking %llu recorded behaviours (%llu observations) of %s against the model%s.\n", (unsigned long long)count,
-            (unsigned long long)first.back(), behaviours_path, flags & MC_BEH_F_STUTTER ? ", stuttering steps allowed" : "");
+    const unsigned hidden = flags >> 8 & 0xffu;   // MC_BEH_F_HIDDEN
+    char unlogged[64] = "";
+    if (hidden) snprintf(unlogged, sizeof unlogged, ", up to %u unlogged steps between observations", hidden);
+    out.put("Checking %llu recorded behaviours (%llu observations) of %s against the model%s%s.\n", (unsigned long long)count,
+            (unsigned long long)first.back(), behaviours_path, flags & MC_BEH_F_STUTTER ? ", stuttering steps allowed" : "", unlogged);
     if (res->ambiguous) {
         out.put("Warning: %llu behaviours are ambiguous (more than %d states of the model fit the observations; observe more variables), not decided:",
                 (unsigned long long)res->ambiguous, MC_BEH_MAX_CANDIDATES);
@@ -2263,19 +2267,24 @@ int mc_check_behaviours_files(const char *tla_path, const char *cfg_path, const 
     }
     if (res->first_rejected != ~0ull) {
         const uint64_t b = res->first_rejected;
+        if (hidden)
+            out.put("Error: Behaviour %llu is not a behaviour of the model: no step, and no step after up to %u unlogged ones, leads to observation %u.\n",
+                    (unsigned long long)b + 1, hidden, v[b].step + 1);
+        else
         out.put("Error: Behaviour %llu is not a behaviour of the model: no step leads to observation %u.\n", (unsigned long long)b + 1, v[b].step + 1);
-        size_t n = v[b].step ? v[b].step : 1;
+        size_t n = (size_t)(v[b].step ? v[b].step : 1) * (hidden + 1);
         std::vector<uint8_t> states(n * W);
         std::vector<int32_t> slots(n);
-        if (mc_engine_behaviour_witness(e, &o, b, states.data(), slots.data(), &n) == MC_OK && n) {
+        std::vector<uint32_t> at(n);   // the observation a state stands at: a hidden state repeats the one before it
+        if (mc_engine_behaviour_path(e, &o, b, states.data(), slots.data(), at.data(), &n) == MC_OK && n) {
             out.put("Error: The behavior of the model up to this point is:\n");
             std::vector<char> txt(1 << 16);
             for (size_t k = 0; k < n; ++k) {
                 mc_state_format(&d, &states[k * W], txt.data(), txt.size());
                 if (slots[k] == -1) out.put("State %zu: <Initial predicate>\n%s\n\n", k + 1, txt.data());
                 else if (slots[k] < 0) out.put("State %zu: <Stuttering>\n%s\n\n", k + 1, txt.data());
-                else out.put("State %zu: <Action %s of module %s>\n%s\n\n", k + 1, mc_action_name(&d, mc_state_action(&d, &states[(k - 1) * W], slots[k])),
-                             R.module.c_str(), txt.data());
+                else out.put("State %zu: <Action %s of module %s>%s\n%s\n\n", k + 1, mc_action_name(&d, mc_state_action(&d, &states[(k - 1) * W], slots[k])),
+                             R.module.c_str(), at[k] == at[k - 1] && slots[k] >= 0 && hidden ? " (not logged)" : "", txt.data());
             }
         } else out.put("No initial state of the model matches it.\n");
         out.put("The observation is:\n%s\n", texts[(size_t)(first[b] + v[b].step)].c_str());

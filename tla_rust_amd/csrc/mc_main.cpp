@@ -7,7 +7,7 @@
 //            [-checkpoint FILE] [-recover FILE] [-gpus P [-samedevice | -torch] [-exchange exact|measured|packed] [-fanout N]] [-noprogress] [-I DIR]
 //            [-coverage [MINUTES]] [-strongfair] [-labelfair] [-continue]
 //   mc X.tla -simulate [num=N] [-depth D] [-seed S] [-config X.cfg] [-deadlock] [-jit] [-device D] [-noprogress] [-I DIR]
-//   mc X.tla -behaviours FILE [-observe v1,v2,...] [-stutter] [-config X.cfg] [-device D] [-I DIR]
+//   mc X.tla -behaviours FILE [-observe v1,v2,...] [-stutter] [-hidden H] [-config X.cfg] [-device D] [-I DIR]
 //   mc --transpile X.tla [Y.tla ...]      the `pcal2tla *tla` of the reference's Makefile:3-4: inserts (or
 //                                         replaces) the TLA+ translation of the PlusCal algorithm in place,
 //                                         the previous text is kept as X.old
@@ -51,10 +51,11 @@
 //             depth give the same walks and the same report.  The report has the error and its behaviour as the search's has, "The
 //             number of states generated: G" and the walks, but no distinct-state count or search depth: nothing was searched
 //             exhaustively.  -gpus, -dump, -checkpoint and -recover do not apply; a module without a GPU lowering is refused.
-// -behaviours FILE [-observe v1,v2,...] [-stutter]: is every execution recorded in FILE a behaviour of the model (a PlusCal module)?
+// -behaviours FILE [-observe v1,v2,...] [-stutter] [-hidden H]: is every execution recorded in FILE a behaviour of the model (a PlusCal module)?
 //             FILE holds states as `mc -dump` / a TLC trace prints them ("State k:" headers are ignored), a blank line between states, a
 //             line of ---- between behaviours; a state may leave variables out.  -observe names the variables that count (default: those
-//             every state of the file mentions); -stutter lets an observation repeat the state before it.  One GPU wavefront decides one
+//             every state of the file mentions); -stutter lets an observation repeat the state before it; -hidden H (0..255) lets up to H model steps that change no
+//             observed variable lie between two observations (the labels an implementation does not log).  One GPU wavefront decides one
 //             behaviour (mc_engine_behaviours).  The report counts the verdicts, names the ambiguous behaviours in a warning, and for
 //             the first rejected one prints a behaviour of the model up to the observation no step leads to.  Exit status 12 if a
 //             behaviour is rejected.  Not with -simulate, -gpus, -recover, -checkpoint, -dump, -coverage or -continue.
@@ -363,10 +364,10 @@ static int run_simulation(const char *tla, const char *cfgp, const mc_config &cf
 }
 
 // ---- mc X.tla -behaviours FILE
-static int run_behaviours(const char *tla, const char *cfgp, const mc_config &cfg, const char *file, const char *observe, bool stutter) {
+static int run_behaviours(const char *tla, const char *cfgp, const mc_config &cfg, const char *file, const char *observe, bool stutter, unsigned hidden) {
     std::vector<char> report(1 << 22);
     mc_beh_result res;
-    const int rc = mc_check_behaviours_files(tla, cfgp, &cfg, file, observe, stutter ? MC_BEH_F_STUTTER : 0u, report.data(), report.size(), &res);
+    const int rc = mc_check_behaviours_files(tla, cfgp, &cfg, file, observe, (stutter ? MC_BEH_F_STUTTER : 0u) | MC_BEH_F_HIDDEN(hidden), report.data(), report.size(), &res);
     if (rc) {
         fprintf(stderr, "mc: %s: %s\n", mc_strerror(rc), mc_last_error());
         return 1;
@@ -425,6 +426,8 @@ int main(int argc, char **argv) {
     unsigned dot_flags = 0;
     bool simulate = false, have_seed = false, have_depth = false, stutter = false;
     const char *beh_file = nullptr, *observe = nullptr;
+    uint64_t hidden = 0;
+    bool have_hidden = false;
     mc_sim_opts sim;
     memset(&sim, 0, sizeof sim);
     sim.depth = 100;   // TLC's default -depth
@@ -464,6 +467,13 @@ int main(int argc, char **argv) {
         else if (arg("-behaviours")) beh_file = argv[++i];
         else if (arg("-observe")) observe = argv[++i];
         else if (!strcmp(argv[i], "-stutter")) stutter = true;
+        else if (arg("-hidden")) {
+            if (!parse_u64(argv[++i], &hidden) || hidden > MC_BEH_MAX_HIDDEN) {
+                fprintf(stderr, "mc: -hidden needs a number of unlogged steps between observations (0..%d)\n", MC_BEH_MAX_HIDDEN);
+                return 1;
+            }
+            have_hidden = true;
+        }
         else if (!strcmp(argv[i], "-deadlock")) cfg.flags &= ~MC_F_DEADLOCK;
         else if (arg("-dump") && (!strcmp(argv[i + 1], "dot") || !strncmp(argv[i + 1], "dot,", 4))) {   // TLC: -dump dot[,actionlabels][,colorize] FILE
             for (const char *s = argv[++i] + 3; *s;) {
@@ -540,18 +550,21 @@ int main(int argc, char **argv) {
                 "                that is depends on the order of arrival within a level, and the counts may differ from run to run; a temporal\n"
                 "                property under a VIEW is named as NOT checked\n"
                 "       mc X.tla -simulate [num=N] [-depth D] [-seed S] [...]                             random walks like `tlc -simulate`\n"
-                "       mc X.tla -behaviours FILE [-observe v1,v2,...] [-stutter]                         is every execution recorded in FILE a behaviour of the model?\n"
+                "       mc X.tla -behaviours FILE [-observe v1,v2,...] [-stutter] [-hidden H]             is every execution recorded in FILE a behaviour of the model?\n"
                 "       mc --transpile X.tla [Y.tla ...]                                                  translate like `pcal2tla`\n"
                 "exit status: 0 no error, 12 invariant / assertion violated, 11 deadlock, 13 a temporal property violated, 1 anything else\n");
         return 1;
     }
     if (!simulate && (have_depth || have_seed)) { fprintf(stderr, "mc: %s needs -simulate\n", have_depth ? "-depth" : "-seed"); return 1; }
-    if (!beh_file && (observe || stutter)) { fprintf(stderr, "mc: %s needs -behaviours\n", observe ? "-observe" : "-stutter"); return 1; }
+    if (!beh_file && (observe || stutter || have_hidden)) {
+        fprintf(stderr, "mc: %s needs -behaviours\n", observe ? "-observe" : stutter ? "-stutter" : "-hidden");
+        return 1;
+    }
     if (beh_file) {
         cfg.flags &= ~(unsigned)MC_F_PROGRESS;
         cfg.table_capacity = 1ull << 16;   // (no search runs: the seen-set and the arena stay empty)
         cfg.arena_capacity = 1ull << 14;
-        return run_behaviours(tla, cfgp, cfg, beh_file, observe, stutter);
+        return run_behaviours(tla, cfgp, cfg, beh_file, observe, stutter, (unsigned)hidden);
     }
     if (simulate) return run_simulation(tla, cfgp, cfg, sim, have_seed, dump || dot ? "-dump" : ckpt ? "-checkpoint" : recover ? "-recover" : nullptr);
     if (gpus) {  // one rank of `mc X.tla -gpus P`
