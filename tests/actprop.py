@@ -255,31 +255,17 @@ def build_actshim(csrc=None, out=None, own_front_end=False):
     """csrc: the directory the sources are taken from (default: the product's; a copy with one edit is a mutant).  own_front_end: the
     PlusCal front end of csrc is compiled INTO the library and bound to it (-Bsymbolic), whatever front end the process has loaded
     already; otherwise it is tests/_shim's library's"""
-    import fcntl
-    import os
-    import subprocess
+    import testlib
     src = helpers.ROOT / "tests" / "_actshim" / "actshim.cpp"
-    out = out or src.parent / "_build"
-    out.mkdir(exist_ok=True)
-    so = out / "libactshim.so"
-    csrc = csrc or helpers.ROOT / "tla_rust_amd" / "csrc"
-    front = [csrc / f for f in ("pcal.cpp", "pcal_compile.cpp", "pcal_codegen.cpp")] if own_front_end else []
-    shim = None if own_front_end else helpers.build_shim()
-    srcs = [src] + ([shim] if shim else front) + list(csrc.glob("*.h")) + [helpers.ROOT / "include" / "tlamc.h"]
-
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    with open(out / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"libactshim.{os.getpid()}.so"
-            link = [str(f) for f in front] + ["-DACTSHIM_OWN_FRONT_END", "-Wl,-Bsymbolic"] if own_front_end else ["-L", str(shim.parent), f"-l:{shim.name}", f"-Wl,-rpath,{shim.parent}"]
-            subprocess.run(["g++", "-O0" if own_front_end else "-O1", "-std=c++17", "-fPIC", "-shared", "-w", "-o", str(tmp), "-I", str(csrc),
-                            "-I", str(helpers.ROOT / "include"), str(src)] + link, check=True)
-            os.replace(tmp, so)
-    return so
+    csrc = csrc or testlib.CSRC
+    if own_front_end:
+        link = [csrc / f for f in testlib.FRONT_END]
+        argv = ["-O0", *link, "-DACTSHIM_OWN_FRONT_END", "-Wl,-Bsymbolic"]
+    else:
+        link = [helpers.build_shim()]
+        argv = ["-O1", "-L", link[0].parent, f"-l:{link[0].name}", f"-Wl,-rpath,{link[0].parent}"]
+    return testlib.build_library((out or src.parent / "_build") / "libactshim.so",
+                                 testlib.host_argv("-w", "-I", csrc, "-I", helpers.ROOT / "include", src, *argv), [src] + link + testlib.product_deps(csrc))
 
 
 def actshim_lib(so=None):

@@ -4,12 +4,10 @@ hidden_check / hidden_path: behaviour.h's rule over a spec lowering with the hid
 word as it is; behgap.cpp adds beh_path).  GapModel: SpecGap's rows are (x, h) pairs; host(): the host rule, device(): the kernel
 k_behaviours<SpecGap, MUTANT, true> of that library."""
 import ctypes as C
-import fcntl
-import os
-import subprocess
 
 import behshim
 import helpers
+import testlib
 from behshim import STUTTER, Verdict
 
 DIR = behshim.BEHSHIM_DIR
@@ -34,25 +32,7 @@ def hidden_check(m, rows_list, mask=None, stutter=False, hidden=0):
 
 def build_host(csrc=None, out=None):
     """behgap.cpp with g++ (csrc: the product's headers, or a copy with one line of behaviour.h edited)"""
-    out = out or DIR / "_build"
-    out.mkdir(exist_ok=True)
-    so = out / "libbehgap.so"
-    csrc = csrc or helpers.ROOT / "tla_rust_amd" / "csrc"
-    shim = helpers.build_shim()
-    srcs = [DIR / "behgap.cpp", DIR / "behgap.h", shim] + list(csrc.glob("*.h")) + [helpers.ROOT / "include" / "tlamc.h"]
-
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    with open(out / ".lock_gap", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"libbehgap.{os.getpid()}.so"
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(tmp), "-I", str(csrc), "-I", str(DIR), str(DIR / "behgap.cpp"),
-                            "-L", str(shim.parent), "-lshim", f"-Wl,-rpath,{shim.parent}"], check=True)
-            os.replace(tmp, so)
-    return so
+    return helpers.build_over_shim((out or DIR / "_build") / "libbehgap.so", DIR / "behgap.cpp", csrc, more=["-I", DIR], deps=[DIR / "behgap.h"])
 
 
 _GAP_ARGS = [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int]
@@ -94,21 +74,14 @@ def hidden_path(m, rows, mask=None, stutter=False, hidden=0, L=None):
 # ------------------------------------------------------------------------------------------------ the kernel over SpecGap
 def build_device(mutant=0):
     """tests/_behshim/behgap.hip for gfx950: mutant 0 is the product's kernel, 4 / 5 / 6 the kernel with one thing broken"""
-    from seenshim import _build
-    csrc = helpers.ROOT / "tla_rust_amd" / "csrc"
-    include = helpers.ROOT / "include"
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     src = DIR / "behgap.hip"
-    # (the flags of tla_rust_amd/build.py's `common`)
-    return _build(DIR / "_build" / f"libbehgapdev{mutant}.so", [src, DIR / "behgap.h", include / "tlamc.h"] + list(csrc.glob("*.h")),
-                  [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result", f"-DBEH_MUTANT={mutant}",
-                   "-I", str(include), "-I", str(csrc), "-I", str(DIR), "-shared", "-x", "hip", str(src)])
+    return testlib.build_library(DIR / "_build" / f"libbehgapdev{mutant}.so",
+                                 testlib.hip_argv(f"-DBEH_MUTANT={mutant}", "-I", helpers.ROOT / "include", "-I", testlib.CSRC, "-I", DIR, src),
+                                 [src, DIR / "behgap.h"] + testlib.product_deps(testlib.CSRC))
 
 
 def build_devices():
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(len(MUTANTS)) as pool:   # (the threads wait for one hipcc each)
-        return list(pool.map(build_device, MUTANTS))
+    return list(testlib.build_mutants(MUTANTS, build_device).values())
 
 
 class GapModel:

@@ -3,11 +3,9 @@
 Built on first use, like simwalk's library, and linked against helpers' libshim.so for the PlusCal front-end.  Rows are bytes
 (8 * words each), as the Python binding hands them around."""
 import ctypes as C
-import fcntl
-import os
-import subprocess
 
 import helpers
+import testlib
 
 BEHSHIM_DIR = helpers.ROOT / "tests" / "_behshim"
 VERDICTS = {1: "accepted", 2: "rejected", 3: "ambiguous"}
@@ -27,25 +25,7 @@ class Verdict(C.Structure):
 def build(csrc=None, out=None):
     """the host library; csrc: where the lowerings and behaviour.h come from (default: the product's; a copy with one line edited is
     how the mutants are built), out: where the library goes"""
-    out = out or BEHSHIM_DIR / "_build"
-    out.mkdir(exist_ok=True)
-    so = out / "libbehshim.so"
-    csrc = csrc or helpers.ROOT / "tla_rust_amd" / "csrc"
-    shim = helpers.build_shim()
-    srcs = [BEHSHIM_DIR / "behshim.cpp", shim] + list(csrc.glob("*.h")) + [helpers.ROOT / "include" / "tlamc.h"]
-
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    with open(out / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"libbehshim.{os.getpid()}.so"
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(tmp), "-I", str(csrc), str(BEHSHIM_DIR / "behshim.cpp"),
-                            "-L", str(shim.parent), "-lshim", f"-Wl,-rpath,{shim.parent}"], check=True)
-            os.replace(tmp, so)
-    return so
+    return helpers.build_over_shim((out or BEHSHIM_DIR / "_build") / "libbehshim.so", BEHSHIM_DIR / "behshim.cpp", csrc)
 
 
 def load(so):
@@ -159,21 +139,14 @@ class Model:
 def build_device(mutant=0):
     """tests/_behshim/behshim.hip: k_behaviours over the lowering SpecHide, a library of its own (hipcc cross-compiles gfx950 without a
     GPU); mutant 1 / 2 / 3: the kernel with one thing broken"""
-    from seenshim import _build
-    csrc = helpers.ROOT / "tla_rust_amd" / "csrc"
-    include = helpers.ROOT / "include"
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     src = BEHSHIM_DIR / "behshim.hip"
-    # (the flags of tla_rust_amd/build.py's `common`)
-    return _build(BEHSHIM_DIR / "_build" / f"libbehdev{mutant}.so", [src, include / "tlamc.h"] + list(csrc.glob("*.h")),
-                  [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result", f"-DBEH_MUTANT={mutant}",
-                   "-I", str(include), "-I", str(csrc), "-shared", "-x", "hip", str(src)])
+    return testlib.build_library(BEHSHIM_DIR / "_build" / f"libbehdev{mutant}.so",
+                                 testlib.hip_argv(f"-DBEH_MUTANT={mutant}", "-I", helpers.ROOT / "include", "-I", testlib.CSRC, src),
+                                 [src] + testlib.product_deps(testlib.CSRC))
 
 
 def build_devices():
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(4) as pool:   # (the threads wait for one hipcc each)
-        return list(pool.map(build_device, range(4)))
+    return list(testlib.build_mutants(range(4), build_device).values())
 
 
 class HideModel:

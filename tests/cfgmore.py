@@ -259,8 +259,8 @@ def gen_check(prog):
     generated code against the interpreter with the cfg's statements on every reachable state and slot (helpers.gen_check's route)"""
     import ctypes as C
     import hashlib
-    import os
-    import subprocess
+
+    import testlib
 
     class Handle:
         h = prog.params[0]
@@ -269,14 +269,7 @@ def gen_check(prog):
     srcs = [root / "tests" / "_cfgmore" / "harness_cfg.cpp", root / "tests" / "_gen" / "harness.cpp", csrc / "spec_gen.h", csrc / "spec_vm.h", csrc / "spec_vm_cfg.h"]
     tag = hashlib.sha256((text + "".join(s.read_text() for s in srcs)).encode()).hexdigest()[:16]
     out = root / "tests" / "_cfgmore" / "_build"
-    out.mkdir(exist_ok=True)
-    so, hdr = out / f"libgen_{tag}.so", out / f"gen_{tag}.h"
-    if not so.exists():
-        hdr.write_text(text)
-        tmp = out / f"libgen_{tag}.{os.getpid()}.tmp"
-        subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-w", "-I", str(csrc), "-I", str(root / "include"), f'-DGEN_HEADER="{hdr}"',
-                        "-o", str(tmp), str(srcs[0])], check=True)
-        os.replace(tmp, so)
+    so = testlib.build_generated(out / f"libgen_{tag}.so", out / f"gen_{tag}.h", text, [srcs[0]])
     C.CDLL(str(helpers.build_shim()), mode=C.RTLD_GLOBAL)   # the interpreter's host helpers (vm_make_params, ...) live in the front-end
     lib = C.CDLL(str(so))
     lib.gen_check.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(helpers.GenCheck)]

@@ -11,9 +11,6 @@ to the end of the level in which an Assert first fails, else the whole graph.
 
 The library is built on first use, like tests/covshim.py's, and linked against helpers' libshim.so."""
 import ctypes as C
-import fcntl
-import os
-import subprocess
 import sys
 
 import helpers
@@ -33,25 +30,7 @@ class ContOut(C.Structure):
 
 def build_contshim(csrc=None, out=None):
     """csrc: the directory the lowerings and violations.h are taken from (default: the product's; a copy with one edit is a mutant)"""
-    out = out or CONTSHIM_DIR / "_build"
-    out.mkdir(exist_ok=True)
-    so = out / "libcontshim.so"
-    csrc = csrc or helpers.ROOT / "tla_rust_amd" / "csrc"
-    shim = helpers.build_shim()
-    srcs = [CONTSHIM_DIR / "contshim.cpp", shim] + list(csrc.glob("*.h")) + [helpers.ROOT / "include" / "tlamc.h"]
-
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    with open(out / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"libcontshim.{os.getpid()}.so"
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(tmp), "-I", str(csrc), str(CONTSHIM_DIR / "contshim.cpp"),
-                            "-L", str(shim.parent), "-lshim", f"-Wl,-rpath,{shim.parent}"], check=True)
-            os.replace(tmp, so)
-    return so
+    return helpers.build_over_shim((out or CONTSHIM_DIR / "_build") / "libcontshim.so", CONTSHIM_DIR / "contshim.cpp", csrc)
 
 
 def load(so):

@@ -3,9 +3,6 @@ oracle's state graph says the counts must be.
 
 The library is built on first use, like tests/simwalk.py's, and linked against helpers' libshim.so."""
 import ctypes as C
-import fcntl
-import os
-import subprocess
 from collections import Counter
 
 import helpers
@@ -16,25 +13,7 @@ MAX_BINS = 512   # coverage.h COV_MAX_BINS
 
 def build_covshim(csrc=None, out=None):
     """csrc: the directory the lowerings and coverage.h are taken from (default: the product's; a copy with one edit is a mutant)"""
-    out = out or COVSHIM_DIR / "_build"
-    out.mkdir(exist_ok=True)
-    so = out / "libcovshim.so"
-    csrc = csrc or helpers.ROOT / "tla_rust_amd" / "csrc"
-    shim = helpers.build_shim()
-    srcs = [COVSHIM_DIR / "covshim.cpp", shim] + list(csrc.glob("*.h")) + [helpers.ROOT / "include" / "tlamc.h"]
-
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    with open(out / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"libcovshim.{os.getpid()}.so"
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(tmp), "-I", str(csrc), str(COVSHIM_DIR / "covshim.cpp"),
-                            "-L", str(shim.parent), "-lshim", f"-Wl,-rpath,{shim.parent}"], check=True)
-            os.replace(tmp, so)
-    return so
+    return helpers.build_over_shim((out or COVSHIM_DIR / "_build") / "libcovshim.so", COVSHIM_DIR / "covshim.cpp", csrc)
 
 
 def load(so):

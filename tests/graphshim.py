@@ -3,9 +3,6 @@ edge multiset the oracle's state graph says it must be.
 
 The library is built on first use, like tests/covshim.py's, and linked against helpers' libshim.so."""
 import ctypes as C
-import fcntl
-import os
-import subprocess
 from collections import Counter
 
 import helpers
@@ -15,25 +12,7 @@ GRAPHSHIM_DIR = helpers.ROOT / "tests" / "_graphshim"
 
 def build_graphshim(csrc=None, out=None):
     """csrc: the directory the lowerings and graph.h are taken from (default: the product's; a copy with one edit is a mutant)"""
-    out = out or GRAPHSHIM_DIR / "_build"
-    out.mkdir(exist_ok=True)
-    so = out / "libgraphshim.so"
-    csrc = csrc or helpers.ROOT / "tla_rust_amd" / "csrc"
-    shim = helpers.build_shim()
-    srcs = [GRAPHSHIM_DIR / "graphshim.cpp", shim] + list(csrc.glob("*.h")) + [helpers.ROOT / "include" / "tlamc.h"]
-
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    with open(out / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"libgraphshim.{os.getpid()}.so"
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(tmp), "-I", str(csrc), str(GRAPHSHIM_DIR / "graphshim.cpp"),
-                            "-L", str(shim.parent), "-lshim", f"-Wl,-rpath,{shim.parent}"], check=True)
-            os.replace(tmp, so)
-    return so
+    return helpers.build_over_shim((out or GRAPHSHIM_DIR / "_build") / "libgraphshim.so", GRAPHSHIM_DIR / "graphshim.cpp", csrc)
 
 
 def load(so):

@@ -8,6 +8,8 @@ import os
 import subprocess
 from pathlib import Path
 
+import testlib
+
 ROOT = Path(__file__).resolve().parent.parent
 ORACLE_DIR = ROOT / "oracle"
 SHIM_DIR = ROOT / "tests" / "_shim"
@@ -146,43 +148,28 @@ class ShimResult(C.Structure):
 
 
 def build_shim():
-    out = SHIM_DIR / "_build"
-    out.mkdir(exist_ok=True)
-    so = out / "libshim.so"
     csrc = ROOT / "tla_rust_amd" / "csrc"
-    pcal = [csrc / "pcal.cpp", csrc / "pcal_compile.cpp", csrc / "pcal_codegen.cpp"]  # the PlusCal front-end is host code: linked as is
-    srcs = [SHIM_DIR / "shim.cpp"] + pcal + list(csrc.glob("*.h")) + [ROOT / "include" / "tlamc.h"]
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    # several ranks of a multi-process test may arrive here together: one builds (into a temporary name, renamed when
-    # complete), the others wait for the lock and find the library fresh
-    import fcntl
-    with open(out / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"libshim.{os.getpid()}.so"
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(tmp), str(SHIM_DIR / "shim.cpp")] + [str(x) for x in pcal],
-                           check=True)
-            os.replace(tmp, so)
-    return so
+    pcal = [csrc / f for f in testlib.FRONT_END]  # the PlusCal front-end is host code: linked as is
+    return testlib.build_library(SHIM_DIR / "_build" / "libshim.so", testlib.host_argv("-O2", SHIM_DIR / "shim.cpp", *pcal),
+                                 [SHIM_DIR / "shim.cpp"] + pcal + testlib.product_deps(csrc))
+
+
+def build_over_shim(so, src, csrc=None, more=(), deps=()):
+    """a host library of tests/_*/: `src` (g++ -O2, no HIP) over the headers of `csrc` (default: the product's; a copy with one edit is a
+    mutant), linked against build_shim()'s library for the PlusCal front-end"""
+    csrc = csrc or ROOT / "tla_rust_amd" / "csrc"
+    shim = build_shim()
+    return testlib.build_library(so, testlib.host_argv("-O2", "-I", csrc, *more, src, "-L", shim.parent, "-lshim", f"-Wl,-rpath,{shim.parent}"),
+                                 [src, shim, *deps] + testlib.product_deps(csrc))
 
 
 def build_tlaeval_door():
     """tests/_tlaeval: the host evaluator of the product (tla_rust_amd/csrc/tlaeval.cpp) behind a test-only door, so that it can be
     run on module texts the product itself never evaluates on the host (the ones with a GPU lowering)"""
     d = ROOT / "tests" / "_tlaeval"
-    out = d / "_build"
-    out.mkdir(exist_ok=True)
-    so = out / "libtlaeval_door.so"
     csrc = ROOT / "tla_rust_amd" / "csrc"
     srcs = [d / "door.cpp", csrc / "tlaeval.cpp", csrc / "tlaeval.h"]
-    if not so.exists() or any(so.stat().st_mtime < s.stat().st_mtime for s in srcs):
-        tmp = out / f"libtlaeval_door.{os.getpid()}.so"
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(tmp), str(srcs[0]), str(srcs[1]), "-lpthread"], check=True)
-        os.replace(tmp, so)
-    return so
+    return testlib.build_library(d / "_build" / "libtlaeval_door.so", testlib.host_argv("-O2", srcs[0], srcs[1], "-lpthread"), srcs)
 
 
 def tlaeval_run(tla, cfg, search=(), max_levels=0, deadlock=True, dump=None, order=(), symmetry=True):
@@ -199,17 +186,9 @@ def tlaeval_run(tla, cfg, search=(), max_levels=0, deadlock=True, dump=None, ord
 
 def build_fakerccl():
     """tests/_fakerccl: the librccl stand-in that lets P ranks of the hip-rccl back-end share ONE GPU ($TLAMC_RCCL)"""
-    d = ROOT / "tests" / "_fakerccl"
-    out = d / "_build"
-    out.mkdir(exist_ok=True)
-    so = out / "libfakerccl.so"
-    src = d / "fakerccl.cpp"
-    if not so.exists() or so.stat().st_mtime < src.stat().st_mtime:
-        tmp = out / f"libfakerccl.{os.getpid()}.so"
-        subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(tmp), str(src),
-                        "-lpthread", "-lrt"], check=True)
-        os.replace(tmp, so)
-    return so
+    src = ROOT / "tests" / "_fakerccl" / "fakerccl.cpp"
+    return testlib.build_library(src.parent / "_build" / "libfakerccl.so",
+                                 [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O2", "-std=c++17", "-fPIC", "-shared", src, "-lpthread", "-lrt"], [src])
 
 
 _shim = None
@@ -292,16 +271,9 @@ def gen_check(prog, max_states=0):
     import hashlib
     text = program_codegen(prog)
     out = ROOT / "tests" / "_gen" / "_build"
-    out.mkdir(exist_ok=True)
     defs = os.environ.get("GEN_CHECK_DEFS", "").split()   # (e.g. -DMC_GEN_FP_SUM=1: the A/B forms of spec_gen.h)
     tag = hashlib.sha256((text + (ROOT / "tests" / "_gen" / "harness.cpp").read_text() + (ROOT / "tla_rust_amd" / "csrc" / "spec_gen.h").read_text() + " ".join(defs)).encode()).hexdigest()[:16]
-    so, hdr = out / f"libgen_{tag}.so", out / f"gen_{tag}.h"
-    if not so.exists():
-        hdr.write_text(text)
-        tmp = out / f"libgen_{tag}.{os.getpid()}.tmp"
-        subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-w", "-I", str(ROOT / "tla_rust_amd" / "csrc"), "-I", str(ROOT / "include"),
-                        f'-DGEN_HEADER="{hdr}"', *defs, "-o", str(tmp), str(ROOT / "tests" / "_gen" / "harness.cpp")], check=True)
-        os.replace(tmp, so)
+    so = testlib.build_generated(out / f"libgen_{tag}.so", out / f"gen_{tag}.h", text, [*defs, ROOT / "tests" / "_gen" / "harness.cpp"])
     C.CDLL(str(build_shim()), mode=C.RTLD_GLOBAL)   # the interpreter's host helpers (vm_make_params, ...) live in the front-end
     lib = C.CDLL(str(so))
     lib.gen_check.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(GenCheck)]

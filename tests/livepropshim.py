@@ -1,9 +1,6 @@
 """Host build of the rule for <>Q, []<>Q, <>[]P and P ~> Q (tests/_livepropshim: tla_rust_amd/csrc/liveness.h built with g++ over the
 compiled-program lowering, no HIP).  Built on first use, like tests/liveshim.py's library, and linked against helpers' libshim.so."""
 import ctypes as C
-import fcntl
-import os
-import subprocess
 
 import helpers
 
@@ -12,25 +9,7 @@ SHIM_DIR = helpers.ROOT / "tests" / "_livepropshim"
 
 def build(csrc=None, out=None):
     """csrc: the directory the lowerings and liveness.h are taken from (default: the product's; a copy with one edit is a mutant)"""
-    out = out or SHIM_DIR / "_build"
-    out.mkdir(exist_ok=True)
-    so = out / "liblivepropshim.so"
-    csrc = csrc or helpers.ROOT / "tla_rust_amd" / "csrc"
-    shim = helpers.build_shim()
-    srcs = [SHIM_DIR / "livepropshim.cpp", shim] + list(csrc.glob("*.h")) + [helpers.ROOT / "include" / "tlamc.h"]
-
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    with open(out / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"liblivepropshim.{os.getpid()}.so"
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(tmp), "-I", str(csrc), str(SHIM_DIR / "livepropshim.cpp"),
-                            "-L", str(shim.parent), "-lshim", f"-Wl,-rpath,{shim.parent}"], check=True)
-            os.replace(tmp, so)
-    return so
+    return helpers.build_over_shim((out or SHIM_DIR / "_build") / "liblivepropshim.so", SHIM_DIR / "livepropshim.cpp", csrc)
 
 
 def load(so):

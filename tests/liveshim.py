@@ -1,9 +1,6 @@
 """Host build of the Termination rule (tests/_liveshim: tla_rust_amd/csrc/liveness.h built with g++ over the compiled-program lowering,
 no HIP).  Built on first use, like tests/graphshim.py's library, and linked against helpers' libshim.so."""
 import ctypes as C
-import fcntl
-import os
-import subprocess
 
 import helpers
 
@@ -12,25 +9,7 @@ LIVESHIM_DIR = helpers.ROOT / "tests" / "_liveshim"
 
 def build_liveshim(csrc=None, out=None):
     """csrc: the directory the lowerings and liveness.h are taken from (default: the product's; a copy with one edit is a mutant)"""
-    out = out or LIVESHIM_DIR / "_build"
-    out.mkdir(exist_ok=True)
-    so = out / "libliveshim.so"
-    csrc = csrc or helpers.ROOT / "tla_rust_amd" / "csrc"
-    shim = helpers.build_shim()
-    srcs = [LIVESHIM_DIR / "liveshim.cpp", shim] + list(csrc.glob("*.h")) + [helpers.ROOT / "include" / "tlamc.h"]
-
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    with open(out / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"libliveshim.{os.getpid()}.so"
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(tmp), "-I", str(csrc), str(LIVESHIM_DIR / "liveshim.cpp"),
-                            "-L", str(shim.parent), "-lshim", f"-Wl,-rpath,{shim.parent}"], check=True)
-            os.replace(tmp, so)
-    return so
+    return helpers.build_over_shim((out or LIVESHIM_DIR / "_build") / "libliveshim.so", LIVESHIM_DIR / "liveshim.cpp", csrc)
 
 
 def load(so):

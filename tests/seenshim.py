@@ -3,13 +3,11 @@ library of its own without libtlamc.so): the probers in every form, k_probe, k_p
 model produced (tests/seenmodel.py).  Built on first use, like tests/sgraph.py's library; hipcc cross-compiles gfx950 without a GPU, loading
 the library needs none either.  host_lib() is graph.h's seen_find alone, built with g++ and no HIP."""
 import ctypes as C
-import fcntl
-import os
-import subprocess
 
 import numpy as np
 
 import helpers
+import testlib
 
 SHIM_DIR = helpers.ROOT / "tests" / "_seenshim"
 CSRC = helpers.ROOT / "tla_rust_amd" / "csrc"
@@ -18,42 +16,21 @@ FORM_NAMES = {PLAIN: "plain", BLIND: "blind", PRE: "pre", SLOW: "slow", KPROBE: 
 DEV_ETABLE = 1
 
 
-def _build(so, srcs, cmd):
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    so.parent.mkdir(parents=True, exist_ok=True)
-    with open(so.parent / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = so.parent / f"{so.stem}.{os.getpid()}.so"
-            subprocess.run(cmd + ["-o", str(tmp)], check=True)
-            os.replace(tmp, so)
-    return so
-
-
 def build(csrc=None, out=None):
     """csrc: the directory engine_kernels.h, graph.h and the headers they include are taken from (default: the product's; a copy with one
     edit is a mutant); out: where the library goes"""
-    out = out or SHIM_DIR / "_build"
     csrc = csrc or CSRC
     include = csrc.parent.parent / "include"   # (spec_registry.h includes ../../include/tlamc.h: a copy of csrc brings its own)
-    srcs = [SHIM_DIR / "seenshim.hip", include / "tlamc.h"] + list(csrc.glob("*.h"))
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    # (the flags of tla_rust_amd/build.py's `common`)
-    return _build(out / "libseenshim.so", srcs,
-                  [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result",
-                   "-I", str(include), "-I", str(csrc), "-shared", "-x", "hip", str(SHIM_DIR / "seenshim.hip")])
+    return testlib.build_library((out or SHIM_DIR / "_build") / "libseenshim.so", testlib.hip_argv("-I", include, "-I", csrc, SHIM_DIR / "seenshim.hip"),
+                                 [SHIM_DIR / "seenshim.hip"] + testlib.product_deps(csrc))
 
 
 def build_host(csrc=None, out=None):
     """graph.h's seen_find over host memory: g++, no HIP"""
-    out = out or SHIM_DIR / "_build"
     csrc = csrc or CSRC
-    srcs = [SHIM_DIR / "seenshim.hip", csrc.parent.parent / "include" / "tlamc.h"] + list(csrc.glob("*.h"))
-    return _build(out / "libseenfind.so", srcs,
-                  ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-DSEENSHIM_HOST", "-I", str(csrc), "-x", "c++", str(SHIM_DIR / "seenshim.hip")])
+    return testlib.build_library((out or SHIM_DIR / "_build") / "libseenfind.so",
+                                 testlib.host_argv("-O2", "-DSEENSHIM_HOST", "-I", csrc, "-x", "c++", SHIM_DIR / "seenshim.hip"),
+                                 [SHIM_DIR / "seenshim.hip"] + testlib.product_deps(csrc))
 
 
 _u64p, _u32p, _u16p, _u8p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)

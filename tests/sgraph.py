@@ -3,13 +3,11 @@ into a library of its own, without libtlamc.so): the strongly-connected-componen
 and the two device scans on CSR arrays that no search of a model produced (tests/randgraph.py).  Built on first use, like
 tests/livepropshim.py's library; hipcc cross-compiles gfx950 without a GPU, loading the library needs none either."""
 import ctypes as C
-import fcntl
-import os
-import subprocess
 
 import numpy as np
 
 import helpers
+import testlib
 
 SHIM_DIR = helpers.ROOT / "tests" / "_sgraph"
 CSRC = helpers.ROOT / "tla_rust_amd" / "csrc"
@@ -39,28 +37,14 @@ class LiveCheckInfo(C.Structure):
 def build(csrc=None, out=None):
     """csrc: the directory state_graph.hip, engine_live.h and the headers they include are taken from (default: the product's; a copy
     with one edit is a mutant); out: where the library goes"""
-    out = out or SHIM_DIR / "_build"
-    out.mkdir(parents=True, exist_ok=True)
-    so = out / "libsgraph.so"
-    csrc = csrc or CSRC
-    include = csrc.parent.parent / "include"   # (state_graph.h includes ../../include/tlamc.h: a copy of csrc brings its own)
-    srcs = [SHIM_DIR / "sgraph.hip", csrc / "state_graph.hip", include / "tlamc.h"] + list(csrc.glob("*.h"))
+    return build_driver((out or SHIM_DIR / "_build") / "libsgraph.so", csrc or CSRC, [SHIM_DIR / "sgraph.hip"])
 
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    with open(out / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"libsgraph.{os.getpid()}.so"
-            hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-            # (the flags of tla_rust_amd/build.py's `common`)
-            subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result",
-                            "-I", str(include), "-I", str(csrc), "-shared", "-o", str(tmp),
-                            "-x", "hip", str(SHIM_DIR / "sgraph.hip"), str(csrc / "state_graph.hip")], check=True)
-            os.replace(tmp, so)
-    return so
+
+def build_driver(so, csrc, drivers):
+    """drivers[0] (which includes the rest of `drivers` whole) compiled together with csrc's state_graph.hip: sfgraph's and ufgraph's too"""
+    include = csrc.parent.parent / "include"   # (state_graph.h includes ../../include/tlamc.h: a copy of csrc brings its own)
+    return testlib.build_library(so, testlib.hip_argv("-I", include, "-I", csrc, drivers[0], csrc / "state_graph.hip"),
+                                 drivers + [csrc / "state_graph.hip"] + testlib.product_deps(csrc))
 
 
 def load(so):

@@ -8,12 +8,12 @@ Outputs the engine clears itself (slot_index, degree, pred) come back as the pas
 pre-filled (FILL*) and comes back whole, so that a test compares the positions a kernel must not write too; `intact` says that the guard
 zones around every written buffer are unchanged."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import helpers
-from seenshim import _build, _aligned_u64
+import testlib
+from seenshim import _aligned_u64
 
 SHIM_DIR = helpers.ROOT / "tests" / "_sideshim"
 CSRC = helpers.ROOT / "tla_rust_amd" / "csrc"
@@ -30,30 +30,20 @@ def words(prm):
     return HEAD + 2 * prm.max_slots
 
 
-def _sources(csrc):
-    include = csrc.parent.parent / "include"   # (spec_registry.h includes ../../include/tlamc.h: a copy of csrc brings its own)
-    return include, [SHIM_DIR / "spec_table.h", include / "tlamc.h"] + list(csrc.glob("*.h"))
-
-
 def build(csrc=None, out=None):
     """csrc: the directory the product's headers are taken from (default: the product's; a copy with one edit is a mutant); out: where
     the library goes"""
-    out = out or SHIM_DIR / "_build"
     csrc = csrc or CSRC
-    include, srcs = _sources(csrc)
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    # (the flags of tests/seenshim.py, which are those of tla_rust_amd/build.py's `common`)
-    return _build(out / "libsideshim.so", srcs + [SHIM_DIR / "sideshim.hip"],
-                  [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result",
-                   "-I", str(include), "-I", str(csrc), "-I", str(SHIM_DIR), "-shared", "-x", "hip", str(SHIM_DIR / "sideshim.hip")])
+    include = csrc.parent.parent / "include"   # (spec_registry.h includes ../../include/tlamc.h: a copy of csrc brings its own)
+    return testlib.build_library((out or SHIM_DIR / "_build") / "libsideshim.so",
+                                 testlib.hip_argv("-I", include, "-I", csrc, "-I", SHIM_DIR, SHIM_DIR / "sideshim.hip"),
+                                 [SHIM_DIR / "sideshim.hip", SHIM_DIR / "spec_table.h"] + testlib.product_deps(csrc))
 
 
 def build_host(csrc=None, out=None):
-    out = out or SHIM_DIR / "_build"
     csrc = csrc or CSRC
-    include, srcs = _sources(csrc)
-    return _build(out / "libsidehost.so", srcs + [SHIM_DIR / "sidehost.cpp"],
-                  ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", str(csrc), "-I", str(SHIM_DIR), str(SHIM_DIR / "sidehost.cpp")])
+    return testlib.build_library((out or SHIM_DIR / "_build") / "libsidehost.so", testlib.host_argv("-O2", "-I", csrc, "-I", SHIM_DIR, SHIM_DIR / "sidehost.cpp"),
+                                 [SHIM_DIR / "sidehost.cpp", SHIM_DIR / "spec_table.h"] + testlib.product_deps(csrc))
 
 
 _u64p, _u32p, _u16p, _i16p, _i8p, _intp = (C.POINTER(t) for t in (C.c_uint64, C.c_uint32, C.c_uint16, C.c_int16, C.c_int8, C.c_int))

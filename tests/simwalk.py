@@ -4,9 +4,6 @@ The library is built on first use (like helpers.build_shim); the PlusCal front-e
 helpers' libshim.so, which it is linked against (not loaded with RTLD_GLOBAL: the shim's host stand-ins of the product's symbols would then
 take the place of libtlamc's in every library loaded later, the generated-code engines of MC_F_JIT among them)."""
 import ctypes as C
-import fcntl
-import os
-import subprocess
 
 import helpers
 
@@ -22,25 +19,7 @@ class SimShimOut(C.Structure):
 def build_simshim(csrc=None, out=None):
     """the host walk library; csrc: the directory the lowerings and sim_walk.h are taken from (default: the product's; a copy of it
     with one edit is how tests/test_simulate_graph.py builds its mutants), out: where the library goes"""
-    out = out or SIMSHIM_DIR / "_build"
-    out.mkdir(exist_ok=True)
-    so = out / "libsimshim.so"
-    csrc = csrc or helpers.ROOT / "tla_rust_amd" / "csrc"
-    shim = helpers.build_shim()
-    srcs = [SIMSHIM_DIR / "simshim.cpp", shim] + list(csrc.glob("*.h")) + [helpers.ROOT / "include" / "tlamc.h"]
-
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    with open(out / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"libsimshim.{os.getpid()}.so"
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(tmp), "-I", str(csrc), str(SIMSHIM_DIR / "simshim.cpp"),
-                            "-L", str(shim.parent), "-lshim", f"-Wl,-rpath,{shim.parent}"], check=True)
-            os.replace(tmp, so)
-    return so
+    return helpers.build_over_shim((out or SIMSHIM_DIR / "_build") / "libsimshim.so", SIMSHIM_DIR / "simshim.cpp", csrc)
 
 
 _lib = None

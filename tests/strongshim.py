@@ -2,9 +2,6 @@
 over the compiled-program lowering, no HIP).  Built on first use, like tests/livepropshim.py's library, and linked against helpers'
 libshim.so."""
 import ctypes as C
-import fcntl
-import os
-import subprocess
 
 import helpers
 
@@ -13,25 +10,7 @@ SHIM_DIR = helpers.ROOT / "tests" / "_strongshim"
 
 def build(csrc=None, out=None):
     """csrc: the directory the lowerings and liveness.h are taken from (default: the product's; a copy with one edit is a mutant)"""
-    out = out or SHIM_DIR / "_build"
-    out.mkdir(parents=True, exist_ok=True)
-    so = out / "libstrongshim.so"
-    csrc = csrc or helpers.ROOT / "tla_rust_amd" / "csrc"
-    shim = helpers.build_shim()
-    srcs = [SHIM_DIR / "strongshim.cpp", shim] + list(csrc.glob("*.h")) + [helpers.ROOT / "include" / "tlamc.h"]
-
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    with open(out / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"libstrongshim.{os.getpid()}.so"
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(tmp), "-I", str(csrc), str(SHIM_DIR / "strongshim.cpp"),
-                            "-L", str(shim.parent), "-lshim", f"-Wl,-rpath,{shim.parent}"], check=True)
-            os.replace(tmp, so)
-    return so
+    return helpers.build_over_shim((out or SHIM_DIR / "_build") / "libstrongshim.so", SHIM_DIR / "strongshim.cpp", csrc)
 
 
 def load(so):

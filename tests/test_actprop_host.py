@@ -5,8 +5,6 @@ without such a property compiles to what it did; -continue's rules hold for a pa
 one-line mutants of the new code are each caught by the model written for it."""
 import ctypes as C
 import re
-import shutil
-import subprocess
 import sys
 from pathlib import Path
 
@@ -15,6 +13,7 @@ import pytest
 import actprop
 import cfgmore
 import helpers
+import testlib
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
@@ -266,25 +265,10 @@ MUTANTS = {
 def test_mutants_of_the_new_code_are_caught(tmp_path):
     """each mutant is a whole front end + interpreter of its own (tests/_actshim's library with the front end compiled in, built from a
     copy of the sources with one edit); the model is compiled BY the mutant and searched by it"""
-    from concurrent.futures import ThreadPoolExecutor
-    csrc = ROOT / "tla_rust_amd" / "csrc"
-
     def build(name):
-        file, old, new, _ = MUTANTS[name]
-        text = (csrc / file).read_text()
-        assert text.count(old) == 1, name
-        top = tmp_path / name
-        d = top / "tla_rust_amd" / "csrc"
-        d.mkdir(parents=True)
-        for f in list(csrc.glob("*.h")) + [csrc / "pcal.cpp", csrc / "pcal_compile.cpp", csrc / "pcal_codegen.cpp"]:
-            shutil.copy(f, d / f.name)
-        (top / "include").mkdir()
-        shutil.copy(ROOT / "include" / "tlamc.h", top / "include" / "tlamc.h")
-        (d / file).write_text(text.replace(old, new))
-        return actprop.build_actshim(csrc=d, out=top / "act", own_front_end=True)
-    with ThreadPoolExecutor(len(MUTANTS)) as pool:   # (the threads wait for g++)
-        libs = dict(zip(MUTANTS, pool.map(build, MUTANTS)))
-    for name, so in libs.items():
+        d = testlib.mutant_tree(tmp_path, name, MUTANTS[name][:3], also=testlib.FRONT_END)
+        return actprop.build_actshim(csrc=d, out=tmp_path / name / "act", own_front_end=True)
+    for name, so in testlib.build_mutants(MUTANTS, build).items():
         model = MUTANTS[name][3]
         L = actprop.actshim_lib(so)
         L.actshim_compile.restype = C.c_void_p

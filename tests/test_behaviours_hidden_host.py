@@ -5,7 +5,6 @@ rejected one step short; H = 0 is the flag-less call and a full mask makes H irr
 rejected; the path with the hidden states in it is a path of the graph; the cases of the test lowering (tests/behgap.py) give the
 figures worked out by hand; seven one-line mutants of behaviour.h each fail a named case.  Nothing here needs a GPU."""
 import random
-import shutil
 import subprocess
 from functools import lru_cache
 
@@ -17,6 +16,7 @@ import behgap
 import behshim
 import helpers
 import test_behaviours_host as host
+import testlib
 
 ROOT = helpers.ROOT
 SB = ROOT / "specs_behaviours"
@@ -231,26 +231,12 @@ MUTANTS = {
 
 
 def test_mutants_are_caught(tmp_path):
-    from concurrent.futures import ThreadPoolExecutor
-    csrc = ROOT / "tla_rust_amd" / "csrc"
-    text = (csrc / "behaviour.h").read_text()
     helpers.build_shim()
 
     def build(name):
-        old, new, _ = MUTANTS[name]
-        assert text.count(old) == 1, name
-        d = tmp_path / name / "tla_rust_amd" / "csrc"   # (spec_registry.h includes ../../include/tlamc.h)
-        d.mkdir(parents=True)
-        for h in csrc.glob("*.h"):
-            shutil.copy(h, d / h.name)
-        (tmp_path / name / "include").mkdir()
-        shutil.copy(ROOT / "include" / "tlamc.h", tmp_path / name / "include" / "tlamc.h")
-        (d / "behaviour.h").write_text(text.replace(old, new))
-        return behgap.build_host(csrc=d, out=tmp_path / name / "_build")
-    with ThreadPoolExecutor(len(MUTANTS)) as pool:   # (the threads wait for one g++ each)
-        libs = dict(zip(MUTANTS, pool.map(build, MUTANTS)))
+        return behgap.build_host(csrc=testlib.mutant_tree(tmp_path, name, ("behaviour.h", *MUTANTS[name][:2])), out=tmp_path / name / "_build")
     good = behgap.GapModel()
-    for name, so in libs.items():
+    for name, so in testlib.build_mutants(MUTANTS, build).items():
         bad = behgap.GapModel()
         bad.L = behgap.load_host(so)
         case, batch, hidden, _, want = behgap.GAP_CASES[MUTANTS[name][2]]

@@ -6,7 +6,6 @@ headers state; mc_state_parse is the inverse of mc_state_format on every reachab
 -behaviours` refuses the options it does not go with.  Five one-line mutants of behaviour.h are each caught by a named case.
 
 Nothing here needs a GPU; tests/test_gpu_behaviours.py checks that the device kernel gives what this host build gives."""
-import shutil
 import sys
 from functools import lru_cache
 from pathlib import Path
@@ -17,6 +16,7 @@ import behaviours
 import behshim
 import helpers
 import simgraph
+import testlib
 
 ROOT = helpers.ROOT
 sys.path.insert(0, str(ROOT / "oracle"))
@@ -355,25 +355,11 @@ MUTANTS = {
 
 
 def test_mutants_are_caught(tmp_path):
-    from concurrent.futures import ThreadPoolExecutor
-    csrc = ROOT / "tla_rust_amd" / "csrc"
-    text = (csrc / "behaviour.h").read_text()
     helpers.build_shim()
 
     def build(name):
-        old, new, _ = MUTANTS[name]
-        assert text.count(old) == 1, name
-        d = tmp_path / name / "tla_rust_amd" / "csrc"   # (spec_registry.h includes ../../include/tlamc.h)
-        d.mkdir(parents=True)
-        for h in csrc.glob("*.h"):
-            shutil.copy(h, d / h.name)
-        (tmp_path / name / "include").mkdir()
-        shutil.copy(ROOT / "include" / "tlamc.h", tmp_path / name / "include" / "tlamc.h")
-        (d / "behaviour.h").write_text(text.replace(old, new))
-        return behshim.build(csrc=d, out=tmp_path / name / "_build")
-    with ThreadPoolExecutor(len(MUTANTS)) as pool:   # (the threads wait for one g++ each)
-        libs = dict(zip(MUTANTS, pool.map(build, MUTANTS)))
+        return behshim.build(csrc=testlib.mutant_tree(tmp_path, name, ("behaviour.h", *MUTANTS[name][:2])), out=tmp_path / name / "_build")
     good = named_cases()
-    for name, so in libs.items():
+    for name, so in testlib.build_mutants(MUTANTS, build).items():
         bad = named_cases(behshim.load(so))
         assert bad[MUTANTS[name][2]] != good[MUTANTS[name][2]], f"mutant {name} survives its case"

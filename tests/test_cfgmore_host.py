@@ -13,6 +13,7 @@ import pytest
 
 import cfgmore
 import helpers
+import testlib
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
@@ -262,31 +263,17 @@ MUTANTS = {
 
 
 def test_mutants_of_the_new_code_are_caught(tmp_path):
-    from concurrent.futures import ThreadPoolExecutor
-    csrc = ROOT / "tla_rust_amd" / "csrc"
-    text = (csrc / "spec_vm_cfg.h").read_text()
-
     def build(name):
-        old, new, _ = MUTANTS[name]
-        assert text.count(old) == 1, name
         top = tmp_path / name
-        d = top / "tla_rust_amd" / "csrc"
-        d.mkdir(parents=True)
-        for f in list(csrc.glob("*.h")) + [csrc / "pcal.cpp", csrc / "pcal_compile.cpp", csrc / "pcal_codegen.cpp"]:
-            shutil.copy(f, d / f.name)
-        (top / "include").mkdir()
-        shutil.copy(ROOT / "include" / "tlamc.h", top / "include" / "tlamc.h")
-        (top / "tests" / "_shim").mkdir(parents=True)
+        d = testlib.mutant_tree(tmp_path, name, ("spec_vm_cfg.h", *MUTANTS[name][:2]), also=testlib.FRONT_END)
+        (top / "tests" / "_shim").mkdir(parents=True)   # (shim.cpp includes ../../tla_rust_amd/csrc/...: the copy reads the mutant's)
         shutil.copy(ROOT / "tests" / "_shim" / "shim.cpp", top / "tests" / "_shim" / "shim.cpp")
-        (d / "spec_vm_cfg.h").write_text(text.replace(old, new))
         so = top / "libshim_mutant.so"
         # (-Bsymbolic: the mutant's own copies of the interpreter's functions, whatever library of the same names the process has loaded)
         subprocess.run(["g++", "-O0", "-std=c++17", "-fPIC", "-shared", "-w", "-Wl,-Bsymbolic", "-o", str(so), str(top / "tests" / "_shim" / "shim.cpp"),
                         str(d / "pcal.cpp"), str(d / "pcal_compile.cpp"), str(d / "pcal_codegen.cpp")], check=True)
         return so
-    with ThreadPoolExecutor(len(MUTANTS)) as pool:   # (the threads wait for one g++ each)
-        libs = dict(zip(MUTANTS, pool.map(build, MUTANTS)))
-    for name, so in libs.items():
+    for name, so in testlib.build_mutants(MUTANTS, build).items():
         run = tmp_path / name / "run"
         run.mkdir()
         with pytest.raises(AssertionError) as e:

@@ -8,13 +8,13 @@ Mutants of violations.h (test_mutants_are_killed builds each and asserts that it
   outside-is-state       an outside successor counts as a stored state  outside_only: Under gets states, loses outside
   fatal-not-separated    every flagged pair ends the search             pcal_intro: the run ends at the first MoneyInvariant level
 """
-import shutil
 import subprocess
 
 import pytest
 
 import contshim
 import helpers
+import testlib
 
 ROOT = helpers.ROOT
 SSI_NAMES = ["WellFormed", "CorrectnessOfHoldingXLocks", "CorrectnessOfWaitingForXLock", "CorrectReadView", "FirstCommitterWins", "CahillOK",
@@ -128,25 +128,11 @@ MUTANTS = {
 
 
 def test_mutants_are_killed(tmp_path):
-    from concurrent.futures import ThreadPoolExecutor
-    csrc = ROOT / "tla_rust_amd" / "csrc"
     helpers.build_shim()
 
     def build(name):
-        header, old, new, _, _ = MUTANTS[name]
-        text = (csrc / header).read_text()
-        assert text.count(old) == 1, name
-        d = tmp_path / name / "tla_rust_amd" / "csrc"   # (spec_registry.h includes ../../include/tlamc.h)
-        d.mkdir(parents=True)
-        for h in csrc.glob("*.h"):
-            shutil.copy(h, d / h.name)
-        (tmp_path / name / "include").mkdir()
-        shutil.copy(ROOT / "include" / "tlamc.h", tmp_path / name / "include" / "tlamc.h")
-        (d / header).write_text(text.replace(old, new))
-        return contshim.build_contshim(csrc=d, out=tmp_path / name / "_build")
-    with ThreadPoolExecutor(len(MUTANTS)) as pool:   # (the threads wait for one g++ each)
-        libs = dict(zip(MUTANTS, pool.map(build, MUTANTS)))
-    for name, so in libs.items():
+        return contshim.build_contshim(csrc=testlib.mutant_tree(tmp_path, name, MUTANTS[name][:3]), out=tmp_path / name / "_build")
+    for name, so in testlib.build_mutants(MUTANTS, build).items():
         _, _, _, (kind, model), says = MUTANTS[name]
         d = tmp_path / name / "run"
         d.mkdir()

@@ -10,13 +10,13 @@ Mutants of the headers (test_mutants_are_killed builds each and asserts that `su
   ids-swapped           atomic_add's Increment and Check swap ids       atomic_add: Increment 1, Check 12
   vote-is-increase      Voting's VoteFor slots counted as IncreaseMaxBal   Voting
 """
-import shutil
 from pathlib import Path
 
 import pytest
 
 import covshim
 import helpers
+import testlib
 
 ROOT = helpers.ROOT
 RAFT = [2, 2, 2, 9, 1, 1]
@@ -89,25 +89,11 @@ MUTANTS = {
 
 
 def test_mutants_are_killed(tmp_path):
-    from concurrent.futures import ThreadPoolExecutor
-    csrc = ROOT / "tla_rust_amd" / "csrc"
     helpers.build_shim()
 
     def build(name):
-        header, old, new, _, _ = MUTANTS[name]
-        text = (csrc / header).read_text()
-        assert text.count(old) == 1, name
-        d = tmp_path / name / "tla_rust_amd" / "csrc"   # (spec_registry.h includes ../../include/tlamc.h)
-        d.mkdir(parents=True)
-        for h in csrc.glob("*.h"):
-            shutil.copy(h, d / h.name)
-        (tmp_path / name / "include").mkdir()
-        shutil.copy(ROOT / "include" / "tlamc.h", tmp_path / name / "include" / "tlamc.h")
-        (d / header).write_text(text.replace(old, new))
-        return covshim.build_covshim(csrc=d, out=tmp_path / name / "_build")
-    with ThreadPoolExecutor(len(MUTANTS)) as pool:   # (the threads wait for one g++ each)
-        libs = dict(zip(MUTANTS, pool.map(build, MUTANTS)))
-    for name, so in libs.items():
+        return covshim.build_covshim(csrc=testlib.mutant_tree(tmp_path, name, MUTANTS[name][:3]), out=tmp_path / name / "_build")
+    for name, so in testlib.build_mutants(MUTANTS, build).items():
         _, _, _, model, says = MUTANTS[name]
         d = tmp_path / name / "run"
         d.mkdir()

@@ -258,9 +258,10 @@ def test_parent_words_model():
 # ------------------------------------------------------------------------------------------------- the cases of the step calls' tests
 def test_the_mutants_are_single_edits_of_the_kernels():
     from test_gpu_exchange import MUTANTS
-    import xchgshim
-    text = (xchgshim.CSRC / "engine_kernels.h").read_text()
-    assert len(MUTANTS) >= 4 and all(text.count(old) == 1 and old != new for old, new in MUTANTS.values())
+    import testlib
+    assert len(MUTANTS) >= 4
+    for old, new in MUTANTS.values():
+        testlib.mutant_texts(("engine_kernels.h", old, new))   # (asserts it)
 
 
 @pytest.mark.parametrize("name", list(__import__("shardref").CASES))

@@ -4,14 +4,13 @@ buffer: what the kernel must not write holds its pre-fill, and the guard zones a
 tests/test_exchange_reference.py checks the model and that these cases hold the edges they are meant to hold.  At the end: four edits of
 engine_kernels.h, each caught by a test here that the product passes."""
 import functools
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-import helpers
 import xchgmodel as M
 import xchgshim as X
+from testlib import build_mutants, mutant_tree, survives
 
 pytestmark = pytest.mark.gpu
 
@@ -165,42 +164,15 @@ MUTANTS = {
 }
 
 
-def write_if_changed(path, text):
-    if not path.exists() or path.read_text() != text:   # (an unchanged copy keeps its time: the library built from it stays fresh)
-        path.write_text(text)
-
-
 @functools.lru_cache(maxsize=None)
 def mutant_libraries():
-    csrc = X.CSRC
-    text = (csrc / "engine_kernels.h").read_text()
-    top = X.SHIM_DIR / "_build" / "mutants"
-
-    def build(name):
-        old, new = MUTANTS[name]
-        assert text.count(old) == 1, name
-        d = top / name / "tla_rust_amd" / "csrc"   # (spec_registry.h includes ../../include/tlamc.h)
-        d.mkdir(parents=True, exist_ok=True)
-        (top / name / "include").mkdir(exist_ok=True)
-        for f in csrc.glob("*.h"):
-            write_if_changed(d / f.name, text.replace(old, new) if f.name == "engine_kernels.h" else f.read_text())
-        write_if_changed(top / name / "include" / "tlamc.h", (helpers.ROOT / "include" / "tlamc.h").read_text())
-        return X.build(csrc=d, out=top / name)
-    with ThreadPoolExecutor(len(MUTANTS)) as pool:   # (the threads wait for one hipcc each)
-        return dict(zip(MUTANTS, pool.map(build, MUTANTS)))
+    top = X.SHIM_DIR / "_build" / "mutants"   # (kept between runs: an unchanged mutant stays fresh)
+    return build_mutants(MUTANTS, lambda name: X.build(csrc=mutant_tree(top, name, ("engine_kernels.h", *MUTANTS[name])), out=top / name))
 
 
 @pytest.fixture(scope="module")
 def mutants():
     return {name: X.load(so) for name, so in mutant_libraries().items()}
-
-
-def survives(compare):
-    try:
-        compare()
-    except AssertionError:
-        return False
-    return True
 
 
 def test_a_moved_owner_boundary_is_caught(mutants):

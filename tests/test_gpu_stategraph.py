@@ -7,16 +7,15 @@ which it shows to answer "violated" and "holds" about equally often on exactly t
 What this does NOT cover: the kernels that build the CSR arrays from the arena (engine_graph.h, k_live_proc, k_live_pred) and the front
 end's classification of properties; the model-based tests (test_gpu_graph, test_gpu_liveness, test_gpu_liveprops) keep those."""
 import functools
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-import helpers
 import livegraph
 import liveprops
 import randgraph as R
 import sgraph
+from testlib import build_mutants, mutant_tree, survives
 
 pytestmark = pytest.mark.gpu
 ALL_SCC = [("any",) + c for c in R.SCC_CASES] + [("bfs",) + c for c in R.LIVE_CASES]
@@ -282,37 +281,14 @@ MUTANTS = {
 }
 
 
-def write_if_changed(path, text):
-    if not path.exists() or path.read_text() != text:   # (an unchanged copy keeps its time: the library built from it stays fresh)
-        path.write_text(text)
-
-
 @pytest.fixture(scope="module")
 def mutants():
-    csrc = sgraph.CSRC
-    text = (csrc / "engine_live.h").read_text()
-    top = sgraph.SHIM_DIR / "_build" / "mutants"
+    top = sgraph.SHIM_DIR / "_build" / "mutants"   # (kept between runs: an unchanged mutant stays fresh)
 
     def build(name):
-        old, new = MUTANTS[name]
-        assert text.count(old) == 1, name
-        d = top / name / "tla_rust_amd" / "csrc"   # (state_graph.h includes ../../include/tlamc.h)
-        d.mkdir(parents=True, exist_ok=True)
-        (top / name / "include").mkdir(exist_ok=True)
-        for f in [csrc / "state_graph.hip"] + list(csrc.glob("*.h")):
-            write_if_changed(d / f.name, text.replace(old, new) if f.name == "engine_live.h" else f.read_text())
-        write_if_changed(top / name / "include" / "tlamc.h", (helpers.ROOT / "include" / "tlamc.h").read_text())
+        d = mutant_tree(top, name, ("engine_live.h", *MUTANTS[name]), also=["state_graph.hip"])
         return sgraph.load(sgraph.build(csrc=d, out=top / name))
-    with ThreadPoolExecutor(len(MUTANTS)) as pool:   # (the threads wait for one hipcc each)
-        return dict(zip(MUTANTS, pool.map(build, MUTANTS)))
-
-
-def survives(compare):
-    try:
-        compare()
-    except AssertionError:
-        return False
-    return True
+    return build_mutants(MUTANTS, build)
 
 
 def test_a_wrong_component_id_is_caught(mutants):

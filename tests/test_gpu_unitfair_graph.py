@@ -5,18 +5,17 @@ and which tests/test_unitfair_reference.py holds against the definition over eve
 
 What this does NOT cover: k_live_unit<S> and the front end's unit map (tests/test_gpu_labelfair.py keeps those)."""
 import functools
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-import helpers
 import sfrandgraph
 import sgraph
 import strongfair
 import ufgraph
 import ufrandgraph as R
 import unitfair
+from testlib import build_mutants, mutant_tree
 
 pytestmark = pytest.mark.gpu
 CASES = R.RELABEL_CASES + R.ONION_CASES
@@ -232,28 +231,13 @@ MUTANTS = {
 MUTANT_CASES = [("ring_perm", 64, 2, 2, 3, 0.1, "mixed", False), ("ring_perm", 64, 2, 2, 1, 0.1, "plus", True), ("cycle_chain", 65, 1, 2, 3, 0.1, "mixed", False)]
 
 
-def write_if_changed(path, text):
-    if not path.exists() or path.read_text() != text:
-        path.write_text(text)
-
-
 @pytest.fixture(scope="module")
 def mutants():
-    csrc = ufgraph.CSRC
-    top = ufgraph.SHIM_DIR / "_build" / "mutants"
+    top = ufgraph.SHIM_DIR / "_build" / "mutants"   # (kept between runs: an unchanged mutant stays fresh)
 
     def build(name):
-        which, old, new = MUTANTS[name]
-        assert (csrc / which).read_text().count(old) == 1, name
-        d = top / name / "tla_rust_amd" / "csrc"   # (state_graph.h includes ../../include/tlamc.h)
-        d.mkdir(parents=True, exist_ok=True)
-        (top / name / "include").mkdir(exist_ok=True)
-        for f in [csrc / "state_graph.hip"] + list(csrc.glob("*.h")):
-            write_if_changed(d / f.name, f.read_text().replace(old, new) if f.name == which else f.read_text())
-        write_if_changed(top / name / "include" / "tlamc.h", (helpers.ROOT / "include" / "tlamc.h").read_text())
-        return ufgraph.load(ufgraph.build(csrc=d, out=top / name))
-    with ThreadPoolExecutor(len(MUTANTS)) as pool:   # (the threads wait for one hipcc each)
-        return dict(zip(MUTANTS, pool.map(build, MUTANTS)))
+        return ufgraph.load(ufgraph.build(csrc=mutant_tree(top, name, MUTANTS[name], also=["state_graph.hip"]), out=top / name))
+    return build_mutants(MUTANTS, build)
 
 
 def run_all(L):

@@ -9,13 +9,12 @@ Mutants of graph.h (test_mutants_are_killed builds each and asserts that the che
   selfloop-dropped      the edge rule drops self loops                 raft / pcal_intro: the stuttering edges are short
   flagged-looked-up     a failed Assert's key is looked up             the README's pcal_intro: 220 edges to states the failed steps never reached, 110 keys "missing"
 """
-import shutil
-
 import pytest
 
 import covshim
 import graphshim
 import helpers
+import testlib
 
 ROOT = helpers.ROOT
 RAFT = [2, 2, 2, 9, 1, 1]
@@ -86,25 +85,11 @@ MUTANTS = {
 
 
 def test_mutants_are_killed(tmp_path, tmp_path_factory):
-    from concurrent.futures import ThreadPoolExecutor
-    csrc = ROOT / "tla_rust_amd" / "csrc"
     helpers.build_shim()
-    text = (csrc / "graph.h").read_text()
 
     def build(name):
-        old, new, _, _ = MUTANTS[name]
-        assert text.count(old) == 1, name
-        d = tmp_path / name / "tla_rust_amd" / "csrc"   # (spec_registry.h includes ../../include/tlamc.h)
-        d.mkdir(parents=True)
-        for h in csrc.glob("*.h"):
-            shutil.copy(h, d / h.name)
-        (tmp_path / name / "include").mkdir()
-        shutil.copy(ROOT / "include" / "tlamc.h", tmp_path / name / "include" / "tlamc.h")
-        (d / "graph.h").write_text(text.replace(old, new))
-        return graphshim.build_graphshim(csrc=d, out=tmp_path / name / "_build")
-    with ThreadPoolExecutor(len(MUTANTS)) as pool:   # (the threads wait for one g++ each)
-        libs = dict(zip(MUTANTS, pool.map(build, MUTANTS)))
-    for name, so in libs.items():
+        return graphshim.build_graphshim(csrc=testlib.mutant_tree(tmp_path, name, ("graph.h", *MUTANTS[name][:2])), out=tmp_path / name / "_build")
+    for name, so in testlib.build_mutants(MUTANTS, build).items():
         _, _, model, says = MUTANTS[name]
         spec, params, oparams, deadlock = MODELS[model]
         d = tmp_path / name / "run"

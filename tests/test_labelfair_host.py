@@ -207,28 +207,14 @@ MUTANTS = {
 
 
 def test_mutants_of_the_new_host_code_are_caught(amd, tmp_path):
-    import shutil
-    from concurrent.futures import ThreadPoolExecutor
-
+    import testlib
     import unitshim
-    csrc = ROOT / "tla_rust_amd" / "csrc"
 
     def build(name):
-        which, old, new, _ = MUTANTS[name]
-        d = tmp_path / name / "tla_rust_amd" / "csrc"   # (the headers include ../../include/tlamc.h)
-        shutil.copytree(csrc, d, ignore=shutil.ignore_patterns("*.hip"))
-        src = unitshim.SHIM_DIR / "unitshim.cpp" if which == "unitshim.cpp" else d / which
-        text = src.read_text()
-        assert text.count(old) == 1, name
-        dst = tmp_path / name / "unitshim.cpp" if which == "unitshim.cpp" else d / which
-        dst.write_text(text.replace(old, new))
-        (tmp_path / name / "include").mkdir()
-        shutil.copy(ROOT / "include" / "tlamc.h", tmp_path / name / "include" / "tlamc.h")
-        return unitshim.build(csrc=d, out=tmp_path / name / "build", shim_src=dst if which == "unitshim.cpp" else None)
-    named = list(MUTANTS)
-    with ThreadPoolExecutor(len(named)) as pool:   # (the threads wait for one g++ each)
-        libs = dict(zip(named, pool.map(build, named)))
-    for name in named:
+        d = testlib.mutant_tree(tmp_path, name, MUTANTS[name][:3], also=(*testlib.FRONT_END, unitshim.SHIM_DIR / "unitshim.cpp"))
+        return unitshim.build(csrc=d, out=tmp_path / name / "build", shim_src=d / "unitshim.cpp" if MUTANTS[name][0] == "unitshim.cpp" else None)
+    libs = testlib.build_mutants(MUTANTS, build)
+    for name in libs:
         (tmp_path / name / "run").mkdir()
         with pytest.raises(AssertionError) as e:
             check_shim(MUTANTS[name][3], tmp_path / name / "run", L=unitshim.load(libs[name]))

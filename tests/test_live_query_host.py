@@ -4,13 +4,11 @@ then every refusal, one defect per row, with the words the engine, the graph pas
 
 The shapes: 3 process instances; a table of 4 units and 3 conjuncts; 2 predicates."""
 import ctypes as C
-import fcntl
-import os
-import subprocess
 
 import pytest
 
 import helpers
+import testlib
 
 SHIM_DIR = helpers.ROOT / "tests" / "_queryshim"
 CSRC = helpers.ROOT / "tla_rust_amd" / "csrc"
@@ -25,22 +23,8 @@ class FairUnits(C.Structure):
 
 
 def build():
-    out = SHIM_DIR / "_build"
-    out.mkdir(parents=True, exist_ok=True)
-    so = out / "libqueryshim.so"
-    srcs = [SHIM_DIR / "queryshim.cpp", helpers.ROOT / "include" / "tlamc.h"] + list(CSRC.glob("*.h"))
-
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    with open(out / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"libqueryshim.{os.getpid()}.so"
-            subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-o", str(tmp), "-I", str(CSRC), str(SHIM_DIR / "queryshim.cpp")], check=True)
-            os.replace(tmp, so)
-    return so
+    return testlib.build_library(SHIM_DIR / "_build" / "libqueryshim.so", testlib.host_argv("-O1", "-I", CSRC, SHIM_DIR / "queryshim.cpp"),
+                                 [SHIM_DIR / "queryshim.cpp"] + testlib.product_deps(CSRC))
 
 
 @pytest.fixture(scope="module")

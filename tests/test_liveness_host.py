@@ -143,28 +143,13 @@ MUTANTS = {
 
 
 def test_mutants_of_the_rule_are_caught(tmp_path):
-    import shutil
-    from concurrent.futures import ThreadPoolExecutor
-
     import liveshim
-    csrc = ROOT / "tla_rust_amd" / "csrc"
+    import testlib
     helpers.build_shim()
-    text = (csrc / "liveness.h").read_text()
 
     def build(name):
-        old, new, _ = MUTANTS[name]
-        assert text.count(old) == 1, name
-        d = tmp_path / name / "tla_rust_amd" / "csrc"   # (spec_registry.h includes ../../include/tlamc.h)
-        d.mkdir(parents=True)
-        for h in csrc.glob("*.h"):
-            shutil.copy(h, d / h.name)
-        (tmp_path / name / "include").mkdir()
-        shutil.copy(ROOT / "include" / "tlamc.h", tmp_path / name / "include" / "tlamc.h")
-        (d / "liveness.h").write_text(text.replace(old, new))
-        return liveshim.build_liveshim(csrc=d, out=tmp_path / name / "_build")
-    with ThreadPoolExecutor(len(MUTANTS)) as pool:   # (the threads wait for one g++ each)
-        libs = dict(zip(MUTANTS, pool.map(build, MUTANTS)))
-    for name, so in libs.items():
+        return liveshim.build_liveshim(csrc=testlib.mutant_tree(tmp_path, name, ("liveness.h", *MUTANTS[name][:2])), out=tmp_path / name / "_build")
+    for name, so in testlib.build_mutants(MUTANTS, build).items():
         run = tmp_path / name / "run"
         run.mkdir()
         with pytest.raises(AssertionError) as e:

@@ -17,6 +17,8 @@ from pathlib import Path
 
 import pytest
 
+import testlib
+
 ROOT = Path(__file__).resolve().parent.parent
 DIR = ROOT / "tests" / "_packshim"
 CSRC = ROOT / "tla_rust_amd" / "csrc"
@@ -27,15 +29,8 @@ T3_KEYS16 = [3, 4, 3, 3, 1, 1, 16, 2, 4, 16]
 
 
 def build():
-    out = DIR / "_build"
-    out.mkdir(exist_ok=True)
-    exe = out / "packshim"
-    srcs = [DIR / "packshim.cpp", CSRC / "spec_raft.h", CSRC / "spec_raft_packed.h", CSRC / "mc_common.h"]
-    if not exe.exists() or any(exe.stat().st_mtime < s.stat().st_mtime for s in srcs):
-        tmp = out / "packshim.tmp"
-        subprocess.run(["g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-o", str(tmp), str(DIR / "packshim.cpp")], check=True)
-        tmp.replace(exe)
-    return exe
+    return testlib.build_library(DIR / "_build" / "packshim", ["g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", DIR / "packshim.cpp"],
+                                 [DIR / "packshim.cpp", CSRC / "spec_raft.h", CSRC / "spec_raft_packed.h", CSRC / "mc_common.h"])
 
 
 def run(*args):

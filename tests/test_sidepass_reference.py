@@ -9,7 +9,9 @@ import pytest
 import seenmodel as SM
 import sidemodel as M
 import sideshim as X
-from test_gpu_sidepasses import MUTANTS, check_coverage, check_graph, check_violations, graph_want, mutant_libraries, survives
+import testlib
+from test_gpu_sidepasses import MUTANTS, check_coverage, check_graph, check_violations, graph_want, mutant_libraries
+from testlib import survives
 
 CASES = M.cases()
 
@@ -43,8 +45,8 @@ def test_a_wrong_model_is_caught(mutant, monkeypatch):
 
 def test_the_device_shim_and_its_mutants_compile():
     assert X.build().exists()
-    for which, old, new in MUTANTS.values():
-        assert (X.CSRC / which).read_text().count(old) == 1 and old != new
+    for edit in MUTANTS.values():
+        testlib.mutant_texts(edit)   # (asserts that its text occurs once and that the replacement differs)
     assert len(MUTANTS) >= 5 and all(so.exists() for so in mutant_libraries().values())
 
 

@@ -23,7 +23,6 @@ Mutants of sim_walk.h (test_mutants_are_killed builds each and asserts that `sui
 The test asserts that each mutant dies of the failure named here (MUTANTS' third column), not of any failure.
 """
 import random
-import shutil
 import sys
 from collections import Counter
 from functools import lru_cache
@@ -34,6 +33,7 @@ import pytest
 import helpers
 import simgraph
 import simwalk
+import testlib
 
 ROOT = helpers.ROOT
 sys.path.insert(0, str(ROOT / "oracle"))
@@ -294,26 +294,12 @@ def test_the_product_passes_the_short_suite(tmp_path):
 
 
 def test_mutants_are_killed(tmp_path):
-    from concurrent.futures import ThreadPoolExecutor
-    csrc = ROOT / "tla_rust_amd" / "csrc"
-    text = (csrc / "sim_walk.h").read_text()
     helpers.build_shim()
 
     def build(name):
-        old, new, _ = MUTANTS[name]
-        assert text.count(old) == 1, name
-        d = tmp_path / name / "tla_rust_amd" / "csrc"   # (spec_registry.h includes ../../include/tlamc.h)
-        d.mkdir(parents=True)
-        for h in csrc.glob("*.h"):
-            shutil.copy(h, d / h.name)
-        (tmp_path / name / "include").mkdir()
-        shutil.copy(ROOT / "include" / "tlamc.h", tmp_path / name / "include" / "tlamc.h")
-        (d / "sim_walk.h").write_text(text.replace(old, new))
-        return simwalk.build_simshim(csrc=d, out=tmp_path / name / "_build")
-    with ThreadPoolExecutor(len(MUTANTS)) as pool:   # (the threads wait for one g++ each)
-        libs = dict(zip(MUTANTS, pool.map(build, MUTANTS)))
+        return simwalk.build_simshim(csrc=testlib.mutant_tree(tmp_path, name, ("sim_walk.h", *MUTANTS[name][:2])), out=tmp_path / name / "_build")
     killed_by = {}
-    for name, so in libs.items():
+    for name, so in testlib.build_mutants(MUTANTS, build).items():
         with pytest.raises(AssertionError) as e:
             suite(tmp_path, simwalk.load(so))
             pytest.fail(f"mutant {name} survives", pytrace=False)

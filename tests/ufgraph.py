@@ -2,9 +2,6 @@
 (tests/_ufgraph/ufgraph.hip, which includes tests/_sfgraph/sfgraph.hip whole, compiled together with tla_rust_amd/csrc/state_graph.hip
 into a library of its own, without libtlamc.so).  Built on first use; hipcc cross-compiles gfx950 without a GPU."""
 import ctypes as C
-import fcntl
-import os
-import subprocess
 
 import numpy as np
 
@@ -32,28 +29,8 @@ def fair_units(of_unit, nunits, nconj, weak, strong):
 def build(csrc=None, out=None):
     """csrc: where state_graph.hip, engine_live.h and their headers are taken from (a copy with one edit is a mutant); out: where the
     library goes"""
-    out = out or SHIM_DIR / "_build"
-    out.mkdir(parents=True, exist_ok=True)
-    so = out / "libufgraph.so"
-    csrc = csrc or CSRC
-    include = csrc.parent.parent / "include"
-    srcs = [SHIM_DIR / "ufgraph.hip", sfgraph.SHIM_DIR / "sfgraph.hip", sgraph.SHIM_DIR / "sgraph.hip", csrc / "state_graph.hip", include / "tlamc.h"] + \
-        list(csrc.glob("*.h"))
-
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    with open(out / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"libufgraph.{os.getpid()}.so"
-            hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-            subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result",
-                            "-I", str(include), "-I", str(csrc), "-shared", "-o", str(tmp),
-                            "-x", "hip", str(SHIM_DIR / "ufgraph.hip"), str(csrc / "state_graph.hip")], check=True)
-            os.replace(tmp, so)
-    return so
+    return sgraph.build_driver((out or SHIM_DIR / "_build") / "libufgraph.so", csrc or CSRC,
+                               [SHIM_DIR / "ufgraph.hip", sfgraph.SHIM_DIR / "sfgraph.hip", sgraph.SHIM_DIR / "sgraph.hip"])
 
 
 def load(so):

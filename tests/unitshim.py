@@ -2,11 +2,9 @@
 units built with g++ over the interpreter lowering, no HIP; pcal.cpp / pcal_compile.cpp are compiled in, so that a copy of csrc with one
 edit is a mutant of the front end too).  Built on first use."""
 import ctypes as C
-import fcntl
-import os
-import subprocess
 
 import helpers
+import testlib
 
 SHIM_DIR = helpers.ROOT / "tests" / "_unitshim"
 
@@ -19,26 +17,11 @@ class FairUnits(C.Structure):
 def build(csrc=None, out=None, shim_src=None):
     """csrc: the directory the front end, the lowerings and liveness.h are taken from (default: the product's; a copy with one edit is
     a mutant); shim_src: unitshim.cpp or an edited copy"""
-    out = out or SHIM_DIR / "_build"
-    out.mkdir(parents=True, exist_ok=True)
-    so = out / "libunitshim.so"
-    csrc = csrc or helpers.ROOT / "tla_rust_amd" / "csrc"
+    csrc = csrc or testlib.CSRC
     shim_src = shim_src or SHIM_DIR / "unitshim.cpp"
-    front = [csrc / "pcal.cpp", csrc / "pcal_compile.cpp", csrc / "pcal_codegen.cpp"]
-    srcs = [shim_src] + front + list(csrc.glob("*.h")) + [helpers.ROOT / "include" / "tlamc.h"]
-
-    def fresh():
-        return so.exists() and all(so.stat().st_mtime >= s.stat().st_mtime for s in srcs)
-    if fresh():
-        return so
-    with open(out / ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not fresh():
-            tmp = out / f"libunitshim.{os.getpid()}.so"
-            subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wl,-Bsymbolic", "-o", str(tmp), "-I", str(csrc), str(shim_src)] +
-                           [str(x) for x in front], check=True)
-            os.replace(tmp, so)
-    return so
+    front = [csrc / f for f in testlib.FRONT_END]
+    return testlib.build_library((out or SHIM_DIR / "_build") / "libunitshim.so", testlib.host_argv("-O1", "-Wl,-Bsymbolic", "-I", csrc, shim_src, *front),
+                                 [shim_src] + front + testlib.product_deps(csrc))
 
 
 def load(so):

@@ -5,12 +5,11 @@ use with the flags of tests/seenshim.py; hipcc cross-compiles gfx950 without a G
 Every output is handed in pre-filled (FILL64 / FILL32 / ...) and comes back whole, so that a test compares the positions the kernel must
 not write too; `intact` says that the guard zones around every written buffer are unchanged."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import helpers
-from seenshim import _build
+import testlib
 
 SHIM_DIR = helpers.ROOT / "tests" / "_xchgshim"
 CSRC = helpers.ROOT / "tla_rust_amd" / "csrc"
@@ -22,15 +21,10 @@ FILL8, FILL16, FILL32, FILL64 = 0xa7, 0xa7a7, 0xa7a7a7a7, 0xa7a7a7a7a7a7a7a7   #
 def build(csrc=None, out=None):
     """csrc: the directory engine_kernels.h and the headers it needs are taken from (default: the product's; a copy with one edit is a
     mutant); out: where the library goes"""
-    out = out or SHIM_DIR / "_build"
     csrc = csrc or CSRC
     include = csrc.parent.parent / "include"   # (spec_registry.h includes ../../include/tlamc.h: a copy of csrc brings its own)
-    srcs = [SHIM_DIR / "xchgshim.hip", include / "tlamc.h"] + list(csrc.glob("*.h"))
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    # (the flags of tests/seenshim.py, which are those of tla_rust_amd/build.py's `common`)
-    return _build(out / "libxchgshim.so", srcs,
-                  [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result",
-                   "-I", str(include), "-I", str(csrc), "-shared", "-x", "hip", str(SHIM_DIR / "xchgshim.hip")])
+    return testlib.build_library((out or SHIM_DIR / "_build") / "libxchgshim.so", testlib.hip_argv("-I", include, "-I", csrc, SHIM_DIR / "xchgshim.hip"),
+                                 [SHIM_DIR / "xchgshim.hip"] + testlib.product_deps(csrc))
 
 
 _u64p, _u32p, _u16p, _u8p, _intp = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), C.POINTER(C.c_int)

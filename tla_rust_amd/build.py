@@ -13,6 +13,10 @@ CLI = OUT / "mc"
 
 SOURCES = ["engine.hip", "frontend.cpp"]
 
+# How every device source of the product is compiled.  The test libraries that build the product's kernels outside the product
+# (tests/testlib.hip_argv) take the same list; build() adds its environment-driven extras to its own copy only.
+HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
+
 # What each object of engine.hip depends on: ENGINE_BASE for every unit, ENGINE_OWN[tu] for the lowerings the unit instantiates kernels of
 # (engine.hip includes every spec header through spec_registry.h; a unit's code changes only with its own).  state_graph.hip, the host
 # half of what consumes the state graph's CSR arrays, is one object for all of them: the spec units never see engine_live.h.
@@ -43,8 +47,7 @@ def build(force=False, verbose=False):
     # engine.hip is compiled once per group of specs (MC_TU = 1..7) plus once for the C ABI (MC_TU = 0), in
     # parallel: the unrolled per-spec kernels dominate compile time.  Each object is rebuilt only when one of the
     # files it really depends on changed (a TU instantiates the kernels of its own spec header only).
-    common = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result",
-              "-I", str(PKG.parent / "include")]
+    common = [hipcc] + HIP_FLAGS + ["-I", str(PKG.parent / "include")]
     if os.environ.get("TLAMC_LINE_TABLES"):  # source lines for rocprofv3's PC sampling (profiles/pcsample.sh); code generation unchanged
         common.append("-gline-tables-only")
     if os.environ.get("TLAMC_EXTRA_DEFS"):   # A/B builds: extra -D flags (e.g. -DMC_NT_PARENT), space-separated
